@@ -20,6 +20,11 @@ rank 0's JSON line and exits non-zero if any child fails.  The line carries `rcc
 counted BY the collective (all-reduce of ones; ncclCommCount of the library's own communicator for the in-library leg),
 the RCCL version, one device per rank, per-rank step times.
 
+A plain run sets up, warms up, times `--steps` steps and prints the line.  `--full` adds the legs the headline does not
+need: the K = 1 single-block latency and, at N = 1, the same workload as one persistent launch (`dataflow`) and the CPU
+baseline.  `--dump-outputs DIR` writes the decrypted outputs of the last timed step to DIR/outputs.npy; keys, input bits
+and input ciphertexts are seeded, so the same arguments give the same inputs in every run.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -137,6 +142,26 @@ def cpu_baseline(circuit_path, paramset, method, seconds_budget=20.0):
                           walked, len(rounds), os.path.basename(circuit_path), boots, paramset, method, cores, t_used, checked)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, outputs):
+    """outputs[k] = Outputs(k) of the last timed step (one list of bits per output value) -> DIR/outputs.npy, float32
+    [blocks][all output bits in header order].  Above DUMP_LIMIT_BYTES a fixed, seeded sample of the blocks is kept and
+    their indices go to DIR/outputs_rows.npy."""
+    bits = np.array([[b for bus in o for b in bus] for o in outputs], dtype=np.float32)
+    os.makedirs(dirname, exist_ok=True)
+    rows_path = os.path.join(dirname, "outputs_rows.npy")
+    if os.path.exists(rows_path):
+        os.remove(rows_path)
+    if bits.nbytes > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (bits.itemsize * bits.shape[1] + 8)     # a kept row and its float64 index
+        rows = np.sort(np.random.default_rng(0).choice(bits.shape[0], size=keep, replace=False))
+        bits = bits[rows]
+        np.save(rows_path, rows.astype(np.float64))
+    np.save(os.path.join(dirname, "outputs.npy"), bits)
+
+
 def spawn_ranks(n, argv):
     """Parent of a self-launched multi-GPU run: N child processes of this script, one rank per GPU, rendezvous
     on 127.0.0.1.  The parent never initialises the GPU (no torch import, no HIP call) and never execs."""
@@ -202,7 +227,15 @@ def main():
     ap.add_argument("--gates-timeout", type=int, default=540,
                     help="N > 1: watchdog (s, from the moment the fallback line exists) over the gate-sharded runs and the teardown")
     ap.add_argument("--gates-steps", type=int, default=2, help="N > 1: timed steps of the strong-scaling gate-sharded leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs the headline does not need: the K = 1 single-block latency, at N = 1 the same workload "
+                         "as one persistent launch (`dataflow`) and the CPU baseline; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/outputs.npy: the decrypted output bits "
+                         "Circuit.Clock() returns, one row per input block (float32; rank 0's blocks when N > 1)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config is not None:
         preset = {2: ("adder_64bit.txt", "STD128_OPT", "GINX", 256), 3: ("AES-expanded.txt", "STD128_OPT", "GINX", 32),
                   4: ("sha256_new.txt", "STD128_OPT", "GINX", 16), 5: ("AES-expanded.txt", "STD192", "AP", 8)}[args.config]
@@ -271,8 +304,8 @@ def main():
         if args.xor_fast:
             circ.setXorFast(True)
         gates = world > 1 and shard_mode == 1
-        if gates:
-            cc.set_encrypt_seed(0x0FE5EED)   # every rank must encrypt IDENTICAL input ciphertexts
+        # the same input ciphertexts from run to run (and, under gate sharding, on every rank)
+        cc.set_encrypt_seed(0x0FE5EED)
         circ.setRelevel(bool(relevel))
         schedule = schedule or args.schedule
         if schedule == "dataflow" and not gates:
@@ -345,7 +378,8 @@ def main():
         elapsed = time.time() - t0
         tm = cc.timing()
         # correctness of the timed work: decrypted outputs of every instance == plaintext evaluation
-        verified = [circ.Outputs(k)[0] for k in range(K_run)] == expect
+        outputs = [circ.Outputs(k) for k in range(K_run)]
+        verified = [o[0] for o in outputs] == expect
         st = circ.stats()
         total_boot = float(tm["bootstraps"])
         per_rank_s = [elapsed]
@@ -380,7 +414,7 @@ def main():
             identity = {"instances_checked": k_ident, "bootstrapped_registers_per_instance": per_inst,
                         "registers_held_over_all_ranks": int(t[0]), "identical_to_single_rank_evaluation": bool(float(tmx[1]) == 0.0)}
             verified = verified and identity["identical_to_single_rank_evaluation"]
-            cc.set_encrypt_seed(None)
+        cc.set_encrypt_seed(None)
         rccl_info = None
         if xch is not None and xch.in_library:
             try:
@@ -388,7 +422,7 @@ def main():
             except Exception as e:
                 rccl_info = {"error": repr(e)}
         circ.close()
-        return {"elapsed": elapsed, "total_boot": total_boot, "verified": verified, "tm": tm, "info": info, "relevel": relevel,
+        return {"elapsed": elapsed, "total_boot": total_boot, "verified": verified, "outputs": outputs, "tm": tm, "info": info, "relevel": relevel,
                 "K_run": K_run, "shard_mode": shard_mode if world > 1 else 0, "per_rank_ms_per_step": [round(x / steps * 1e3, 3) for x in per_rank_s],
                 "in_library_comm": rccl_info,
                 "launches_per_step": st["sublaunches"], "dataflow": df_active, "identity": identity,
@@ -475,6 +509,8 @@ def main():
         sys.stderr.write("bench.py: rank %d: headline run failed: %s\n" % (rank, R_err))
     if R is None:
         R, head_mode = REP, "instances"     # the fallback line (error field set below)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, R["outputs"])
     # also the end-to-end latency of ONE input block (K = 1: every dependent launch is a single narrow frontier)
     def single_block_latency():
         c1 = bce.Circuit(cc)
@@ -492,7 +528,7 @@ def main():
         dt = time.time() - t0
         c1.close()
         return dt
-    block_latency_s = None if (args.no_block_latency or (world > 1 and R is REP)) else single_block_latency()
+    block_latency_s = None if (not args.full or args.no_block_latency or (world > 1 and R is REP)) else single_block_latency()
 
     def load_profile(name):
         try:
@@ -747,7 +783,7 @@ def main():
                 out["rccl"]["rccl_version_seen_by_the_library"] = int(bce.lib().bce_rccl_version()) or None
             except Exception:
                 pass
-        if world == 1 and args.schedule == "steps" and R["relevel"] and not args.no_dataflow_leg and cc.dag_supported():
+        if args.full and world == 1 and args.schedule == "steps" and R["relevel"] and not args.no_dataflow_leg and cc.dag_supported():
             # the same workload as ONE persistent launch with device-side ready queues (identical registers); secondary: the
             # headline keeps the per-step launches its per-launch roofline evidence is collected on
             try:
@@ -758,7 +794,7 @@ def main():
                                    "outputs_verified": bool(D["verified"]), "scheduler": D["dag_last_run"]}
             except Exception as e:
                 out["dataflow"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(path, args.paramset, args.method, args.cpu_seconds)
         with emit_lock:
             emit()

@@ -39,6 +39,44 @@ def test_bench_rejects_mismatched_world_size():
     assert p.returncode != 0 and "does not match" in p.stderr
 
 
+def test_bench_rejects_zero_steps():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert p.returncode != 0 and "--steps must be at least 1" in p.stderr
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """A plain run carries no secondary legs; --dump-outputs writes the decrypted outputs of the last timed step, one row per
+    block: the seeded inputs of every block (np.random.default_rng(12345)) added correctly by adder_32bit."""
+    import numpy as np
+    p = _run(["--steps", "2", "--warmup", "0", "--circuit", "adder_32bit.txt", "--instances", "4",
+              "--dump-outputs", str(tmp_path / "out")], timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["config"]["outputs_verified"] is True
+    assert d["config"]["bootstraps_per_step"] == 4 * 310
+    assert "cpu_baseline" not in d and "dataflow" not in d and d["config"]["single_block_latency_s"] is None
+    got = np.load(tmp_path / "out" / "outputs.npy")
+    assert got.dtype == np.float32 and got.shape == (4, 33)
+    assert not (tmp_path / "out" / "outputs_rows.npy").exists()
+    rng = np.random.default_rng(12345)
+    for k in range(4):
+        a, b = (int("".join(map(str, rng.integers(0, 2, 32)[::-1])), 2) for _ in range(2))
+        assert sum(int(v) << i for i, v in enumerate(got[k])) == a + b, k
+
+
+@pytest.mark.gpu
+def test_bench_full_runs_the_secondary_legs():
+    p = _run(["--full", "--steps", "1", "--warmup", "0", "--circuit", "adder_32bit.txt", "--instances", "4", "--cpu-seconds", "2"],
+             timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == 1 and d["config"]["outputs_verified"] is True
+    assert d["config"]["single_block_latency_s"] > 0
+    assert d["dataflow"]["outputs_verified"] is True
+    assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["kind"] == "port"
+
+
 @pytest.mark.gpu
 def test_bench_gpus2_rehearsal_on_one_gpu():
     """N > 1: the line's `value` is north_star's partition (every step's gates split over the ranks, K x N blocks in

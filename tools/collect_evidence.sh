@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 cd "$R"
 if [ "$2" != "profile-only" ]; then
   python -m pytest tests -m gpu -x -q 2>&1 | tee "$OUT/gpu_tests.log" | tail -3
-  python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+  python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
   tail -c 600 "$OUT/bench.json"; echo
 fi
 export TMPDIR=/tmp
