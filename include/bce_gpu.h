@@ -249,6 +249,10 @@ int bce_bytes_per_bootstrap_parts(const bce_ctx*, uint64_t out[3]);
  * or 2 dG - 2 when this context keeps its key with the lowest gadget digit folded in (same accumulator words; the
  * decomposition is exact for the parameter set and the digit-0 rows multiply the accumulator itself) */
 uint32_t bce_forward_transforms_per_step(const bce_ctx*);
+/* 1 when saturated launches of this context run their forward transforms as quarter units, three per wave (folded
+ * N = 1024 GINX kernel at two workgroups per compute unit, even 2N / q); 0: whole-row + half-row bodies (other contexts,
+ * or BCE_FWD_UNITS=0 at context creation). */
+uint32_t bce_forward_units(const bce_ctx*);
 /* Launch granularity of this context's blind-rotation kernels, for callers that shape their frontiers (the host
  * scheduler of bce_circuit.h does): one bootstrap is one workgroup, so a call's time is a staircase in its size.
  * *lone = bootstraps up to which every workgroup has a compute unit to itself (one bootstrap latency per call),

@@ -60,7 +60,7 @@ ENGINE_SYMBOLS = [
     "bce_keygen", "bce_import_keys", "bce_import_keys_eval", "bce_export_bsk_eval", "bce_import_keys_file", "bce_export_keys_file", "bce_bsk_words", "bce_ksk_words", "bce_export_sk", "bce_export_bsk",
     "bce_export_ksk", "bce_pool_reserve", "bce_pool_slots", "bce_lwe_write", "bce_lwe_read",
     "bce_encrypt_bits", "bce_set_encrypt_seed", "bce_decrypt_bits", "bce_eval_gates", "bce_eval_gates_strided", "bce_synchronize",
-    "bce_timing_reset", "bce_timing_get", "bce_timing_set_events", "bce_bytes_per_bootstrap", "bce_bytes_per_bootstrap_parts", "bce_forward_transforms_per_step", "bce_launch_capacity", "bce_rccl_available", "bce_rccl_version", "bce_rccl_unique_id", "bce_rccl_init", "bce_rccl_allgather", "bce_rccl_comm_info",
+    "bce_timing_reset", "bce_timing_get", "bce_timing_set_events", "bce_bytes_per_bootstrap", "bce_bytes_per_bootstrap_parts", "bce_forward_transforms_per_step", "bce_forward_units", "bce_launch_capacity", "bce_rccl_available", "bce_rccl_version", "bce_rccl_unique_id", "bce_rccl_init", "bce_rccl_allgather", "bce_rccl_comm_info",
     "bce_rccl_shutdown", "bce_debug_eval_stages", "bce_debug_ntt", "bce_debug_tail",
     "bce_dag_supported", "bce_dag_create", "bce_dag_run", "bce_dag_destroy", "bce_dag_set_limits", "bce_dag_last_run", "bce_dag_debug_block_task",
     "bce_plan_create", "bce_plan_run_step", "bce_plan_run", "bce_plan_destroy",
@@ -123,6 +123,8 @@ def lib():
     L.bce_bytes_per_bootstrap_parts.argtypes = [vp, C.POINTER(u64)]
     L.bce_forward_transforms_per_step.argtypes = [vp]
     L.bce_forward_transforms_per_step.restype = C.c_uint32
+    L.bce_forward_units.argtypes = [vp]
+    L.bce_forward_units.restype = C.c_uint32
     L.bce_launch_capacity.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.bce_rccl_unique_id.argtypes = [C.c_char_p]
     L.bce_rccl_init.argtypes = [vp, C.c_char_p, i32, i32]
@@ -430,6 +432,10 @@ class BinFHEContext:
 
     def forward_transforms_per_step(self):
         return int(self._L.bce_forward_transforms_per_step(self.h))
+
+    def forward_units(self):
+        """1: saturated launches transform as 24 quarter units, three per wave; 0: whole-row + half-row bodies"""
+        return int(self._L.bce_forward_units(self.h))
 
     def launch_capacity(self):
         lone, full = C.c_uint32(), C.c_uint32()

@@ -254,6 +254,7 @@ int build_ctx(u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 baseG, u32 ba
     P.gBits = c->gBits; P.dG = c->dG; P.baseR = baseR; P.dR = c->dR;
     P.method_ap = method == BCE_AP ? 1 : 0;
     P.factor = (u32)(2 * N / q);
+    P.factor_even = (P.factor & 1u) ? 0 : 1;   // every STD128 set (q = N); the GINX MAC tail then needs no parity selects
     P.Q8p1 = (u32)(Q / 8 + 1);
     int bq = bit_length(Q);
     P.red_shift = (u32)std::max(2 * bq + 3 - 32, 0);
@@ -374,6 +375,11 @@ int build_ctx(u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 baseG, u32 ba
         const char* fo = std::getenv("BCE_FOLD");
         P.fold = (exact && has_kernel && !(fo && fo[0] == '0')) ? 1 : 0;
         P.fold_ninv = (BCE_KEY_NINV && P.fold && c->is64 && P.fp64) ? 1 : 0;
+        // forward transforms of the folded N = 1024 GINX kernel as quarter units (kernels.hip); that build is also compiled
+        // with the MAC tail of an even factor, so an odd factor keeps the whole-row + half-row bodies and the general tail.
+        // BCE_FWD_UNITS=0 keeps them everywhere (development / parity knob, same binary)
+        const char* fu = std::getenv("BCE_FWD_UNITS");
+        P.fwd_units = (P.fold && !c->is64 && c->method == BCE_GINX && P.factor_even && !(fu && fu[0] == '0')) ? 1 : 0;
     }
     P.pool_stride = n + 1;
     c->enc_seed_ok = os_entropy(c->enc_seed);
@@ -1521,6 +1527,7 @@ int bce_timing_get(bce_ctx* c, bce_timing* out) {
 }
 
 uint32_t bce_forward_transforms_per_step(const bce_ctx* c) { return c ? 2 * c->dG - (c->P.fold ? 2 : 0) : 0; }
+uint32_t bce_forward_units(const bce_ctx* c) { return c ? c->P.fwd_units : 0; }
 
 int bce_launch_capacity(const bce_ctx* c, uint32_t* lone, uint32_t* full) {
     if (!c || !lone || !full) return BCE_ERR_ARG;

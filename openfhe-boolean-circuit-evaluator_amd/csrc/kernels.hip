@@ -446,7 +446,8 @@ __device__ __forceinline__ void ntt_forward_wave_low8(u32* poly, const uint2* tw
 // 256-point sub-transforms left after the stages on bits 9 and 8.  64 lanes x 8 register pairs, three passes (bits
 // 7..5, 4..2, 1..0), two wave-local re-shuffles, in place: half the butterflies of ntt_forward_wave_low8 with every
 // lane busy.  The FOLD kernel transforms six rows per step with it: four whole rows on waves 0..3, two rows as four
-// halves on waves 4..7 -- 1.5 transforms on every SIMD.
+// halves on waves 4..7 -- 1.5 transforms on every SIMD (one workgroup per CU, AP, odd 2N / q; the two-workgroups-per-CU GINX
+// build runs ntt_forward_quarter3_low8 below instead).
 __device__ __forceinline__ void fwd_bfly_pair(u64& xa, u64& xb, uint2 w, u32 Q) {
     const u32 X = (u32)xa, Y = (u32)xb;
     const u64 t = mad64(__umulhi(Y, w.y), 0u - Q, mad64(Y, w.x, xa));
@@ -518,6 +519,108 @@ __device__ __forceinline__ void ntt_forward_half_low8(u32* row, u32 h, const uin
         for (int g = 0; g < 4; ++g) fwd_bfly_pair(xp[2 * g], xp[2 * g + 1], twf[tw_pos<512>((i1 << 1) | g)], Q);
         p[0] = make_uint4((u32)xp[0], (u32)xp[1], (u32)xp[2], (u32)xp[3]);
         p[1] = make_uint4((u32)xp[4], (u32)xp[5], (u32)xp[6], (u32)xp[7]);
+    }
+    wave_sync();
+}
+// The same eight stages as 24 QUARTER units, three per wave (FOLD kernel, two workgroups per CU).  After the stages on bits 9
+// and 8 every digit row is four independent 256-point transforms; quarter qr of a row is its positions [256 qr, +256), i.e.
+// the 272 padded words at 272 qr.  A wave takes the SAME quarter of three rows (`rows`, stride 2 NP: the digit rows of one
+// accumulator component), so that
+//   * all eight waves carry the same work: 48 butterflies per lane (the whole-row body has 64, the half-row body 40);
+//   * the three units share every twiddle (the twiddle of the stage on bit B is tw[2^(9-B) + (j >> (B+1))]: the row does not
+//     enter), and those of the first pass (bits 7, 6) are wave-uniform: w7, w6a, w6b arrive in SGPRs, read once per bootstrap;
+//   * the MAC of wave w reads quarter w & 3 of every row: what waves w & 3 and (w & 3) + 4 -- its own SIMD -- produce.
+// Four passes of two stages on 4 register pairs per row (register = the 2-bit field of the position index the pass works on),
+// three wave-local re-shuffles inside the quarter's own words.  Index i = b7..b0 inside the quarter; images (word offsets):
+//   in / out  i + 4 (i >> 6)                                   (phys; pass 1 reads 4-byte words, lane = b5..b0)
+//   A  (b7 b6 | b3 b2 b1 b0 | b5 b4)     B  (b5 b4 | b7 b6 b1 b0 | b3 b2)     C  (b3 b2 | b7 b6 b5 b4 | b1 b0)
+// i.e. the writing pass's register field on top (a 4-byte store of one register covers 64 consecutive words: at most the
+// 2-way conflict that costs a ds_write_b32 nothing), the reading pass's register field at the bottom, its two bits swapped
+// (ONE 16-byte read per lane and row at 16 * lane, conflict-free).  The last pass holds four consecutive positions per lane:
+// one 16-byte store per row into the layout the MAC reads.  Every load of a pass precedes its stores (data dependence, one
+// wave): in place.
+__device__ __forceinline__ u64 mad64_su(u32 a, u32 b_uniform, u64 c) {   // b in an SGPR (one scalar source per VOP3)
+    u64 r, carry;
+    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(carry) : "v"(a), "s"(b_uniform), "v"(c));
+    return r;
+}
+__device__ __forceinline__ void fwd_bfly_pair_su(u64& xa, u64& xb, uint2 w_uniform, u32 Q) {
+    const u32 X = (u32)xa, Y = (u32)xb;
+    const u64 t = mad64(__umulhi(Y, w_uniform.y), 0u - Q, mad64_su(Y, w_uniform.x, xa));
+    xb = with_lo(xb, (X << 1) + 2 * Q - (u32)t);
+    xa = t;
+}
+// two stages on the 4 register pairs of one unit: the upper bit pairs (0,2), (1,3) [wa], the lower (0,1) [wb0], (2,3) [wb1]
+template <bool SU>
+__device__ __forceinline__ void fwd_pass4_pair(u64 (&x)[4], uint2 wa, uint2 wb0, uint2 wb1, u32 Q) {
+    if constexpr (SU) {
+        fwd_bfly_pair_su(x[0], x[2], wa, Q); fwd_bfly_pair_su(x[1], x[3], wa, Q);
+        fwd_bfly_pair_su(x[0], x[1], wb0, Q); fwd_bfly_pair_su(x[2], x[3], wb1, Q);
+    } else {
+        fwd_bfly_pair(x[0], x[2], wa, Q); fwd_bfly_pair(x[1], x[3], wa, Q);
+        fwd_bfly_pair(x[0], x[1], wb0, Q); fwd_bfly_pair(x[2], x[3], wb1, Q);
+    }
+}
+__device__ __forceinline__ void ntt_forward_quarter3_low8(u32* rows, u32 qr, uint2 w7, uint2 w6a, uint2 w6b, const uint2* twf,
+                                                          u32 lane, u32 Q) {
+    constexpr int RS = 2 * Cfg<10>::NP;   // words between the three rows of a wave
+    u64 xp[3][4];
+    // a lane's 16 bytes hold its registers in the order 0, 2, 1, 3: the loaded register pairs (x0, x2) and (x1, x3) are then
+    // the addends of the pass's first butterflies as they stand (low half = X, the high half is ignored) and Y is their high
+    // half -- no register moves between the read and the arithmetic
+    auto pass16 = [&](uint2 wa, uint2 wb0, uint2 wb1) {
+        const uint4* const p = reinterpret_cast<const uint4*>(rows + 4 * lane);
+        uint4 v[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v[k] = p[k * (RS / 4)];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            xp[k][0] = ((u64)v[k].y << 32) | v[k].x; xp[k][2] = pair_of(v[k].y);
+            xp[k][1] = ((u64)v[k].w << 32) | v[k].z; xp[k][3] = pair_of(v[k].w);
+            fwd_pass4_pair<false>(xp[k], wa, wb0, wb1, Q);
+        }
+    };
+    auto store4 = [&](u32 off) {          // register r of every row to off + 64 r
+        u32* const p = rows + off;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) p[k * RS + 64 * r] = (u32)xp[k][r];
+    };
+    {   // bits 7, 6: lane = b5..b0, twiddles tw[4 + qr], tw[8 + 2 qr + b7] (wave-uniform)
+        const u32* const p = rows + lane;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) xp[k][r] = pair_of(p[k * RS + 68 * r]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) fwd_pass4_pair<true>(xp[k], w7, w6a, w6b, Q);
+        store4(((lane & 15u) << 2) | ((lane >> 3) & 2u) | (lane >> 5));
+    }
+    wave_sync();
+    {   // bits 5, 4: lane = (b7 b6, b3..b0), twiddles tw[16 + 4 qr + b7b6], tw[32 + 8 qr + 2 b7b6 + b5] (one 16-byte read)
+        const u32 h = lane >> 4;
+        const uint2 w5 = twf[tw_pos<16>(4 * qr + h)];
+        const uint4 w4 = *reinterpret_cast<const uint4*>(twf + tw_pos<32>(8 * qr + 2 * h));
+        pass16(w5, make_uint2(w4.x, w4.y), make_uint2(w4.z, w4.w));
+        store4(((lane >> 4) << 4) | ((lane & 3u) << 2) | ((lane >> 1) & 2u) | ((lane >> 3) & 1u));
+    }
+    wave_sync();
+    {   // bits 3, 2: lane = (b5 b4, b7 b6, b1 b0); i >> 4 = h; twiddles tw_pos<64>(16 qr + h), tw_pos<128>(2 (16 qr + h) + b3)
+        const u32 h = (((lane >> 2) & 3u) << 2) | (lane >> 4);
+        const uint2* const t = twf + tw_pos<64>(16 * qr + h);
+        pass16(t[0], t[64], t[128]);
+        store4((((lane >> 2) & 3u) << 4) | ((lane >> 4) << 2) | ((lane & 1u) << 1) | ((lane >> 1) & 1u));
+    }
+    wave_sync();
+    {   // bits 1, 0: lane = (b3 b2, b7..b4); twiddles tw_pos<256>(4 (16 qr + h) + b3b2), tw_pos<512>(8 (16 qr + h) + 2 b3b2 + b1)
+        const u32 h = lane & 15u, g = lane >> 4;
+        const uint2* const t = twf + 512 + 128 * g + 16 * qr + h;
+        pass16(twf[256 + 64 * g + 16 * qr + h], t[0], t[64]);
+        // positions 16 h + 4 g + (0..3) of the quarter, padded layout
+        uint4* const p = reinterpret_cast<uint4*>(rows + 16 * h + 4 * g + 4 * (h >> 2));
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p[k * (RS / 4)] = make_uint4((u32)xp[k][0], (u32)xp[k][1], (u32)xp[k][2], (u32)xp[k][3]);
     }
     wave_sync();
 }
@@ -629,12 +732,11 @@ __device__ __forceinline__ void ginx_mac_tail(const PT& P, __amdgpu_buffer_rsrc_
 // below 2Q (bounds: engine.cpp, ok5), + acc (< 2Q) < 4Q, one conditional subtraction.  The accumulator words it leaves are
 // congruent to the Barrett form's and in the same range [0, 2Q); every reduced value downstream is therefore the same.
 __device__ __forceinline__ u32 redc(u64 x, u32 Q, u32 qn) { return (u32)(mad64((u32)x * qn, Q, x) >> 32); }
-template <int LOGN, typename PT>
-__device__ __forceinline__ void ginx_mac_tail_redc(const PT& P, __amdgpu_buffer_rsrc_t psi_r2_rsrc, u32 Q, u32 ap, uint2 Ia,
-                                                   uint2 Ina, u32 p0, const u32* accp, u32* accw, const u64 (&sp)[4],
-                                                   const u64 (&sn)[4], u32 (&a)[4]) {
+template <int LOGN, bool EVENF = false, typename PT>
+__device__ __forceinline__ void ginx_mac_tail_redc(const PT& P, __amdgpu_buffer_rsrc_t psi_r2_rsrc, u32 Q, u32 ap, u32 p0,
+                                                   const u32* accp, u32* accw, const u64 (&sp)[4], const u64 (&sn)[4],
+                                                   u32 (&a)[4]) {
     constexpr u32 N = 1u << LOGN;
-    const bool odd = ap & 1u;
     const u32 k0 = __brev(p0) >> (32 - LOGN);
     const u32 ex = ((2 * k0 + 1) * ap) & (2 * N - 1);
     const u32 off = P.r2_off, K = Q + 2 * off, qn = P.qinv_neg;     // -(M - off) + off = K - M
@@ -642,12 +744,27 @@ __device__ __forceinline__ void ginx_mac_tail_redc(const PT& P, __amdgpu_buffer_
     const u32 p0r = psi_pow<LOGN>(psi_r2_rsrc, ex, Q), n0r = psi_pow<LOGN>(psi_r2_rsrc, (2 * N - ex) & (2 * N - 1), Q);
     mp[0] = p0r + off;
     mn[0] = n0r + off;
-    mp[2] = csub(mul_shoup_lazy(p0r, Ia, Q), Q) + off;
-    mn[2] = csub(mul_shoup_lazy(n0r, Ina, Q), Q) + off;
-    mp[1] = odd ? K - mp[0] : mp[0];
-    mn[1] = odd ? K - mn[0] : mn[0];
-    mp[3] = odd ? K - mp[2] : mp[2];
-    mn[3] = odd ? K - mn[2] : mn[2];
+    if constexpr (EVENF) {
+        // (host-decided, DevParams::factor_even) a' = factor * a is even: no parity selects, and I^a' = I^-a' = +1 (a' = 0 mod 4) or -1 (a' = 2 mod 4), one launch-
+        // uniform sign.  The same words as the general form below: its Shoup product of a value < Q by 1 is the value itself
+        // (quotient estimate 0), by Q - 1 a value congruent to its negative in [0, 2Q) that the conditional subtraction
+        // makes Q - value (the table entries are non-zero): K - (value + off) in both forms.
+        const bool neg = ap & 2u;
+        mp[2] = neg ? K - mp[0] : mp[0];
+        mn[2] = neg ? K - mn[0] : mn[0];
+        mp[1] = mp[0]; mn[1] = mn[0]; mp[3] = mp[2]; mn[3] = mn[2];
+    } else {
+        const bool odd = ap & 1u;
+        const u32 a4 = ap & 3u;
+        const uint2 Ia = make_uint2(P.I4[a4], P.I4s[a4]);
+        const uint2 Ina = make_uint2(P.I4[(4u - a4) & 3u], P.I4s[(4u - a4) & 3u]);
+        mp[2] = csub(mul_shoup_lazy(p0r, Ia, Q), Q) + off;
+        mn[2] = csub(mul_shoup_lazy(n0r, Ina, Q), Q) + off;
+        mp[1] = odd ? K - mp[0] : mp[0];
+        mn[1] = odd ? K - mn[0] : mn[0];
+        mp[3] = odd ? K - mp[2] : mp[2];
+        mn[3] = odd ? K - mn[2] : mn[2];
+    }
     const uint4 a4v = *reinterpret_cast<const uint4*>(accp);
     a[0] = a4v.x; a[1] = a4v.y; a[2] = a4v.z; a[3] = a4v.w;
 #pragma unroll
@@ -1082,10 +1199,11 @@ __device__ __forceinline__ void split_inverse_rest(const SplitInv<REGTW>& S, con
 // kernel k_blind_rotate_lat and the dependency-driven persistent kernel k_bootstrap_dag.  g: the gate, soff: slot offset
 // of the instance, boot: index of this bootstrap in acc_out / the debug buffers (acc_out may be null).
 // WPS = waves per SIMD the register budget allows: 2 (one workgroup per CU) or 4 (two)
-template <int DG, int WPS, bool AP, bool FUSE, bool FOLD, bool PERSIST = false, typename PT>
+template <int DG, int WPS, bool AP, bool FUSE, bool FOLD, bool PERSIST = false, bool QUNITS = false, bool EVENF = false, typename PT>
 __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g, const u32 soff, const u32 boot, u32* smem,
                                               u32* __restrict__ acc_out, u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks) {
     static_assert(DG == 4, "the split inverse transform is laid out for 8 waves");
+    static_assert(!QUNITS || (FOLD && WPS >= 4), "quarter units: six digit rows on eight waves, two workgroups per CU");
     constexpr int LOGN = 10;
     using C = Cfg<LOGN>;
     constexpr int N = C::N, NP = C::NP;
@@ -1152,6 +1270,14 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
     const u32 dig0 = phys(S.t);  // digit destination of register r: dig0 + 272 r  (phys(t + 256 r))
     // forward twiddles of the stages on bits 9 and 8 (wave-uniform): applied to the digits in registers
     const uint2 w9 = twf[1], w8a = twf[2], w8b = twf[3];
+    // quarter units: the wave's twiddles of the stages on bits 7 and 6 (quarter wave & 3), held in SGPRs for the whole bootstrap
+    uint2 q7 = make_uint2(0, 0), q6a = q7, q6b = q7;
+    if constexpr (QUNITS) {
+        const uint2 a = twf[tw_pos<4>(wave & 3u)], b = twf[tw_pos<8>(2 * (wave & 3u))], d = twf[tw_pos<8>(2 * (wave & 3u) + 1)];
+        q7 = make_uint2(__builtin_amdgcn_readfirstlane(a.x), __builtin_amdgcn_readfirstlane(a.y));
+        q6a = make_uint2(__builtin_amdgcn_readfirstlane(b.x), __builtin_amdgcn_readfirstlane(b.y));
+        q6b = make_uint2(__builtin_amdgcn_readfirstlane(d.x), __builtin_amdgcn_readfirstlane(d.y));
+    }
     {   // pass 0 of the first inverse transform (afterwards the MAC tail produces it)
         const uint4 v = *reinterpret_cast<const uint4*>(accc + S.a0);
         u32 a[4] = {v.x, v.y, v.z, v.w};
@@ -1223,10 +1349,20 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
         // (folded key: the half-row waves 4..7 -- the younger ones, which the arbiter serves last -- one level above the
         // whole-row waves, so that both kinds finish the phase together: -2 % per saturated launch, profiles/r02_prio_ab.log)
         // (round 4, profiles/r04_fwd_prio_ab.log: the whole-row waves above the half-row ones, or both at 1 -- within 0.3 % of this)
+        // (quarter units: equal waves.  The same policy -- the younger half one level above the low level -- against both
+        // at the low level and the older half above, -DBCE_FWD_UNITS_PRIO=1 / 2: profiles/fwd_units_ab.log)
+#if defined(BCE_FWD_UNITS_PRIO) && BCE_FWD_UNITS_PRIO == 1
+        if constexpr (QUNITS) __builtin_amdgcn_s_setprio(0); else
+#elif defined(BCE_FWD_UNITS_PRIO) && BCE_FWD_UNITS_PRIO == 2
+        if constexpr (QUNITS) { if (wave < 4) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); } else
+#endif
         if constexpr (WPS >= 4) { if (FOLD && wave >= 4) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
 #ifndef BCE_SKIP_FWD   // development: -DBCE_SKIP_FWD / -DBCE_SKIP_MAC leave a phase's LDS traffic out (wrong results) to
                        // attribute the LDS counters to phases, tools/lds_attribution.sh
-        if constexpr (FOLD) {
+        if constexpr (QUNITS) {
+            // six rows (2..7) as 24 quarters, three per wave: quarter wave & 3 of this wave's own component's rows 2 + c, 4 + c, 6 + c
+            ntt_forward_quarter3_low8(dct + (2 + c) * NP + 272u * (wave & 3u), wave & 3u, q7, q6a, q6b, twf, lane, Q);
+        } else if constexpr (FOLD) {
             // six rows (2..7) on eight waves: whole rows 2..5 on waves 0..3, rows 6 and 7 as halves on waves 4..7
             if (wave < 4) ntt_forward_wave_low8(dct + (2 + wave) * NP, twf, lane, Q);
             else ntt_forward_half_low8(dct + (6 + ((wave - 4) >> 1)) * NP, (wave - 4) & 1u, twf, lane, Q);
@@ -1271,13 +1407,13 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
                 for (int e = 0; e < 4; ++e) anew[e] = barrett_fold(sp[e], P.c32, Q, P.red_shift, P.red_mu);
                 *reinterpret_cast<uint4*>(accw) = make_uint4(anew[0], anew[1], anew[2], anew[3]);
             } else {
+#ifdef BCE_BARRETT_TAIL
                 const u32 a4 = ap & 3u;
                 const uint2 Ia = make_uint2(P.I4[a4], P.I4s[a4]);
                 const uint2 Ina = make_uint2(P.I4[(4u - a4) & 3u], P.I4s[(4u - a4) & 3u]);
-#ifdef BCE_BARRETT_TAIL
                 ginx_mac_tail<LOGN, true>(P, psi_rsrc, Q, ap, Ia, Ina, mp0, accr, accw, sp, sn, anew);
 #else
-                ginx_mac_tail_redc<LOGN>(P, psi_rsrc, Q, ap, Ia, Ina, mp0, accr, accw, sp, sn, anew);
+                ginx_mac_tail_redc<LOGN, EVENF>(P, psi_rsrc, Q, ap, mp0, accr, accw, sp, sn, anew);
 #endif
             }
             if constexpr (FOLD) cb = 2 * NP - cb;
@@ -1318,12 +1454,12 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
     }
 }
 
-template <int DG, int WPS, bool AP = false, bool FUSE = false, bool FOLD = false>
+template <int DG, int WPS, bool AP = false, bool FUSE = false, bool FOLD = false, bool QUNITS = false>
 __global__ __launch_bounds__(128 * DG, WPS) void k_blind_rotate_lat(DevParams P, const bce_gate_desc* __restrict__ descs, u32 n_desc,
                                                                    u32 slot_stride, u32* __restrict__ acc_out,
                                                                    u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks) {
     extern __shared__ __align__(16) u32 smem[];
-    lat_bootstrap<DG, WPS, AP, FUSE, FOLD>(P, descs[blockIdx.x % n_desc], (blockIdx.x / n_desc) * slot_stride, blockIdx.x, smem,
+    lat_bootstrap<DG, WPS, AP, FUSE, FOLD, false, QUNITS, QUNITS>(P, descs[blockIdx.x % n_desc], (blockIdx.x / n_desc) * slot_stride, blockIdx.x, smem,
                                            acc_out, dbg_lweN, dbg_ks);
 }
 
@@ -1390,12 +1526,12 @@ __global__ void k_dag_rearm(DagParams D) {
     for (size_t j = i0 + kDagAbort; j < kDagCtlWords; j += stride) D.ctl[j] = 0;
 }
 
-template <int WPS, bool AP, bool FOLD>
+template <int WPS, bool AP, bool FOLD, bool QUNITS = false>
 __global__ __launch_bounds__(512, WPS) void k_bootstrap_dag(const DevParams* Pp, const DagParams* Dp) {
     extern __shared__ __align__(16) u32 smem[];
     // the worker's mailbox sits in front of the LDS layout of lat_bootstrap
     dag_worker(Dp, smem, [&](ConstDagParams& D, u32 t, u32 k) {
-        lat_bootstrap<4, WPS, AP, true, FOLD, true>(*as_constant<ConstDevParams>(Pp), D.tasks[t], D.slot_base + k * D.slot_stride, 0,
+        lat_bootstrap<4, WPS, AP, true, FOLD, true, QUNITS, QUNITS>(*as_constant<ConstDevParams>(Pp), D.tasks[t], D.slot_base + k * D.slot_stride, 0,
                                                    smem + kDagMailboxWords, nullptr, nullptr, nullptr);
     });
 }
@@ -1416,7 +1552,8 @@ hipError_t launch_bootstrap_dag(const DevParams& P, const DevParams* d_P, const 
     using DagKernel = void (*)(const DevParams*, const DagParams*);
     const bool ap = P.method_ap != 0, x1 = wps <= 2;
     DagKernel k;
-    if (P.fold) k = ap ? (x1 ? k_bootstrap_dag<2, true, true> : k_bootstrap_dag<4, true, true>) : (x1 ? k_bootstrap_dag<2, false, true> : k_bootstrap_dag<4, false, true>);
+    if (P.fold && P.fwd_units && !ap && !x1) k = k_bootstrap_dag<4, false, true, true>;   // forward transforms as quarter units
+    else if (P.fold) k = ap ? (x1 ? k_bootstrap_dag<2, true, true> : k_bootstrap_dag<4, true, true>) : (x1 ? k_bootstrap_dag<2, false, true> : k_bootstrap_dag<4, false, true>);
     else k = ap ? (x1 ? k_bootstrap_dag<2, true, false> : k_bootstrap_dag<4, true, false>) : (x1 ? k_bootstrap_dag<2, false, false> : k_bootstrap_dag<4, false, false>);
     const size_t lds = blind_rotate_lat_lds_bytes(P) + kDagMailboxWords * 4;   // + the worker's mailbox in front
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1469,6 +1606,7 @@ hipError_t launch_blind_rotate(const DevParams& P, const bce_gate_desc* d, u32 n
         LatKernel lk;
         if (P.fold) {   // key rows l >= 1 hold ek_l - B^l ek_0 (see the kernel's FOLD note)
             if (ap) lk = x1 ? k_blind_rotate_lat<4, 2, true, false, true> : (fuse ? k_blind_rotate_lat<4, 4, true, true, true> : k_blind_rotate_lat<4, 4, true, false, true>);
+            else if (P.fwd_units && !x1) lk = fuse ? k_blind_rotate_lat<4, 4, false, true, true, true> : k_blind_rotate_lat<4, 4, false, false, true, true>;
             else lk = x1 ? k_blind_rotate_lat<4, 2, false, false, true> : (fuse ? k_blind_rotate_lat<4, 4, false, true, true> : k_blind_rotate_lat<4, 4, false, false, true>);
         } else if (ap) lk = x1 ? k_blind_rotate_lat<4, 2, true, false> : (fuse ? k_blind_rotate_lat<4, 4, true, true> : k_blind_rotate_lat<4, 4, true, false>);
         else lk = x1 ? k_blind_rotate_lat<4, 2, false, false> : (fuse ? k_blind_rotate_lat<4, 4, false, true> : k_blind_rotate_lat<4, 4, false, false>);

@@ -52,6 +52,11 @@ struct DevParams {
                            // the coefficients themselves (no N^-1 product per coefficient and step; -DBCE_KEY_NINV=0 disables)
     u32 fold;              // 1: the key is stored with the lowest gadget digit folded in (rows l >= 1 hold ek_l - B^l ek_0) and
                            // the kernels multiply the digit-0 rows by the evaluation-form accumulator itself (BCE_FOLD=0 disables)
+    u32 fwd_units;         // 1: the two-workgroups-per-CU build of the folded GINX split-transform kernel runs its six forward transforms
+                           // as 24 quarter units, three per wave (kernels.hip, ntt_forward_quarter3_low8; BCE_FWD_UNITS=0 keeps
+                           // the whole-row + half-row bodies)
+    u32 factor_even;       // 1: factor = 2N / q is even, so every rotation exponent a' is even and I^a' = +-1: the quarter-unit build
+                           // is compiled with the GINX MAC tail for that case (no parity selects, no products by I^+-a')
     u32 I4[4], I4s[4];     // powers of I = psi^(N/2) (primitive 4th root of unity) and Shoup companions
     const uint2* tw_f;  // [N] (psi^brv(i), shoup), index m+i as in the CT forward NTT; the inverse
                         // transform derives psi^-k = -psi^(N-k) from the same table
