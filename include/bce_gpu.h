@@ -253,6 +253,18 @@ uint32_t bce_forward_transforms_per_step(const bce_ctx*);
  * N = 1024 GINX kernel at two workgroups per compute unit, even 2N / q); 0: whole-row + half-row bodies (other contexts,
  * or BCE_FWD_UNITS=0 at context creation). */
 uint32_t bce_forward_units(const bce_ctx*);
+/* 1 when those quarter units run the stages on position bits 9..4 on the matrix pipe: i8 products of the gadget digits with
+ * the four 7-bit limbs of one constant 64 x 64 matrix (needs the quarter units, gadget base <= 2^7 and the bounds of
+ * csrc/fwd_mfma.hpp for this Q); 0: the quarter-unit body, in other contexts or with BCE_FWD_MFMA=0 at context creation. */
+uint32_t bce_forward_mfma(const bce_ctx*);
+/* The host-built tables of that body, without a context or a device (tests).  Any output pointer may be null.
+ * psi: the 2N-th root used; M6[64][64]: the six stages as a matrix over the positions p >> 4; C[64]: the balance words of
+ * the raw-digit form (the kernel multiplies signed digits and needs none); table[4096]: the device image (A operands per
+ * quarter, tile and lane); w14: 2^14 mod Q and its Shoup companion; bounds[4]: limb sum, low part, high part, recombined word.
+ * Returns 1: the body may be enabled for these parameters; -1: tables built but a bound fails; 0: not this class
+ * (N != 1024, dG != 4, gBits > 7, Q >= 2^28 or Q != 1 mod 2N), nothing written. */
+int bce_forward_mfma_tables(uint64_t Q, uint32_t N, uint32_t gBits, uint32_t dG, uint64_t* psi, uint32_t* M6, uint32_t* C,
+                            uint32_t* table, uint32_t* w14, uint64_t* bounds);
 /* Launch granularity of this context's blind-rotation kernels, for callers that shape their frontiers (the host
  * scheduler of bce_circuit.h does): one bootstrap is one workgroup, so a call's time is a staircase in its size.
  * *lone = bootstraps up to which every workgroup has a compute unit to itself (one bootstrap latency per call),

@@ -60,7 +60,7 @@ ENGINE_SYMBOLS = [
     "bce_keygen", "bce_import_keys", "bce_import_keys_eval", "bce_export_bsk_eval", "bce_import_keys_file", "bce_export_keys_file", "bce_bsk_words", "bce_ksk_words", "bce_export_sk", "bce_export_bsk",
     "bce_export_ksk", "bce_pool_reserve", "bce_pool_slots", "bce_lwe_write", "bce_lwe_read",
     "bce_encrypt_bits", "bce_set_encrypt_seed", "bce_decrypt_bits", "bce_eval_gates", "bce_eval_gates_strided", "bce_synchronize",
-    "bce_timing_reset", "bce_timing_get", "bce_timing_set_events", "bce_bytes_per_bootstrap", "bce_bytes_per_bootstrap_parts", "bce_forward_transforms_per_step", "bce_forward_units", "bce_launch_capacity", "bce_rccl_available", "bce_rccl_version", "bce_rccl_unique_id", "bce_rccl_init", "bce_rccl_allgather", "bce_rccl_comm_info",
+    "bce_timing_reset", "bce_timing_get", "bce_timing_set_events", "bce_bytes_per_bootstrap", "bce_bytes_per_bootstrap_parts", "bce_forward_transforms_per_step", "bce_forward_units", "bce_forward_mfma", "bce_forward_mfma_tables", "bce_launch_capacity", "bce_rccl_available", "bce_rccl_version", "bce_rccl_unique_id", "bce_rccl_init", "bce_rccl_allgather", "bce_rccl_comm_info",
     "bce_rccl_shutdown", "bce_debug_eval_stages", "bce_debug_ntt", "bce_debug_tail",
     "bce_dag_supported", "bce_dag_create", "bce_dag_run", "bce_dag_destroy", "bce_dag_set_limits", "bce_dag_last_run", "bce_dag_debug_block_task",
     "bce_plan_create", "bce_plan_run_step", "bce_plan_run", "bce_plan_destroy",
@@ -72,6 +72,21 @@ _lib = None
 def build(force=False):
     """Compile the extension for gfx950 if needed and return its path."""
     return _build.build(force=force)
+
+
+def forward_mfma_tables(Q, N=1024, gBits=7, dG=4):
+    """Host-built tables of the matrix-pipe forward body (no context, no GPU): (status, dict).  status 1: may be enabled,
+    -1: a bound fails for this Q, 0: not this class of parameters (dict is None)."""
+    import numpy as np
+    L = lib()
+    psi, w14, bounds = C.c_uint64(), (C.c_uint32 * 2)(), (C.c_uint64 * 4)()
+    M6, Cw, tab = np.zeros((64, 64), np.uint32), np.zeros(64, np.uint32), np.zeros((4, 4, 64, 4), np.uint32)
+    st = int(L.bce_forward_mfma_tables(int(Q), int(N), int(gBits), int(dG), C.byref(psi), M6.ctypes.data, Cw.ctypes.data, tab.ctypes.data,
+                                       C.cast(w14, C.c_void_p), C.cast(bounds, C.c_void_p)))
+    if st == 0:
+        return 0, None
+    return st, {"psi": int(psi.value), "M6": M6, "C": Cw, "table": tab, "w14": (int(w14[0]), int(w14[1])),
+                "limb_sum_max": int(bounds[0]), "lo_max": int(bounds[1]), "hi_max": int(bounds[2]), "out_max": int(bounds[3])}
 
 
 def lib():
@@ -125,6 +140,10 @@ def lib():
     L.bce_forward_transforms_per_step.restype = C.c_uint32
     L.bce_forward_units.argtypes = [vp]
     L.bce_forward_units.restype = C.c_uint32
+    L.bce_forward_mfma.argtypes = [vp]
+    L.bce_forward_mfma.restype = C.c_uint32
+    L.bce_forward_mfma_tables.argtypes = [u64, u32, u32, u32, vp, vp, vp, vp, vp, vp]
+    L.bce_forward_mfma_tables.restype = i32
     L.bce_launch_capacity.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.bce_rccl_unique_id.argtypes = [C.c_char_p]
     L.bce_rccl_init.argtypes = [vp, C.c_char_p, i32, i32]
@@ -436,6 +455,10 @@ class BinFHEContext:
     def forward_units(self):
         """1: saturated launches transform as 24 quarter units, three per wave; 0: whole-row + half-row bodies"""
         return int(self._L.bce_forward_units(self.h))
+
+    def forward_mfma(self):
+        """1: the quarter units run the stages on bits 9..4 as i8 matrix products (BCE_FWD_MFMA=0: the quarter-unit body)"""
+        return int(self._L.bce_forward_mfma(self.h))
 
     def launch_capacity(self):
         lone, full = C.c_uint32(), C.c_uint32()

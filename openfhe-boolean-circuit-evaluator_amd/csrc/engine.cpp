@@ -22,6 +22,7 @@
 
 #include "../../include/bce_circuit.h"
 #include "../../include/bce_gpu.h"
+#include "fwd_mfma.hpp"
 #include "host_math.hpp"
 #include "kernels.hpp"
 #include "keygen.hpp"
@@ -93,6 +94,7 @@ struct bce_ctx {
     DevParams P{};
     // device tables / keys
     uint2* d_twf = nullptr;
+    u32* d_fwd_mfma = nullptr;
     u32* d_psi = nullptr;
     u32* d_psi_r2 = nullptr;
     u32* d_xcd_gate = nullptr;
@@ -380,6 +382,22 @@ int build_ctx(u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 baseG, u32 ba
         // BCE_FWD_UNITS=0 keeps them everywhere (development / parity knob, same binary)
         const char* fu = std::getenv("BCE_FWD_UNITS");
         P.fwd_units = (P.fold && !c->is64 && c->method == BCE_GINX && P.factor_even && !(fu && fu[0] == '0')) ? 1 : 0;
+        // The stages on bits 9..4 of those transforms on the matrix pipe (kernels.hip, ntt_forward_quarter3_mfma): a variant of
+        // the quarter units, so it needs everything they need (folded key, GINX, even factor, N = 1024, dG = 4) and the
+        // arithmetic conditions of fwd_mfma.hpp (gBits <= 7, four 7-bit limbs, exact limb sums, recombined word <= 13Q).
+        // Bound chain of the forward phase with this body: recombined words < 2Q + lo_max (< 4Q for STD128*), four lazy stages
+        // add < 2Q each -> MAC operands < 12Q, below the 22Q = (2 logN + 2) Q that ok1..ok5 above were checked with.
+        // Anything that fails keeps the quarter-unit body; BCE_FWD_MFMA=0 keeps it as well (development / parity knob).
+        P.fwd_mfma = 0; P.w14 = P.w14s = 0; P.fwd_mfma_tab = nullptr;
+        const char* fm = std::getenv("BCE_FWD_MFMA");
+        if (P.fwd_units && !(fm && fm[0] == '0')) {
+            const FwdMfmaTables T = build_fwd_mfma_tables(Q, N, c->gBits, c->dG, c->psi);
+            if (T.ok) {
+                if (hipMalloc(&c->d_fwd_mfma, sizeof(u32) * kFwdMfmaTableWords) != hipSuccess) { g_create_error = "hipMalloc(forward matrix table) failed"; return BCE_ERR_HIP; }
+                hipMemcpy(c->d_fwd_mfma, T.table.data(), sizeof(u32) * kFwdMfmaTableWords, hipMemcpyHostToDevice);
+                P.fwd_mfma = 1; P.w14 = T.w14; P.w14s = T.w14s; P.fwd_mfma_tab = c->d_fwd_mfma;
+            }
+        }
     }
     P.pool_stride = n + 1;
     c->enc_seed_ok = os_entropy(c->enc_seed);
@@ -763,7 +781,7 @@ void bce_ctx_destroy(bce_ctx* c) {
     }
     hipFree(c->d_io); if (c->h_io) hipHostFree(c->h_io);
     hipFree(c->d_P); if (c->h_dag_status) hipHostFree(c->h_dag_status); if (c->h_dag_stage) hipHostFree(c->h_dag_stage);
-    hipFree(c->d_twf); hipFree(c->d_psi); hipFree(c->d_psi_r2); hipFree(c->d_xcd_gate); hipFree(c->d_tw64); hipFree(c->d_tw64d); hipFree(c->d_bsk); hipFree(c->d_ksk); hipFree(c->d_pool); hipFree(c->d_acc); hipFree(c->d_tail_partial);
+    hipFree(c->d_twf); hipFree(c->d_fwd_mfma); hipFree(c->d_psi); hipFree(c->d_psi_r2); hipFree(c->d_xcd_gate); hipFree(c->d_tw64); hipFree(c->d_tw64d); hipFree(c->d_bsk); hipFree(c->d_ksk); hipFree(c->d_pool); hipFree(c->d_acc); hipFree(c->d_tail_partial);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1528,6 +1546,19 @@ int bce_timing_get(bce_ctx* c, bce_timing* out) {
 
 uint32_t bce_forward_transforms_per_step(const bce_ctx* c) { return c ? 2 * c->dG - (c->P.fold ? 2 : 0) : 0; }
 uint32_t bce_forward_units(const bce_ctx* c) { return c ? c->P.fwd_units : 0; }
+uint32_t bce_forward_mfma(const bce_ctx* c) { return c ? c->P.fwd_mfma : 0; }
+int bce_forward_mfma_tables(uint64_t Q, uint32_t N, uint32_t gBits, uint32_t dG, uint64_t* psi, uint32_t* M6, uint32_t* C, uint32_t* table,
+                            uint32_t* w14, uint64_t* bounds) {
+    const FwdMfmaTables T = build_fwd_mfma_tables(Q, N, gBits, dG);
+    if (T.M6.empty()) return 0;   // not this class of parameters: nothing was built
+    if (psi) *psi = T.psi;
+    if (M6) std::copy(T.M6.begin(), T.M6.end(), M6);
+    if (C) std::copy(T.C.begin(), T.C.end(), C);
+    if (table) std::copy(T.table.begin(), T.table.end(), table);
+    if (w14) { w14[0] = T.w14; w14[1] = T.w14s; }
+    if (bounds) { bounds[0] = T.limb_sum_max; bounds[1] = T.lo_max; bounds[2] = T.hi_max; bounds[3] = T.out_max; }
+    return T.ok ? 1 : -1;         // -1: built, but a bound fails for this Q
+}
 
 int bce_launch_capacity(const bce_ctx* c, uint32_t* lone, uint32_t* full) {
     if (!c || !lone || !full) return BCE_ERR_ARG;

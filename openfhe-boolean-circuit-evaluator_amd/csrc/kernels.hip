@@ -18,7 +18,9 @@
 // All arithmetic is 32-bit unsigned modular integer (Q < 2^28): lazy Shoup butterflies on register
 // pairs (forward, values below 22Q, 5 instructions) and compile-time bound-tracked Gentleman-Sande
 // stages (inverse), 64-bit MAC sums folded and reduced by lazy Barrett steps; the non-lazy Harvey
-// forms remain for Q >= 2^27.6.  No MFMA: nothing here is a dense contraction.
+// forms remain for Q >= 2^27.6.  The transforms are not dense contractions -- with one exception: the first six forward
+// stages of the gadget digits (7-bit operands, twiddles independent of the low position bits) are a 64 x 64 x 16 product per
+// digit row and run as i8 MFMAs in the two-workgroups-per-CU GINX build (ntt_forward_quarter3_mfma).
 //
 // NTT organisation (64-wide wavefronts): E = N/64 coefficients per lane held in registers, log2(E)
 // radix-2 stages per register pass, LDS re-shuffles between passes instead of one barrier per stage.
@@ -624,6 +626,85 @@ __device__ __forceinline__ void ntt_forward_quarter3_low8(u32* rows, u32 qr, uin
     }
     wave_sync();
 }
+// The same quarter units with the stages on bits 9..4 on the MATRIX pipe (fwd_mfma.hpp has the algebra, the tables and the
+// bounds).  The producer of the digits does not run the stages on bits 9 and 8: it stores the signed digits s = d - 2^(gBits-1)
+// in [-64, 64) as SIGNED bytes, four per thread and row in one dword, into a byte matrix Xb[column j = p & 15][K slot],
+// 1 KiB per digit row.  K slot k = 4 ((p >> 4) & 15) + (p >> 8) (fwd_mfma_h_of_k is its inverse); a column's four 16-byte K
+// groups g are stored at 64 j + 16 (g ^ (-(j >> 2) & 3)): the 16-byte read below (lane = (g, j), lane groups of
+// ds_read_b128) and the 4-byte stores (2-way at most) are conflict-free.
+// Per digit row a wave issues four v_mfma_i32_16x16x64_i8, one per tile of four output rows h' = 16 qr + 4 i + o:
+//   A (constant, from the table)  row 4 o + limb = limb `limb` of M6[h'][.], so that -- C/D map: column = lane & 15, row =
+//                                 4 (lane >> 4) + register -- a lane's four accumulator registers are the four limbs of ONE word;
+//   B (one 16-byte LDS read)      the digits of column j = lane & 15, K group lane >> 4;
+//   C                             (Q, 0, Q, 0), the same for every tile: the limb sums are signed (|S0 + 2^7 S1| <= 129 * 64 * 127 * 64
+//                                 < Q, host check), the offsets make low and high part positive.
+// word = (S0 + Q + 2^7 S1) + 2^14 (S2 + Q + 2^7 S3): two v_lshl_add_u32 and one lazy Shoup product by 2^14 whose 64-bit addend is
+// the low part; < 2Q + lo_max < 4Q (the six lazy stages it replaces leave < 13Q).  Afterwards a lane holds, per row, quarter
+// positions i = b7..b0 with b7 b6 = tile (register), b5 b4 = lane >> 4, b3..b0 = lane & 15; the passes on bits 3, 2 and 1, 0
+// are those of ntt_forward_quarter3_low8 with image B's upper fields swapped to (b7 b6 | b5 b4 b1 b0 | b3 b2), so that the
+// 4-byte stores of one register cover 64 consecutive words.
+typedef int v4i __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32 xb_group(u32 j, u32 g) { return 64u * j + 16u * ((g ^ (0u - (j >> 2))) & 3u); }  // byte offset
+__device__ __forceinline__ void ntt_forward_quarter3_mfma(u32* rows, const u32* xb, u32 qr, const v4i (&A)[4], uint2 w14,
+                                                          const uint2* twf, u32 lane, u32 Q) {
+    constexpr int RS = 2 * Cfg<10>::NP;   // words between the three rows of a wave
+    u64 xp[3][4];
+    auto pass16 = [&](uint2 wa, uint2 wb0, uint2 wb1) {   // as in ntt_forward_quarter3_low8
+        const uint4* const p = reinterpret_cast<const uint4*>(rows + 4 * lane);
+        uint4 v[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v[k] = p[k * (RS / 4)];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            xp[k][0] = ((u64)v[k].y << 32) | v[k].x; xp[k][2] = pair_of(v[k].y);
+            xp[k][1] = ((u64)v[k].w << 32) | v[k].z; xp[k][3] = pair_of(v[k].w);
+            fwd_pass4_pair<false>(xp[k], wa, wb0, wb1, Q);
+        }
+    };
+    auto store4 = [&](u32 off) {          // register r of every row to off + 64 r
+        u32* const p = rows + off;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) p[k * RS + 64 * r] = (u32)xp[k][r];
+    };
+    {   // bits 9..4: lane = (K group | column) for B, (b5 b4 | b3..b0) for the result
+        const char* const pb = reinterpret_cast<const char*>(xb) + xb_group(lane & 15u, lane >> 4);
+        v4i B[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) B[k] = *reinterpret_cast<const v4i*>(pb + 1024 * k);
+        const u32 negQ = 0u - Q;
+        const v4i c0 = {(int)Q, 0, (int)Q, 0};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const v4i s = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[i], B[k], c0, 0, 0, 0);
+                const u32 lo = ((u32)s[1] << 7) + (u32)s[0], hi = ((u32)s[3] << 7) + (u32)s[2];
+                // the addend pair is (lo, S1): S1 already sits in the register next to S0 and the high half is a don't-care
+                xp[k][i] = mad64(__umulhi(hi, w14.y), negQ, mad64_su(hi, w14.x, ((u64)(u32)s[1] << 32) | lo));
+            }
+        }
+        store4(((lane >> 4) << 4) | ((lane & 3u) << 2) | ((lane >> 1) & 2u) | ((lane >> 3) & 1u));
+    }
+    wave_sync();
+    {   // bits 3, 2: lane = (b7 b6, b5 b4, b1 b0); i >> 4 = h; twiddles tw_pos<64>(16 qr + h), tw_pos<128>(2 (16 qr + h) + b3)
+        const u32 h = lane >> 2;
+        const uint2* const t = twf + tw_pos<64>(16 * qr + h);
+        pass16(t[0], t[64], t[128]);
+        store4((h << 2) | ((lane & 1u) << 1) | ((lane >> 1) & 1u));
+    }
+    wave_sync();
+    {   // bits 1, 0: lane = (b3 b2, b7..b4), as in ntt_forward_quarter3_low8
+        const u32 h = lane & 15u, g = lane >> 4;
+        const uint2* const t = twf + 512 + 128 * g + 16 * qr + h;
+        pass16(twf[256 + 64 * g + 16 * qr + h], t[0], t[64]);
+        uint4* const p = reinterpret_cast<uint4*>(rows + 16 * h + 4 * g + 4 * (h >> 2));
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p[k * (RS / 4)] = make_uint4((u32)xp[k][0], (u32)xp[k][1], (u32)xp[k][2], (u32)xp[k][3]);
+    }
+    wave_sync();
+}
 // one lazy Cooley-Tukey butterfly on plain registers (5 instructions; X' = X + wY, Y' = X - wY + 2Q)
 __device__ __forceinline__ void fwd_bfly(u32& X, u32& Y, uint2 w, u32 Q) {
     const u64 t = mad64(__umulhi(Y, w.y), 0u - Q, mad64(Y, w.x, pair_of(X)));
@@ -1199,11 +1280,13 @@ __device__ __forceinline__ void split_inverse_rest(const SplitInv<REGTW>& S, con
 // kernel k_blind_rotate_lat and the dependency-driven persistent kernel k_bootstrap_dag.  g: the gate, soff: slot offset
 // of the instance, boot: index of this bootstrap in acc_out / the debug buffers (acc_out may be null).
 // WPS = waves per SIMD the register budget allows: 2 (one workgroup per CU) or 4 (two)
-template <int DG, int WPS, bool AP, bool FUSE, bool FOLD, bool PERSIST = false, bool QUNITS = false, bool EVENF = false, typename PT>
+// MFMA (needs QUNITS): the forward stages on bits 9..4 as i8 matrix products (ntt_forward_quarter3_mfma)
+template <int DG, int WPS, bool AP, bool FUSE, bool FOLD, bool PERSIST = false, bool QUNITS = false, bool EVENF = false, bool MFMA = false, typename PT>
 __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g, const u32 soff, const u32 boot, u32* smem,
                                               u32* __restrict__ acc_out, u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks) {
     static_assert(DG == 4, "the split inverse transform is laid out for 8 waves");
     static_assert(!QUNITS || (FOLD && WPS >= 4), "quarter units: six digit rows on eight waves, two workgroups per CU");
+    static_assert(!MFMA || (QUNITS && !AP), "matrix-pipe forward stages: a variant of the quarter units");
     constexpr int LOGN = 10;
     using C = Cfg<LOGN>;
     constexpr int N = C::N, NP = C::NP;
@@ -1212,7 +1295,8 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
     u32* acc = reinterpret_cast<u32*>(twf + N);  // [2][NP]
     u32* dct = acc + 2 * NP;                     // [R][NP]
     u32* xab = dct + R * NP;                     // [2 polynomials][2 buffers][XB]
-    u32* av = xab + 4 * XB;
+    u32* xbm = xab + 4 * XB;                     // MFMA: [2 components][3 digit rows] byte matrices of 1 KiB (256 words)
+    u32* av = xbm + (MFMA ? 6 * 256 : 0);
 
     u32 tid_ = threadIdx.x;
     // opaque inside the persistent kernel's loop: nothing derived from the thread index is hoisted out of the bootstrap
@@ -1265,6 +1349,10 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
     u32 off = 0;
     for (u32 l = 0; l < (u32)DG; ++l) off |= 1u << (l * gb + gb - 1);
     const u32 offm = off - Q, bias = Q - (1u << (gb - 1));
+    // MFMA: the table of A operands (fwd_mfma.hpp), [quarter][tile][lane] x 16 bytes
+    const __amdgpu_buffer_rsrc_t mrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32*>(P.fwd_mfma_tab), 0, MFMA ? 4 * 4 * 1024 : 0, 0x00020000);
+    // v_perm_b32 selectors (SGPRs): bytes 0 of two registers side by side; the low halves of two registers side by side
+    const u32 psel0 = 0x0c0c0400u, psel1 = 0x05040100u;
     // MAC item of this thread: component mc, positions mp0..mp0+3 (T == 2 * N/4: exactly one item each)
     const u32 mc = tid / (N / 4), mp0 = (tid % (N / 4)) * 4, mpp = phys(mp0);
     const u32 dig0 = phys(S.t);  // digit destination of register r: dig0 + 272 r  (phys(t + 256 r))
@@ -1272,7 +1360,7 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
     const uint2 w9 = twf[1], w8a = twf[2], w8b = twf[3];
     // quarter units: the wave's twiddles of the stages on bits 7 and 6 (quarter wave & 3), held in SGPRs for the whole bootstrap
     uint2 q7 = make_uint2(0, 0), q6a = q7, q6b = q7;
-    if constexpr (QUNITS) {
+    if constexpr (QUNITS && !MFMA) {
         const uint2 a = twf[tw_pos<4>(wave & 3u)], b = twf[tw_pos<8>(2 * (wave & 3u))], d = twf[tw_pos<8>(2 * (wave & 3u) + 1)];
         q7 = make_uint2(__builtin_amdgcn_readfirstlane(a.x), __builtin_amdgcn_readfirstlane(a.y));
         q6a = make_uint2(__builtin_amdgcn_readfirstlane(b.x), __builtin_amdgcn_readfirstlane(b.y));
@@ -1309,6 +1397,7 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
         // 128-register one (the rest is requested at the end of phase 2)
         constexpr u32 PR = (WPS <= 2) ? R : R / 2;
         uint4 kA[R], kB[R];
+        v4i mA[4];       // MFMA: A operands of the wave's four tiles, requested at pass 4 of the inverse transform
         auto request_rows = [&](auto kc) {
             constexpr u32 k = decltype(kc)::value - 1, G = PR / 4;  // pass k+1 requests rows [k*G, (k+1)*G) of each key
             BCE_PROF_MARK(8 + k);   // 8: step head, 9: pass 1, 10: pass 2, 11: pass 3 + the barrier; slot 0 is then pass 4 + digits
@@ -1316,6 +1405,10 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
             for (u32 l = k * G; l < (k + 1) * G; ++l) {
                 kA[l] = bsk_row(rsrc, tid * 16u, rowb + l * (2 * N * 4));
                 if constexpr (!AP) kB[l] = bsk_row(rsrc, tid * 16u, rowb + (rgsw + l * 2 * N) * 4);
+            }
+            if constexpr (MFMA && k == 3) {
+#pragma unroll
+                for (u32 v = 0; v < 4; ++v) mA[v] = __builtin_bit_cast(v4i, bsk_row(mrsrc, lane * 16u, ((wave & 3u) * 4u + v) * 1024u));
             }
         };
         // (1) inverse transforms on all 8 waves (passes 1..4), SignedDigitDecompose in closed form, and the
@@ -1325,8 +1418,22 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
             split_inverse_rest(S, twf, xa, xb, Q, P.mu32, ninv, wlast, x, request_rows);
 #pragma unroll
             for (int r = 0; r < 4; ++r) u[r] = x[r] + ((x[r] < Qh) ? off : offm);
+            if constexpr (MFMA) {   // digit fields d -> d - 2^(gb-1) mod 2^gb: flip every field's top bit (`off` is exactly those bits)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) u[r] ^= off;
+            }
 #pragma unroll
             for (u32 l = FOLD ? 1 : 0; l < (u32)DG; ++l) {
+                if constexpr (MFMA) {
+                    // signed digits of coefficients t + 256 r (u's fields hold d - 2^(gb-1) in two's complement here: sign-extending
+                    // extracts) as the bytes r of ONE dword: K slots 4 (t >> 4) + r of column t & 15
+                    const u32 e01 = __builtin_amdgcn_perm((u32)__builtin_amdgcn_sbfe((int)u[1], l * gb, gb), (u32)__builtin_amdgcn_sbfe((int)u[0], l * gb, gb), psel0);
+                    const u32 e23 = __builtin_amdgcn_perm((u32)__builtin_amdgcn_sbfe((int)u[3], l * gb, gb), (u32)__builtin_amdgcn_sbfe((int)u[2], l * gb, gb), psel0);
+                    const u32 d = __builtin_amdgcn_perm(e23, e01, psel1);
+                    const u32 G = S.t >> 4;
+                    xbm[(3 * c + l - 1) * 256 + (xb_group(S.t & 15u, G >> 2) >> 2) + (G & 3u)] = d;
+                    continue;
+                }
                 u32 v[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = __builtin_amdgcn_ubfe(u[r], l * gb, gb) + bias;
@@ -1349,6 +1456,7 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
         // (folded key: the half-row waves 4..7 -- the younger ones, which the arbiter serves last -- one level above the
         // whole-row waves, so that both kinds finish the phase together: -2 % per saturated launch, profiles/r02_prio_ab.log)
         // (round 4, profiles/r04_fwd_prio_ab.log: the whole-row waves above the half-row ones, or both at 1 -- within 0.3 % of this)
+        // (matrix-pipe body: the same policy is kept.)
         // (quarter units: equal waves.  The same policy -- the younger half one level above the low level -- against both
         // at the low level and the older half above, -DBCE_FWD_UNITS_PRIO=1 / 2: profiles/fwd_units_ab.log)
 #if defined(BCE_FWD_UNITS_PRIO) && BCE_FWD_UNITS_PRIO == 1
@@ -1359,7 +1467,9 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
         if constexpr (WPS >= 4) { if (FOLD && wave >= 4) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
 #ifndef BCE_SKIP_FWD   // development: -DBCE_SKIP_FWD / -DBCE_SKIP_MAC leave a phase's LDS traffic out (wrong results) to
                        // attribute the LDS counters to phases, tools/lds_attribution.sh
-        if constexpr (QUNITS) {
+        if constexpr (MFMA) {
+            ntt_forward_quarter3_mfma(dct + (2 + c) * NP + 272u * (wave & 3u), xbm + 3 * c * 256, wave & 3u, mA, make_uint2(P.w14, P.w14s), twf, lane, Q);
+        } else if constexpr (QUNITS) {
             // six rows (2..7) as 24 quarters, three per wave: quarter wave & 3 of this wave's own component's rows 2 + c, 4 + c, 6 + c
             ntt_forward_quarter3_low8(dct + (2 + c) * NP + 272u * (wave & 3u), wave & 3u, q7, q6a, q6b, twf, lane, Q);
         } else if constexpr (FOLD) {
@@ -1454,12 +1564,12 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
     }
 }
 
-template <int DG, int WPS, bool AP = false, bool FUSE = false, bool FOLD = false, bool QUNITS = false>
+template <int DG, int WPS, bool AP = false, bool FUSE = false, bool FOLD = false, bool QUNITS = false, bool MFMA = false>
 __global__ __launch_bounds__(128 * DG, WPS) void k_blind_rotate_lat(DevParams P, const bce_gate_desc* __restrict__ descs, u32 n_desc,
                                                                    u32 slot_stride, u32* __restrict__ acc_out,
                                                                    u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks) {
     extern __shared__ __align__(16) u32 smem[];
-    lat_bootstrap<DG, WPS, AP, FUSE, FOLD, false, QUNITS, QUNITS>(P, descs[blockIdx.x % n_desc], (blockIdx.x / n_desc) * slot_stride, blockIdx.x, smem,
+    lat_bootstrap<DG, WPS, AP, FUSE, FOLD, false, QUNITS, QUNITS, MFMA>(P, descs[blockIdx.x % n_desc], (blockIdx.x / n_desc) * slot_stride, blockIdx.x, smem,
                                            acc_out, dbg_lweN, dbg_ks);
 }
 
@@ -1471,9 +1581,11 @@ bool fused_tail_fits(const DevParams& P) {
     return (size_t)P.n + 1 <= 512 * VW && RW <= 8 && need <= (R * NP + 4 * 1280) * 4;
 }
 
-size_t blind_rotate_lat_lds_bytes(const DevParams& P) {
+// x2_ginx: the launch runs the two-workgroups-per-CU GINX build (the one with the matrix-pipe forward body and its six byte matrices)
+size_t blind_rotate_lat_lds_bytes(const DevParams& P, bool x2_ginx) {
     const size_t N = P.N, NP = N + (N >> 6) * 4, R = 2 * P.dG;
-    return (2 * N + (2 + R) * NP + 4 * 1280 + ((P.n + 1 + 3) & ~3u)) * sizeof(u32);
+    const size_t xbm = (x2_ginx && P.fold && P.fwd_units && P.fwd_mfma) ? 6 * 256 : 0;
+    return (2 * N + (2 + R) * NP + 4 * 1280 + xbm + ((P.n + 1 + 3) & ~3u)) * sizeof(u32);
 }
 
 size_t blind_rotate_lds_bytes(const DevParams& P) {
@@ -1526,12 +1638,12 @@ __global__ void k_dag_rearm(DagParams D) {
     for (size_t j = i0 + kDagAbort; j < kDagCtlWords; j += stride) D.ctl[j] = 0;
 }
 
-template <int WPS, bool AP, bool FOLD, bool QUNITS = false>
+template <int WPS, bool AP, bool FOLD, bool QUNITS = false, bool MFMA = false>
 __global__ __launch_bounds__(512, WPS) void k_bootstrap_dag(const DevParams* Pp, const DagParams* Dp) {
     extern __shared__ __align__(16) u32 smem[];
     // the worker's mailbox sits in front of the LDS layout of lat_bootstrap
     dag_worker(Dp, smem, [&](ConstDagParams& D, u32 t, u32 k) {
-        lat_bootstrap<4, WPS, AP, true, FOLD, true, QUNITS, QUNITS>(*as_constant<ConstDevParams>(Pp), D.tasks[t], D.slot_base + k * D.slot_stride, 0,
+        lat_bootstrap<4, WPS, AP, true, FOLD, true, QUNITS, QUNITS, MFMA>(*as_constant<ConstDevParams>(Pp), D.tasks[t], D.slot_base + k * D.slot_stride, 0,
                                                    smem + kDagMailboxWords, nullptr, nullptr, nullptr);
     });
 }
@@ -1552,10 +1664,11 @@ hipError_t launch_bootstrap_dag(const DevParams& P, const DevParams* d_P, const 
     using DagKernel = void (*)(const DevParams*, const DagParams*);
     const bool ap = P.method_ap != 0, x1 = wps <= 2;
     DagKernel k;
-    if (P.fold && P.fwd_units && !ap && !x1) k = k_bootstrap_dag<4, false, true, true>;   // forward transforms as quarter units
+    if (P.fold && P.fwd_units && P.fwd_mfma && !ap && !x1) k = k_bootstrap_dag<4, false, true, true, true>;   // quarter units, bits 9..4 on the matrix pipe
+    else if (P.fold && P.fwd_units && !ap && !x1) k = k_bootstrap_dag<4, false, true, true>;   // forward transforms as quarter units
     else if (P.fold) k = ap ? (x1 ? k_bootstrap_dag<2, true, true> : k_bootstrap_dag<4, true, true>) : (x1 ? k_bootstrap_dag<2, false, true> : k_bootstrap_dag<4, false, true>);
     else k = ap ? (x1 ? k_bootstrap_dag<2, true, false> : k_bootstrap_dag<4, true, false>) : (x1 ? k_bootstrap_dag<2, false, false> : k_bootstrap_dag<4, false, false>);
-    const size_t lds = blind_rotate_lat_lds_bytes(P) + kDagMailboxWords * 4;   // + the worker's mailbox in front
+    const size_t lds = blind_rotate_lat_lds_bytes(P, !ap && !x1) + kDagMailboxWords * 4;   // + the worker's mailbox in front
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, s, d_P, d_params);
@@ -1597,15 +1710,16 @@ hipError_t launch_blind_rotate(const DevParams& P, const bce_gate_desc* d, u32 n
         // launch leaves every workgroup a CU of its own, else with the 128-register one (two per CU);
         // measured against the one-wave-per-transform kernel over launch sizes 64..6144: tools/kernel_sweep.py
         using LatKernel = void (*)(DevParams, const bce_gate_desc*, u32, u32, u32*, u32*, u32*);
-        const size_t lds_lat = blind_rotate_lat_lds_bytes(P);
         const bool alone = (P.variant == 2) || (P.variant == 0 && grid.x <= P.cu_count);
         const bool x1 = alone && P.variant != 3;
+        const size_t lds_lat = blind_rotate_lat_lds_bytes(P, !ap && !x1);
         // saturated launches run the tail of EvalBinGate in the kernel's epilogue (fused_tail); a launch that leaves
         // CUs to themselves keeps the separate tail kernels, which spread one bootstrap's row gather over many CUs
         const bool fuse = !x1 && tail_fused && P.fuse_tail && fused_tail_fits(P);
         LatKernel lk;
         if (P.fold) {   // key rows l >= 1 hold ek_l - B^l ek_0 (see the kernel's FOLD note)
             if (ap) lk = x1 ? k_blind_rotate_lat<4, 2, true, false, true> : (fuse ? k_blind_rotate_lat<4, 4, true, true, true> : k_blind_rotate_lat<4, 4, true, false, true>);
+            else if (P.fwd_units && P.fwd_mfma && !x1) lk = fuse ? k_blind_rotate_lat<4, 4, false, true, true, true, true> : k_blind_rotate_lat<4, 4, false, false, true, true, true>;
             else if (P.fwd_units && !x1) lk = fuse ? k_blind_rotate_lat<4, 4, false, true, true, true> : k_blind_rotate_lat<4, 4, false, false, true, true>;
             else lk = x1 ? k_blind_rotate_lat<4, 2, false, false, true> : (fuse ? k_blind_rotate_lat<4, 4, false, true, true> : k_blind_rotate_lat<4, 4, false, false, true>);
         } else if (ap) lk = x1 ? k_blind_rotate_lat<4, 2, true, false> : (fuse ? k_blind_rotate_lat<4, 4, true, true> : k_blind_rotate_lat<4, 4, true, false>);

@@ -83,6 +83,12 @@ struct DevParams {
     const void* ksk;    // [N][baseKS][dKS][ksk_stride]
     u32* pool;          // [slots][pool_stride]
     u32 pool_stride;
+    // ---- matrix-pipe forward stages of the quarter units (at the end: the other kernels' argument layout is unchanged) ----
+    u32 fwd_mfma;          // 1 (needs fwd_units): the stages on bits 9..4 of those transforms run on the matrix pipe as i8 products of
+                           // the signed gadget digits with the limbs of one constant 64 x 64 matrix (kernels.hip,
+                           // ntt_forward_quarter3_mfma; tables and conditions: fwd_mfma.hpp; BCE_FWD_MFMA=0 keeps the quarter-unit body)
+    u32 w14, w14s;         // 2^14 mod Q and its Shoup companion (recombination of the limb products)
+    const u32* fwd_mfma_tab;   // [4 quarters][4 tiles][64 lanes][4 words]: A operands, or null
 };
 
 // LDS bytes the blind-rotation kernel needs for these parameters

@@ -1,9 +1,10 @@
-"""Static itemisation of a blind-rotation kernel's step loop: VALU / LDS / VMEM / SALU instructions per phase.
+"""Static itemisation of a blind-rotation kernel's step loop: VALU / MFMA / LDS / VMEM / SALU instructions per phase
+(v_mfma_* are counted on their own: they issue from the VALU port but execute on the matrix pipe).
 
 Build the ISA with the phase marks in (-DBCE_PHASE_PROF: every BCE_PROF_MARK is one s_memtime), cut the step loop of the
 named kernel at the marks and count instructions per segment.  The step loop holds both forward-transform bodies (whole
 row, waves 0..3; half rows, waves 4..7): segments are reported with their label-delimited basic blocks so that the
-either/or blocks can be told apart.  The quarter-unit build (…<4,4,false,FUSE,FOLD,true>) has ONE forward body, the same on every wave.
+either/or blocks can be told apart.  The quarter-unit builds (…<4,4,false,FUSE,FOLD,true[,MFMA]>) have ONE forward body, the same on every wave.
 
 usage: phase_itemize.py <kernels_prof.s> <mangled-kernel-substring>
 """
@@ -47,8 +48,8 @@ def main():
     for i, (c, blocks, mix) in enumerate(segs):
         tot.update(c)
         top = ", ".join("%s %d" % kv for kv in sorted(mix.items(), key=lambda kv: -kv[1])[:8])
-        print("segment %2d: valu %4d lds %3d vmem %3d salu %3d | valu per basic block %s" % (
-            i, c.get("valu", 0), c.get("lds", 0), c.get("vmem", 0), c.get("salu", 0), [b.get("valu", 0) for b in blocks]))
+        print("segment %2d: valu %4d mfma %2d lds %3d vmem %3d salu %3d | valu per basic block %s" % (
+            i, c.get("valu", 0), c.get("mfma", 0), c.get("lds", 0), c.get("vmem", 0), c.get("salu", 0), [b.get("valu", 0) for b in blocks]))
         print("            %s" % top)
     print("step loop total:", dict(tot))
 

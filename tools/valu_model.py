@@ -7,6 +7,9 @@
   (3) SQ_INSTS_VALU of one saturated launch (rocprofv3 --pmc pass, tools/pmc_sq_summary.py) = executed VALU
       wave-instructions per bootstrap.
 
+v_mfma_* instructions are kept out of the mix, and SQ_INSTS_MFMA (when the counter file has it) out of the executed count:
+they occupy the matrix pipe, not the integer VALU this roof is about.
+
 Output (JSON): weighted ns per wave-instruction per SIMD of this kernel's mix and the wave-instructions per bootstrap;
 bench.py turns them into `roofline.valu`: floor = insts/bootstrap x bootstraps/launch x ns / SIMDs, frac = floor / measured.
 
@@ -45,6 +48,8 @@ def step_loop(body):
 
 
 def classify(op):
+    if op.startswith("v_mfma"):   # issued from the VALU port, executed on the matrix pipe: not part of the VALU mix
+        return "mfma"
     if op.startswith("v_"):
         return "valu"
     if op.startswith("ds_"):
@@ -106,7 +111,8 @@ def main():
         "step_loop_instructions": dict(kinds),
         "step_loop_valu_mix": {op: {"count": n, "ns": price(op)[0], "how": price(op)[1]} for op, n in mix.most_common()},
         "ns_per_wave_inst_per_simd": weighted,
-        "valu_insts_per_bootstrap": pmc["SQ_INSTS_VALU"] / boots,
+        "valu_insts_per_bootstrap": (pmc["SQ_INSTS_VALU"] - pmc.get("SQ_INSTS_MFMA", 0.0)) / boots,
+        "mfma_insts_per_bootstrap": pmc.get("SQ_INSTS_MFMA", 0.0) / boots,
         "pmc_launch_bootstraps": boots,
         "cu_count": 256,
         "sources": {"isa": "hipcc -S --cuda-device-only csrc/kernels.hip", "issue_costs": issue_path, "pmc": pmc_path},
