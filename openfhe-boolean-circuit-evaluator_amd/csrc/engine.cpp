@@ -382,7 +382,7 @@ int build_ctx(u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 baseG, u32 ba
         // BCE_FWD_UNITS=0 keeps them everywhere (development / parity knob, same binary)
         const char* fu = std::getenv("BCE_FWD_UNITS");
         P.fwd_units = (P.fold && !c->is64 && c->method == BCE_GINX && P.factor_even && !(fu && fu[0] == '0')) ? 1 : 0;
-        // The stages on bits 9..4 of those transforms on the matrix pipe (kernels.hip, ntt_forward_quarter3_mfma): a variant of
+        // The stages on bits 9..4 of those transforms on the matrix pipe (kernels.hip, ntt_forward_quarter3<true>): a variant of
         // the quarter units, so it needs everything they need (folded key, GINX, even factor, N = 1024, dG = 4) and the
         // arithmetic conditions of fwd_mfma.hpp (gBits <= 7, four 7-bit limbs, exact limb sums, recombined word <= 13Q).
         // Bound chain of the forward phase with this body: recombined words < 2Q + lo_max (< 4Q for STD128*), four lazy stages

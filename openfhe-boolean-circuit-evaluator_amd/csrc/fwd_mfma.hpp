@@ -1,4 +1,4 @@
-// fwd_mfma.hpp -- host-only tables of the matrix-pipe body of the forward transforms (kernels.hip, ntt_forward_quarter3_mfma).
+// fwd_mfma.hpp -- host-only tables of the matrix-pipe body of the forward transforms (kernels.hip, ntt_forward_quarter3<true>).
 //
 // In the merged Cooley-Tukey order of this engine (tw[m + i] = psi^brv(m + i), the stage on position bit B uses
 // tw[2^(9-B) + (p >> (B + 1))]) the twiddle of a butterfly of the six stages on bits 9..4 of an N = 1024 transform does not

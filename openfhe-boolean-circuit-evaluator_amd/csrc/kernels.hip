@@ -20,7 +20,7 @@
 // stages (inverse), 64-bit MAC sums folded and reduced by lazy Barrett steps; the non-lazy Harvey
 // forms remain for Q >= 2^27.6.  The transforms are not dense contractions -- with one exception: the first six forward
 // stages of the gadget digits (7-bit operands, twiddles independent of the low position bits) are a 64 x 64 x 16 product per
-// digit row and run as i8 MFMAs in the two-workgroups-per-CU GINX build (ntt_forward_quarter3_mfma).
+// digit row and run as i8 MFMAs in the two-workgroups-per-CU GINX build (ntt_forward_quarter3<true>).
 //
 // NTT organisation (64-wide wavefronts): E = N/64 coefficients per lane held in registers, log2(E)
 // radix-2 stages per register pass, LDS re-shuffles between passes instead of one barrier per stage.
@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <iterator>
 #include <utility>
 
 #include "kernels.hpp"
@@ -449,7 +450,7 @@ __device__ __forceinline__ void ntt_forward_wave_low8(u32* poly, const uint2* tw
 // 7..5, 4..2, 1..0), two wave-local re-shuffles, in place: half the butterflies of ntt_forward_wave_low8 with every
 // lane busy.  The FOLD kernel transforms six rows per step with it: four whole rows on waves 0..3, two rows as four
 // halves on waves 4..7 -- 1.5 transforms on every SIMD (one workgroup per CU, AP, odd 2N / q; the two-workgroups-per-CU GINX
-// build runs ntt_forward_quarter3_low8 below instead).
+// build runs ntt_forward_quarter3<false> below instead).
 __device__ __forceinline__ void fwd_bfly_pair(u64& xa, u64& xb, uint2 w, u32 Q) {
     const u32 X = (u32)xa, Y = (u32)xb;
     const u64 t = mad64(__umulhi(Y, w.y), 0u - Q, mad64(Y, w.x, xa));
@@ -563,8 +564,31 @@ __device__ __forceinline__ void fwd_pass4_pair(u64 (&x)[4], uint2 wa, uint2 wb0,
         fwd_bfly_pair(x[0], x[1], wb0, Q); fwd_bfly_pair(x[2], x[3], wb1, Q);
     }
 }
-__device__ __forceinline__ void ntt_forward_quarter3_low8(u32* rows, u32 qr, uint2 w7, uint2 w6a, uint2 w6b, const uint2* twf,
-                                                          u32 lane, u32 Q) {
+// The same quarter units with the stages on bits 9..4 on the MATRIX pipe (fwd_mfma.hpp has the algebra, the tables and the
+// bounds).  The producer of the digits does not run the stages on bits 9 and 8: it stores the signed digits s = d - 2^(gBits-1)
+// in [-64, 64) as SIGNED bytes, four per thread and row in one dword, into a byte matrix Xb[column j = p & 15][K slot],
+// 1 KiB per digit row.  K slot k = 4 ((p >> 4) & 15) + (p >> 8) (fwd_mfma_h_of_k is its inverse); a column's four 16-byte K
+// groups g are stored at 64 j + 16 (g ^ (-(j >> 2) & 3)): the 16-byte read below (lane = (g, j), lane groups of
+// ds_read_b128) and the 4-byte stores (2-way at most) are conflict-free.
+// Per digit row a wave issues four v_mfma_i32_16x16x64_i8, one per tile of four output rows h' = 16 qr + 4 i + o:
+//   A (constant, from the table)  row 4 o + limb = limb `limb` of M6[h'][.], so that -- C/D map: column = lane & 15, row =
+//                                 4 (lane >> 4) + register -- a lane's four accumulator registers are the four limbs of ONE word;
+//   B (one 16-byte LDS read)      the digits of column j = lane & 15, K group lane >> 4;
+//   C                             (Q, 0, Q, 0), the same for every tile: the limb sums are signed (|S0 + 2^7 S1| <= 129 * 64 * 127 * 64
+//                                 < Q, host check), the offsets make low and high part positive.
+// word = (S0 + Q + 2^7 S1) + 2^14 (S2 + Q + 2^7 S3): two v_lshl_add_u32 and one lazy Shoup product by 2^14 whose 64-bit addend is
+// the low part; < 2Q + lo_max < 4Q (the six lazy stages it replaces leave < 13Q).  Afterwards a lane holds, per row, quarter
+// positions i = b7..b0 with b7 b6 = tile (register), b5 b4 = lane >> 4, b3..b0 = lane & 15; the passes on bits 3, 2 and 1, 0
+// are those of the VALU form with image B's upper fields swapped to (b7 b6 | b5 b4 b1 b0 | b3 b2), so that the
+// 4-byte stores of one register cover 64 consecutive words.
+// One body for both: MFMA = false takes the wave's twiddles of the stages on bits 7, 6 (w7, w6a, w6b); MFMA = true takes the
+// byte matrices of its three rows (xb), the A operands of its four tiles and 2^14 with its Shoup companion (w14).  The
+// arguments of the other kind are unused.
+typedef int v4i __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32 xb_group(u32 j, u32 g) { return 64u * j + 16u * ((g ^ (0u - (j >> 2))) & 3u); }  // byte offset
+template <bool MFMA>
+__device__ __forceinline__ void ntt_forward_quarter3(u32* rows, u32 qr, uint2 w7, uint2 w6a, uint2 w6b, const u32* xb,
+                                                     const v4i (&A)[4], uint2 w14, const uint2* twf, u32 lane, u32 Q) {
     constexpr int RS = 2 * Cfg<10>::NP;   // words between the three rows of a wave
     u64 xp[3][4];
     // a lane's 16 bytes hold its registers in the order 0, 2, 1, 3: the loaded register pairs (x0, x2) and (x1, x3) are then
@@ -589,30 +613,59 @@ __device__ __forceinline__ void ntt_forward_quarter3_low8(u32* rows, u32 qr, uin
 #pragma unroll
             for (int r = 0; r < 4; ++r) p[k * RS + 64 * r] = (u32)xp[k][r];
     };
-    {   // bits 7, 6: lane = b5..b0, twiddles tw[4 + qr], tw[8 + 2 qr + b7] (wave-uniform)
-        const u32* const p = rows + lane;
+    if constexpr (!MFMA) {
+        {   // bits 7, 6: lane = b5..b0, twiddles tw[4 + qr], tw[8 + 2 qr + b7] (wave-uniform)
+            const u32* const p = rows + lane;
 #pragma unroll
-        for (int k = 0; k < 3; ++k)
+            for (int k = 0; k < 3; ++k)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) xp[k][r] = pair_of(p[k * RS + 68 * r]);
+                for (int r = 0; r < 4; ++r) xp[k][r] = pair_of(p[k * RS + 68 * r]);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) fwd_pass4_pair<true>(xp[k], w7, w6a, w6b, Q);
-        store4(((lane & 15u) << 2) | ((lane >> 3) & 2u) | (lane >> 5));
-    }
-    wave_sync();
-    {   // bits 5, 4: lane = (b7 b6, b3..b0), twiddles tw[16 + 4 qr + b7b6], tw[32 + 8 qr + 2 b7b6 + b5] (one 16-byte read)
-        const u32 h = lane >> 4;
-        const uint2 w5 = twf[tw_pos<16>(4 * qr + h)];
-        const uint4 w4 = *reinterpret_cast<const uint4*>(twf + tw_pos<32>(8 * qr + 2 * h));
-        pass16(w5, make_uint2(w4.x, w4.y), make_uint2(w4.z, w4.w));
-        store4(((lane >> 4) << 4) | ((lane & 3u) << 2) | ((lane >> 1) & 2u) | ((lane >> 3) & 1u));
-    }
-    wave_sync();
-    {   // bits 3, 2: lane = (b5 b4, b7 b6, b1 b0); i >> 4 = h; twiddles tw_pos<64>(16 qr + h), tw_pos<128>(2 (16 qr + h) + b3)
-        const u32 h = (((lane >> 2) & 3u) << 2) | (lane >> 4);
-        const uint2* const t = twf + tw_pos<64>(16 * qr + h);
-        pass16(t[0], t[64], t[128]);
-        store4((((lane >> 2) & 3u) << 4) | ((lane >> 4) << 2) | ((lane & 1u) << 1) | ((lane >> 1) & 1u));
+            for (int k = 0; k < 3; ++k) fwd_pass4_pair<true>(xp[k], w7, w6a, w6b, Q);
+            store4(((lane & 15u) << 2) | ((lane >> 3) & 2u) | (lane >> 5));
+        }
+        wave_sync();
+        {   // bits 5, 4: lane = (b7 b6, b3..b0), twiddles tw[16 + 4 qr + b7b6], tw[32 + 8 qr + 2 b7b6 + b5] (one 16-byte read)
+            const u32 h = lane >> 4;
+            const uint2 w5 = twf[tw_pos<16>(4 * qr + h)];
+            const uint4 w4 = *reinterpret_cast<const uint4*>(twf + tw_pos<32>(8 * qr + 2 * h));
+            pass16(w5, make_uint2(w4.x, w4.y), make_uint2(w4.z, w4.w));
+            store4(((lane >> 4) << 4) | ((lane & 3u) << 2) | ((lane >> 1) & 2u) | ((lane >> 3) & 1u));
+        }
+        wave_sync();
+        {   // bits 3, 2: lane = (b5 b4, b7 b6, b1 b0); i >> 4 = h; twiddles tw_pos<64>(16 qr + h), tw_pos<128>(2 (16 qr + h) + b3)
+            const u32 h = (((lane >> 2) & 3u) << 2) | (lane >> 4);
+            const uint2* const t = twf + tw_pos<64>(16 * qr + h);
+            pass16(t[0], t[64], t[128]);
+            store4((((lane >> 2) & 3u) << 4) | ((lane >> 4) << 2) | ((lane & 1u) << 1) | ((lane >> 1) & 1u));
+        }
+    } else {
+        {   // bits 9..4: lane = (K group | column) for B, (b5 b4 | b3..b0) for the result
+            const char* const pb = reinterpret_cast<const char*>(xb) + xb_group(lane & 15u, lane >> 4);
+            v4i B[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) B[k] = *reinterpret_cast<const v4i*>(pb + 1024 * k);
+            const u32 negQ = 0u - Q;
+            const v4i c0 = {(int)Q, 0, (int)Q, 0};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const v4i s = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[i], B[k], c0, 0, 0, 0);
+                    const u32 lo = ((u32)s[1] << 7) + (u32)s[0], hi = ((u32)s[3] << 7) + (u32)s[2];
+                    // the addend pair is (lo, S1): S1 already sits in the register next to S0 and the high half is a don't-care
+                    xp[k][i] = mad64(__umulhi(hi, w14.y), negQ, mad64_su(hi, w14.x, ((u64)(u32)s[1] << 32) | lo));
+                }
+            }
+            store4(((lane >> 4) << 4) | ((lane & 3u) << 2) | ((lane >> 1) & 2u) | ((lane >> 3) & 1u));
+        }
+        wave_sync();
+        {   // bits 3, 2: lane = (b7 b6, b5 b4, b1 b0); i >> 4 = h; twiddles tw_pos<64>(16 qr + h), tw_pos<128>(2 (16 qr + h) + b3)
+            const u32 h = lane >> 2;
+            const uint2* const t = twf + tw_pos<64>(16 * qr + h);
+            pass16(t[0], t[64], t[128]);
+            store4((h << 2) | ((lane & 1u) << 1) | ((lane >> 1) & 1u));
+        }
     }
     wave_sync();
     {   // bits 1, 0: lane = (b3 b2, b7..b4); twiddles tw_pos<256>(4 (16 qr + h) + b3b2), tw_pos<512>(8 (16 qr + h) + 2 b3b2 + b1)
@@ -620,85 +673,6 @@ __device__ __forceinline__ void ntt_forward_quarter3_low8(u32* rows, u32 qr, uin
         const uint2* const t = twf + 512 + 128 * g + 16 * qr + h;
         pass16(twf[256 + 64 * g + 16 * qr + h], t[0], t[64]);
         // positions 16 h + 4 g + (0..3) of the quarter, padded layout
-        uint4* const p = reinterpret_cast<uint4*>(rows + 16 * h + 4 * g + 4 * (h >> 2));
-#pragma unroll
-        for (int k = 0; k < 3; ++k) p[k * (RS / 4)] = make_uint4((u32)xp[k][0], (u32)xp[k][1], (u32)xp[k][2], (u32)xp[k][3]);
-    }
-    wave_sync();
-}
-// The same quarter units with the stages on bits 9..4 on the MATRIX pipe (fwd_mfma.hpp has the algebra, the tables and the
-// bounds).  The producer of the digits does not run the stages on bits 9 and 8: it stores the signed digits s = d - 2^(gBits-1)
-// in [-64, 64) as SIGNED bytes, four per thread and row in one dword, into a byte matrix Xb[column j = p & 15][K slot],
-// 1 KiB per digit row.  K slot k = 4 ((p >> 4) & 15) + (p >> 8) (fwd_mfma_h_of_k is its inverse); a column's four 16-byte K
-// groups g are stored at 64 j + 16 (g ^ (-(j >> 2) & 3)): the 16-byte read below (lane = (g, j), lane groups of
-// ds_read_b128) and the 4-byte stores (2-way at most) are conflict-free.
-// Per digit row a wave issues four v_mfma_i32_16x16x64_i8, one per tile of four output rows h' = 16 qr + 4 i + o:
-//   A (constant, from the table)  row 4 o + limb = limb `limb` of M6[h'][.], so that -- C/D map: column = lane & 15, row =
-//                                 4 (lane >> 4) + register -- a lane's four accumulator registers are the four limbs of ONE word;
-//   B (one 16-byte LDS read)      the digits of column j = lane & 15, K group lane >> 4;
-//   C                             (Q, 0, Q, 0), the same for every tile: the limb sums are signed (|S0 + 2^7 S1| <= 129 * 64 * 127 * 64
-//                                 < Q, host check), the offsets make low and high part positive.
-// word = (S0 + Q + 2^7 S1) + 2^14 (S2 + Q + 2^7 S3): two v_lshl_add_u32 and one lazy Shoup product by 2^14 whose 64-bit addend is
-// the low part; < 2Q + lo_max < 4Q (the six lazy stages it replaces leave < 13Q).  Afterwards a lane holds, per row, quarter
-// positions i = b7..b0 with b7 b6 = tile (register), b5 b4 = lane >> 4, b3..b0 = lane & 15; the passes on bits 3, 2 and 1, 0
-// are those of ntt_forward_quarter3_low8 with image B's upper fields swapped to (b7 b6 | b5 b4 b1 b0 | b3 b2), so that the
-// 4-byte stores of one register cover 64 consecutive words.
-typedef int v4i __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32 xb_group(u32 j, u32 g) { return 64u * j + 16u * ((g ^ (0u - (j >> 2))) & 3u); }  // byte offset
-__device__ __forceinline__ void ntt_forward_quarter3_mfma(u32* rows, const u32* xb, u32 qr, const v4i (&A)[4], uint2 w14,
-                                                          const uint2* twf, u32 lane, u32 Q) {
-    constexpr int RS = 2 * Cfg<10>::NP;   // words between the three rows of a wave
-    u64 xp[3][4];
-    auto pass16 = [&](uint2 wa, uint2 wb0, uint2 wb1) {   // as in ntt_forward_quarter3_low8
-        const uint4* const p = reinterpret_cast<const uint4*>(rows + 4 * lane);
-        uint4 v[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) v[k] = p[k * (RS / 4)];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            xp[k][0] = ((u64)v[k].y << 32) | v[k].x; xp[k][2] = pair_of(v[k].y);
-            xp[k][1] = ((u64)v[k].w << 32) | v[k].z; xp[k][3] = pair_of(v[k].w);
-            fwd_pass4_pair<false>(xp[k], wa, wb0, wb1, Q);
-        }
-    };
-    auto store4 = [&](u32 off) {          // register r of every row to off + 64 r
-        u32* const p = rows + off;
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) p[k * RS + 64 * r] = (u32)xp[k][r];
-    };
-    {   // bits 9..4: lane = (K group | column) for B, (b5 b4 | b3..b0) for the result
-        const char* const pb = reinterpret_cast<const char*>(xb) + xb_group(lane & 15u, lane >> 4);
-        v4i B[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) B[k] = *reinterpret_cast<const v4i*>(pb + 1024 * k);
-        const u32 negQ = 0u - Q;
-        const v4i c0 = {(int)Q, 0, (int)Q, 0};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const v4i s = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[i], B[k], c0, 0, 0, 0);
-                const u32 lo = ((u32)s[1] << 7) + (u32)s[0], hi = ((u32)s[3] << 7) + (u32)s[2];
-                // the addend pair is (lo, S1): S1 already sits in the register next to S0 and the high half is a don't-care
-                xp[k][i] = mad64(__umulhi(hi, w14.y), negQ, mad64_su(hi, w14.x, ((u64)(u32)s[1] << 32) | lo));
-            }
-        }
-        store4(((lane >> 4) << 4) | ((lane & 3u) << 2) | ((lane >> 1) & 2u) | ((lane >> 3) & 1u));
-    }
-    wave_sync();
-    {   // bits 3, 2: lane = (b7 b6, b5 b4, b1 b0); i >> 4 = h; twiddles tw_pos<64>(16 qr + h), tw_pos<128>(2 (16 qr + h) + b3)
-        const u32 h = lane >> 2;
-        const uint2* const t = twf + tw_pos<64>(16 * qr + h);
-        pass16(t[0], t[64], t[128]);
-        store4((h << 2) | ((lane & 1u) << 1) | ((lane >> 1) & 1u));
-    }
-    wave_sync();
-    {   // bits 1, 0: lane = (b3 b2, b7..b4), as in ntt_forward_quarter3_low8
-        const u32 h = lane & 15u, g = lane >> 4;
-        const uint2* const t = twf + 512 + 128 * g + 16 * qr + h;
-        pass16(twf[256 + 64 * g + 16 * qr + h], t[0], t[64]);
         uint4* const p = reinterpret_cast<uint4*>(rows + 16 * h + 4 * g + 4 * (h >> 2));
 #pragma unroll
         for (int k = 0; k < 3; ++k) p[k * (RS / 4)] = make_uint4((u32)xp[k][0], (u32)xp[k][1], (u32)xp[k][2], (u32)xp[k][3]);
@@ -1276,27 +1250,55 @@ __device__ __forceinline__ void split_inverse_rest(const SplitInv<REGTW>& S, con
 //   the accumulator rows where the digit-0 rows used to be: 6 forward transforms per step instead of 8, same
 //   accumulator words.  The evaluation-form accumulator is double-buffered between `acc` and the two digit rows that
 //   became free (other threads read a component's words as a MAC row while its owner writes the new ones).
-// lat_bootstrap: ONE gate bootstrap by the calling workgroup (all 128 DG threads), the body shared by the per-frontier
+//
+// The forward body of the step's digit rows, i.e. the builds of the kernel that differ in more than a register budget:
+enum class Fwd {
+    Rows,           // plain key: eight digit rows, a whole row per wave (ntt_forward_wave_low8)
+    RowsAndHalves,  // folded key: six rows; rows 2..5 whole on waves 0..3, rows 6, 7 as halves on waves 4..7 (ntt_forward_half_low8)
+    Quarters,       // folded key: six rows as 24 quarter units, three per wave (ntt_forward_quarter3<false>)
+    QuartersMfma,   // the same with the stages on bits 9..4 as i8 matrix products (ntt_forward_quarter3<true>)
+};
+// One build of lat_bootstrap.  WPS = waves per SIMD the register budget allows: 2 (one workgroup per CU) or 4 (two); AP,
+// FUSE, FOLD as above; everything else follows from these four.
+template <int WPS_, bool AP_, bool FUSE_, Fwd FWD_>
+struct LatVariant {
+    static constexpr int LOGN = 10, DG = 4, WPS = WPS_;   // the split inverse transform is laid out for 8 waves: dG = 4
+    static constexpr bool AP = AP_, FUSE = FUSE_, FOLD = FWD_ != Fwd::Rows;
+    static constexpr bool MFMA = FWD_ == Fwd::QuartersMfma, QUNITS = MFMA || FWD_ == Fwd::Quarters;
+    static constexpr bool EVENF = QUNITS;                 // MAC tail for an even 2N / q, which the host requires of the quarter units
+    static constexpr bool REGTW = WPS <= 2;               // inverse twiddles in registers
+    static constexpr u32 R = 2 * DG, T = 64 * R;          // digit rows = waves, threads
+    static constexpr u32 PR = REGTW ? R : R / 2;          // key rows of each kind requested during the inverse passes
+    static_assert(WPS == 2 || WPS == 4, "one or two workgroups per CU");
+    static_assert(!QUNITS || (WPS == 4 && !AP), "quarter units (folded key by construction): two workgroups per CU, GINX");
+};
+// LDS of one workgroup of lat_bootstrap, in words: used by the kernel, by its launchers and by fused_tail_fits
+struct LatLds {
+    static constexpr u32 N = Cfg<10>::N, NP = Cfg<10>::NP, R = 8, XB = 1280;
+    static constexpr u32 twf = 0;                  // uint2 [N] forward twiddles
+    static constexpr u32 acc = twf + 2 * N;        // [2][NP]
+    static constexpr u32 dct = acc + 2 * NP;       // [R][NP]
+    static constexpr u32 xab = dct + R * NP;       // [2 polynomials][2 buffers][XB]
+    static constexpr u32 xbm = xab + 4 * XB;       // MFMA only: [2 components][3 digit rows] byte matrices of 1 KiB (256 words)
+    static constexpr u32 av(bool mfma) { return xbm + (mfma ? 6 * 256 : 0); }   // a[0..n), b
+    static constexpr size_t bytes(bool mfma, u32 n) { return (av(mfma) + ((n + 1 + 3) & ~3u)) * sizeof(u32); }
+    static constexpr size_t tail_bytes = (xbm - dct) * sizeof(u32);   // digit rows + exchange buffers: dead when the fused tail runs
+};
+// lat_bootstrap: ONE gate bootstrap by the calling workgroup (all 512 threads), the body shared by the per-frontier
 // kernel k_blind_rotate_lat and the dependency-driven persistent kernel k_bootstrap_dag.  g: the gate, soff: slot offset
 // of the instance, boot: index of this bootstrap in acc_out / the debug buffers (acc_out may be null).
-// WPS = waves per SIMD the register budget allows: 2 (one workgroup per CU) or 4 (two)
-// MFMA (needs QUNITS): the forward stages on bits 9..4 as i8 matrix products (ntt_forward_quarter3_mfma)
-template <int DG, int WPS, bool AP, bool FUSE, bool FOLD, bool PERSIST = false, bool QUNITS = false, bool EVENF = false, bool MFMA = false, typename PT>
+// V: a LatVariant; PERSIST: the caller is the persistent kernel's loop.
+template <class V, bool PERSIST, typename PT>
 __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g, const u32 soff, const u32 boot, u32* smem,
                                               u32* __restrict__ acc_out, u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks) {
-    static_assert(DG == 4, "the split inverse transform is laid out for 8 waves");
-    static_assert(!QUNITS || (FOLD && WPS >= 4), "quarter units: six digit rows on eight waves, two workgroups per CU");
-    static_assert(!MFMA || (QUNITS && !AP), "matrix-pipe forward stages: a variant of the quarter units");
-    constexpr int LOGN = 10;
+    constexpr int LOGN = V::LOGN, DG = V::DG, WPS = V::WPS;
+    constexpr bool AP = V::AP, FUSE = V::FUSE, FOLD = V::FOLD, QUNITS = V::QUNITS, MFMA = V::MFMA;
     using C = Cfg<LOGN>;
     constexpr int N = C::N, NP = C::NP;
-    constexpr u32 R = 2 * DG, T = 64 * R, XB = 1280;
-    uint2* twf = reinterpret_cast<uint2*>(smem);
-    u32* acc = reinterpret_cast<u32*>(twf + N);  // [2][NP]
-    u32* dct = acc + 2 * NP;                     // [R][NP]
-    u32* xab = dct + R * NP;                     // [2 polynomials][2 buffers][XB]
-    u32* xbm = xab + 4 * XB;                     // MFMA: [2 components][3 digit rows] byte matrices of 1 KiB (256 words)
-    u32* av = xbm + (MFMA ? 6 * 256 : 0);
+    constexpr u32 R = V::R, T = V::T, PR = V::PR, XB = LatLds::XB;
+    constexpr bool REGTW = V::REGTW;
+    uint2* twf = reinterpret_cast<uint2*>(smem + LatLds::twf);
+    u32 *acc = smem + LatLds::acc, *dct = smem + LatLds::dct, *xab = smem + LatLds::xab, *xbm = smem + LatLds::xbm, *av = smem + LatLds::av(MFMA);
 
     u32 tid_ = threadIdx.x;
     // opaque inside the persistent kernel's loop: nothing derived from the thread index is hoisted out of the bootstrap
@@ -1327,7 +1329,6 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
     bootstrap_prologue<LOGN, true, T>(P, g, soff, twf, acc, av, tid, lane, wave);
 
     const u32 c = wave >> 2;  // this wave's inverse-transform group = accumulator component
-    constexpr bool REGTW = WPS <= 2;
     SplitInv<REGTW> S;
     split_inv_setup(S, twf, tid & 255u);
     u32* const accc = acc + c * NP;
@@ -1339,11 +1340,7 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
     // GINX key: n * 2 RGSW ciphertexts; AP key: n * baseR * dR of them (< 2^31 bytes for every 32-bit parameter set)
     const __amdgpu_buffer_rsrc_t rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<u32*>(P.bsk), 0, AP ? 0x7FFFFFFF : (int)(n * 2 * rgsw * 4), 0x00020000);
-#ifdef BCE_BARRETT_TAIL   // development: round 3's fold + Barrett tail, for the same-box A/B (tools/tail_ab.sh)
-    const __amdgpu_buffer_rsrc_t psi_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32*>(P.psi_tab), 0, N * 4, 0x00020000);
-#else
     const __amdgpu_buffer_rsrc_t psi_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32*>(P.psi_tab_r2), 0, N * 4, 0x00020000);
-#endif
     // digit extraction constants (see the throughput kernel)
     const u32 gb = P.gBits, Qh = Q >> 1;
     u32 off = 0;
@@ -1394,8 +1391,7 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
         }
         // key rows of this step, requested during phase 1 (a quarter at the start of each inverse pass),
         // consumed in phase 3: all 16 with the 256-register budget, the first half of each key with the
-        // 128-register one (the rest is requested at the end of phase 2)
-        constexpr u32 PR = (WPS <= 2) ? R : R / 2;
+        // 128-register one (the rest is requested at the end of phase 2): PR rows
         uint4 kA[R], kB[R];
         v4i mA[4];       // MFMA: A operands of the wave's four tiles, requested at pass 4 of the inverse transform
         auto request_rows = [&](auto kc) {
@@ -1449,29 +1445,19 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
         block_sync_lds();
         BCE_PROF_MARK(1);
         // (2) one wave per decomposed polynomial: the remaining 8 forward stages, in place
-        // two workgroups per CU: the multiplier-bound forward transforms run at LOW wave priority, so the other
-        // workgroup's latency-bound phases (inverse passes, MAC tail) get their issue slots first and the transform
-        // waves fill the gaps (+1..4 %, same-box A/B; the opposite policy costs 7 %, and a lone workgroup loses 6 %
-        // with either, hence only in this build)
-        // (folded key: the half-row waves 4..7 -- the younger ones, which the arbiter serves last -- one level above the
-        // whole-row waves, so that both kinds finish the phase together: -2 % per saturated launch, profiles/r02_prio_ab.log)
-        // (round 4, profiles/r04_fwd_prio_ab.log: the whole-row waves above the half-row ones, or both at 1 -- within 0.3 % of this)
-        // (matrix-pipe body: the same policy is kept.)
-        // (quarter units: equal waves.  The same policy -- the younger half one level above the low level -- against both
-        // at the low level and the older half above, -DBCE_FWD_UNITS_PRIO=1 / 2: profiles/fwd_units_ab.log)
-#if defined(BCE_FWD_UNITS_PRIO) && BCE_FWD_UNITS_PRIO == 1
-        if constexpr (QUNITS) __builtin_amdgcn_s_setprio(0); else
-#elif defined(BCE_FWD_UNITS_PRIO) && BCE_FWD_UNITS_PRIO == 2
-        if constexpr (QUNITS) { if (wave < 4) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); } else
-#endif
+        // two workgroups per CU: the multiplier-bound forward transforms run at LOW wave priority, so that the other
+        // workgroup's latency-bound phases (inverse passes, MAC tail) get their issue slots first and the transform waves
+        // fill the gaps; with a folded key waves 4..7 -- the younger ones, which the arbiter serves last -- run one level
+        // above waves 0..3, so that all finish the phase together.  The same policy for every folded forward body; a lone
+        // workgroup loses with any, hence only in this build.  Alternatives measured: profiles/r02_prio_ab.log,
+        // profiles/r04_fwd_prio_ab.log, profiles/fwd_units_ab.log.
         if constexpr (WPS >= 4) { if (FOLD && wave >= 4) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
 #ifndef BCE_SKIP_FWD   // development: -DBCE_SKIP_FWD / -DBCE_SKIP_MAC leave a phase's LDS traffic out (wrong results) to
                        // attribute the LDS counters to phases, tools/lds_attribution.sh
-        if constexpr (MFMA) {
-            ntt_forward_quarter3_mfma(dct + (2 + c) * NP + 272u * (wave & 3u), xbm + 3 * c * 256, wave & 3u, mA, make_uint2(P.w14, P.w14s), twf, lane, Q);
-        } else if constexpr (QUNITS) {
+        if constexpr (QUNITS) {
             // six rows (2..7) as 24 quarters, three per wave: quarter wave & 3 of this wave's own component's rows 2 + c, 4 + c, 6 + c
-            ntt_forward_quarter3_low8(dct + (2 + c) * NP + 272u * (wave & 3u), wave & 3u, q7, q6a, q6b, twf, lane, Q);
+            ntt_forward_quarter3<MFMA>(dct + (2 + c) * NP + 272u * (wave & 3u), wave & 3u, q7, q6a, q6b, xbm + 3 * c * 256, mA,
+                                       make_uint2(P.w14, P.w14s), twf, lane, Q);
         } else if constexpr (FOLD) {
             // six rows (2..7) on eight waves: whole rows 2..5 on waves 0..3, rows 6 and 7 as halves on waves 4..7
             if (wave < 4) ntt_forward_wave_low8(dct + (2 + wave) * NP, twf, lane, Q);
@@ -1517,14 +1503,7 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
                 for (int e = 0; e < 4; ++e) anew[e] = barrett_fold(sp[e], P.c32, Q, P.red_shift, P.red_mu);
                 *reinterpret_cast<uint4*>(accw) = make_uint4(anew[0], anew[1], anew[2], anew[3]);
             } else {
-#ifdef BCE_BARRETT_TAIL
-                const u32 a4 = ap & 3u;
-                const uint2 Ia = make_uint2(P.I4[a4], P.I4s[a4]);
-                const uint2 Ina = make_uint2(P.I4[(4u - a4) & 3u], P.I4s[(4u - a4) & 3u]);
-                ginx_mac_tail<LOGN, true>(P, psi_rsrc, Q, ap, Ia, Ina, mp0, accr, accw, sp, sn, anew);
-#else
-                ginx_mac_tail_redc<LOGN, EVENF>(P, psi_rsrc, Q, ap, mp0, accr, accw, sp, sn, anew);
-#endif
+                ginx_mac_tail_redc<LOGN, V::EVENF>(P, psi_rsrc, Q, ap, mp0, accr, accw, sp, sn, anew);
             }
             if constexpr (FOLD) cb = 2 * NP - cb;
             split_pass0(S, twf, anew, xa, Q, P.mu32);  // mc == c, mp0 == 4 t: this thread's pass-0 registers
@@ -1555,7 +1534,7 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
     if constexpr (FUSE) {
         if constexpr (WPS >= 4) __builtin_amdgcn_s_setprio(0);
         __syncthreads();
-        // rowidx and the partial sums live in the digit rows + exchange buffers (54 KiB, all dead now)
+        // rowidx and the partial sums live in the digit rows + exchange buffers (LatLds::tail_bytes = 54 KiB, all dead now)
         u32* rowidx = dct;
         u64* red = reinterpret_cast<u64*>(dct + ((N * P.dKS + 3) & ~3u));
         u32* outp = P.pool + (size_t)(g.out + soff) * P.pool_stride;
@@ -1564,28 +1543,46 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
     }
 }
 
-template <int DG, int WPS, bool AP = false, bool FUSE = false, bool FOLD = false, bool QUNITS = false, bool MFMA = false>
-__global__ __launch_bounds__(128 * DG, WPS) void k_blind_rotate_lat(DevParams P, const bce_gate_desc* __restrict__ descs, u32 n_desc,
+template <class V>
+__global__ __launch_bounds__(V::T, V::WPS) void k_blind_rotate_lat(DevParams P, const bce_gate_desc* __restrict__ descs, u32 n_desc,
                                                                    u32 slot_stride, u32* __restrict__ acc_out,
                                                                    u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks) {
     extern __shared__ __align__(16) u32 smem[];
-    lat_bootstrap<DG, WPS, AP, FUSE, FOLD, false, QUNITS, QUNITS, MFMA>(P, descs[blockIdx.x % n_desc], (blockIdx.x / n_desc) * slot_stride, blockIdx.x, smem,
-                                           acc_out, dbg_lweN, dbg_ks);
+    lat_bootstrap<V, false>(P, descs[blockIdx.x % n_desc], (blockIdx.x / n_desc) * slot_stride, blockIdx.x, smem, acc_out, dbg_lweN, dbg_ks);
 }
 
 // LDS the fused tail needs inside the digit rows + exchange buffers of k_blind_rotate_lat (T = 512 threads)
 bool fused_tail_fits(const DevParams& P) {
-    const size_t N = P.N, NP = N + (N >> 6) * 4, R = 2 * P.dG;
+    const size_t N = P.N;
     const size_t VW = P.ksk_u16 ? 8 : 4, G = (P.n + VW) / VW, Gv = G < 512 ? G : 512, RW = (Gv + 63) / 64, SL = 8 / RW;
     const size_t need = ((N * P.dKS + 3) & ~(size_t)3) * 4 + SL * Gv * VW * 8;
-    return (size_t)P.n + 1 <= 512 * VW && RW <= 8 && need <= (R * NP + 4 * 1280) * 4;
+    return (size_t)P.n + 1 <= 512 * VW && RW <= 8 && need <= LatLds::tail_bytes;
 }
 
-// x2_ginx: the launch runs the two-workgroups-per-CU GINX build (the one with the matrix-pipe forward body and its six byte matrices)
-size_t blind_rotate_lat_lds_bytes(const DevParams& P, bool x2_ginx) {
-    const size_t N = P.N, NP = N + (N >> 6) * 4, R = 2 * P.dG;
-    const size_t xbm = (x2_ginx && P.fold && P.fwd_units && P.fwd_mfma) ? 6 * 256 : 0;
-    return (2 * N + (2 + R) * NP + 4 * 1280 + xbm + ((P.n + 1 + 3) & ~3u)) * sizeof(u32);
+// ---- which build a launch runs ---------------------------------------------------------------------------------------
+// The builds that exist, as (waves per SIMD, AP, forward body); k_bootstrap_dag has each with the tail fused,
+// k_blind_rotate_lat each without and the two-workgroups-per-CU ones also with (launch_blind_rotate).  A new forward body is
+// an enumerator of Fwd, a line here and a line in lat_variant().
+struct LatBuild { int wps; bool ap; Fwd fwd; };
+constexpr bool operator==(const LatBuild& a, const LatBuild& b) { return a.wps == b.wps && a.ap == b.ap && a.fwd == b.fwd; }
+constexpr LatBuild kLatBuilds[] = {
+    {2, false, Fwd::Rows}, {2, true, Fwd::Rows}, {2, false, Fwd::RowsAndHalves}, {2, true, Fwd::RowsAndHalves},
+    {4, false, Fwd::Rows}, {4, true, Fwd::Rows}, {4, false, Fwd::RowsAndHalves}, {4, true, Fwd::RowsAndHalves},
+    {4, false, Fwd::Quarters}, {4, false, Fwd::QuartersMfma},
+};
+// The build for a context and a register budget (x1: one workgroup per CU).  P.fwd_units / P.fwd_mfma hold what the engine
+// checked (tables, even 2N / q) and BCE_FWD_UNITS / BCE_FWD_MFMA; the quarter units exist for GINX at two workgroups per CU.
+LatBuild lat_variant(const DevParams& P, bool x1) {
+    const bool ap = P.method_ap != 0, quarters = P.fwd_units && !ap && !x1;
+    const Fwd fwd = !P.fold ? Fwd::Rows : !quarters ? Fwd::RowsAndHalves : P.fwd_mfma ? Fwd::QuartersMfma : Fwd::Quarters;
+    return {x1 ? 2 : 4, ap, fwd};
+}
+size_t blind_rotate_lat_lds_bytes(const DevParams& P, const LatBuild& v) { return LatLds::bytes(v.fwd == Fwd::QuartersMfma, P.n); }
+// of(integral_constant<size_t, I>) for the entry I of kLatBuilds that equals v: the kernel pointer; null if there is none
+template <size_t I = 0, class F>
+auto lat_kernel(const LatBuild& v, F of) -> decltype(of(std::integral_constant<size_t, 0>{})) {
+    if constexpr (I == std::size(kLatBuilds)) return nullptr;
+    else return kLatBuilds[I] == v ? of(std::integral_constant<size_t, I>{}) : lat_kernel<I + 1>(v, of);
 }
 
 size_t blind_rotate_lds_bytes(const DevParams& P) {
@@ -1638,13 +1635,13 @@ __global__ void k_dag_rearm(DagParams D) {
     for (size_t j = i0 + kDagAbort; j < kDagCtlWords; j += stride) D.ctl[j] = 0;
 }
 
-template <int WPS, bool AP, bool FOLD, bool QUNITS = false, bool MFMA = false>
-__global__ __launch_bounds__(512, WPS) void k_bootstrap_dag(const DevParams* Pp, const DagParams* Dp) {
+template <class V>
+__global__ __launch_bounds__(V::T, V::WPS) void k_bootstrap_dag(const DevParams* Pp, const DagParams* Dp) {
     extern __shared__ __align__(16) u32 smem[];
     // the worker's mailbox sits in front of the LDS layout of lat_bootstrap
     dag_worker(Dp, smem, [&](ConstDagParams& D, u32 t, u32 k) {
-        lat_bootstrap<4, WPS, AP, true, FOLD, true, QUNITS, QUNITS, MFMA>(*as_constant<ConstDevParams>(Pp), D.tasks[t], D.slot_base + k * D.slot_stride, 0,
-                                                   smem + kDagMailboxWords, nullptr, nullptr, nullptr);
+        lat_bootstrap<V, true>(*as_constant<ConstDevParams>(Pp), D.tasks[t], D.slot_base + k * D.slot_stride, 0, smem + kDagMailboxWords,
+                               nullptr, nullptr, nullptr);
     });
 }
 
@@ -1662,13 +1659,13 @@ hipError_t launch_bootstrap_dag(const DevParams& P, const DevParams* d_P, const 
     if (!dag_kernel_available(P)) return hipErrorInvalidValue;
     if (P.is64) return launch_bootstrap_dag64(P, d_P, d_params, grid, s);
     using DagKernel = void (*)(const DevParams*, const DagParams*);
-    const bool ap = P.method_ap != 0, x1 = wps <= 2;
-    DagKernel k;
-    if (P.fold && P.fwd_units && P.fwd_mfma && !ap && !x1) k = k_bootstrap_dag<4, false, true, true, true>;   // quarter units, bits 9..4 on the matrix pipe
-    else if (P.fold && P.fwd_units && !ap && !x1) k = k_bootstrap_dag<4, false, true, true>;   // forward transforms as quarter units
-    else if (P.fold) k = ap ? (x1 ? k_bootstrap_dag<2, true, true> : k_bootstrap_dag<4, true, true>) : (x1 ? k_bootstrap_dag<2, false, true> : k_bootstrap_dag<4, false, true>);
-    else k = ap ? (x1 ? k_bootstrap_dag<2, true, false> : k_bootstrap_dag<4, true, false>) : (x1 ? k_bootstrap_dag<2, false, false> : k_bootstrap_dag<4, false, false>);
-    const size_t lds = blind_rotate_lat_lds_bytes(P, !ap && !x1) + kDagMailboxWords * 4;   // + the worker's mailbox in front
+    const LatBuild v = lat_variant(P, wps <= 2);
+    const DagKernel k = lat_kernel(v, [](auto i) -> DagKernel {
+        constexpr LatBuild b = kLatBuilds[i];
+        return k_bootstrap_dag<LatVariant<b.wps, b.ap, true, b.fwd>>;
+    });
+    if (!k) return hipErrorInvalidValue;
+    const size_t lds = blind_rotate_lat_lds_bytes(P, v) + kDagMailboxWords * 4;   // + the worker's mailbox in front
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, s, d_P, d_params);
@@ -1712,18 +1709,17 @@ hipError_t launch_blind_rotate(const DevParams& P, const bce_gate_desc* d, u32 n
         using LatKernel = void (*)(DevParams, const bce_gate_desc*, u32, u32, u32*, u32*, u32*);
         const bool alone = (P.variant == 2) || (P.variant == 0 && grid.x <= P.cu_count);
         const bool x1 = alone && P.variant != 3;
-        const size_t lds_lat = blind_rotate_lat_lds_bytes(P, !ap && !x1);
+        const LatBuild v = lat_variant(P, x1);   // a folded key's rows l >= 1 hold ek_l - B^l ek_0 (see the kernel's FOLD note)
+        const size_t lds_lat = blind_rotate_lat_lds_bytes(P, v);
         // saturated launches run the tail of EvalBinGate in the kernel's epilogue (fused_tail); a launch that leaves
         // CUs to themselves keeps the separate tail kernels, which spread one bootstrap's row gather over many CUs
         const bool fuse = !x1 && tail_fused && P.fuse_tail && fused_tail_fits(P);
-        LatKernel lk;
-        if (P.fold) {   // key rows l >= 1 hold ek_l - B^l ek_0 (see the kernel's FOLD note)
-            if (ap) lk = x1 ? k_blind_rotate_lat<4, 2, true, false, true> : (fuse ? k_blind_rotate_lat<4, 4, true, true, true> : k_blind_rotate_lat<4, 4, true, false, true>);
-            else if (P.fwd_units && P.fwd_mfma && !x1) lk = fuse ? k_blind_rotate_lat<4, 4, false, true, true, true, true> : k_blind_rotate_lat<4, 4, false, false, true, true, true>;
-            else if (P.fwd_units && !x1) lk = fuse ? k_blind_rotate_lat<4, 4, false, true, true, true> : k_blind_rotate_lat<4, 4, false, false, true, true>;
-            else lk = x1 ? k_blind_rotate_lat<4, 2, false, false, true> : (fuse ? k_blind_rotate_lat<4, 4, false, true, true> : k_blind_rotate_lat<4, 4, false, false, true>);
-        } else if (ap) lk = x1 ? k_blind_rotate_lat<4, 2, true, false> : (fuse ? k_blind_rotate_lat<4, 4, true, true> : k_blind_rotate_lat<4, 4, true, false>);
-        else lk = x1 ? k_blind_rotate_lat<4, 2, false, false> : (fuse ? k_blind_rotate_lat<4, 4, false, true> : k_blind_rotate_lat<4, 4, false, false>);
+        const LatKernel lk = lat_kernel(v, [fuse](auto i) -> LatKernel {
+            constexpr LatBuild b = kLatBuilds[i];
+            if constexpr (b.wps >= 4) { if (fuse) return k_blind_rotate_lat<LatVariant<b.wps, b.ap, true, b.fwd>>; }
+            return k_blind_rotate_lat<LatVariant<b.wps, b.ap, false, b.fwd>>;
+        });
+        if (!lk) return hipErrorInvalidValue;
         if (kernel_id) *kernel_id = x1 ? BCE_BR_SPLIT_X1 : BCE_BR_SPLIT_X2;
         if (tail_fused) *tail_fused = fuse;
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_lat);

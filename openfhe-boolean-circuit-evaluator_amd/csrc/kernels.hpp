@@ -53,7 +53,7 @@ struct DevParams {
     u32 fold;              // 1: the key is stored with the lowest gadget digit folded in (rows l >= 1 hold ek_l - B^l ek_0) and
                            // the kernels multiply the digit-0 rows by the evaluation-form accumulator itself (BCE_FOLD=0 disables)
     u32 fwd_units;         // 1: the two-workgroups-per-CU build of the folded GINX split-transform kernel runs its six forward transforms
-                           // as 24 quarter units, three per wave (kernels.hip, ntt_forward_quarter3_low8; BCE_FWD_UNITS=0 keeps
+                           // as 24 quarter units, three per wave (kernels.hip, ntt_forward_quarter3<false>; BCE_FWD_UNITS=0 keeps
                            // the whole-row + half-row bodies)
     u32 factor_even;       // 1: factor = 2N / q is even, so every rotation exponent a' is even and I^a' = +-1: the quarter-unit build
                            // is compiled with the GINX MAC tail for that case (no parity selects, no products by I^+-a')
@@ -86,7 +86,7 @@ struct DevParams {
     // ---- matrix-pipe forward stages of the quarter units (at the end: the other kernels' argument layout is unchanged) ----
     u32 fwd_mfma;          // 1 (needs fwd_units): the stages on bits 9..4 of those transforms run on the matrix pipe as i8 products of
                            // the signed gadget digits with the limbs of one constant 64 x 64 matrix (kernels.hip,
-                           // ntt_forward_quarter3_mfma; tables and conditions: fwd_mfma.hpp; BCE_FWD_MFMA=0 keeps the quarter-unit body)
+                           // ntt_forward_quarter3<true>; tables and conditions: fwd_mfma.hpp; BCE_FWD_MFMA=0 keeps the quarter-unit body)
     u32 w14, w14s;         // 2^14 mod Q and its Shoup companion (recombination of the limb products)
     const u32* fwd_mfma_tab;   // [4 quarters][4 tiles][64 lanes][4 words]: A operands, or null
 };

@@ -1,4 +1,4 @@
-"""Forward stages on position bits 9..4 of the quarter units as i8 matrix products (kernels.hip, ntt_forward_quarter3_mfma;
+"""Forward stages on position bits 9..4 of the quarter units as i8 matrix products (kernels.hip, ntt_forward_quarter3<true>;
 default where the host conditions of csrc/fwd_mfma.hpp hold), against the quarter-unit body it replaces (BCE_FWD_MFMA=0, same
 binary) and against the oracle.
 
@@ -82,7 +82,7 @@ def test_multi_round_launch_every_stage_equals_quarter_units_and_oracle(bce, orc
 
 def test_small_dag_through_the_persistent_kernel(bce, orc, monkeypatch):
     """The dependency-driven kernel shares the bootstrap body: 120 dependent gates x 2 instances through bce_dag_run at two
-    workgroups per CU leave the same registers with either forward body (k_bootstrap_dag has the same template flag), and a gate deep in the DAG replays on the oracle."""
+    workgroups per CU leave the same registers with either forward body (k_bootstrap_dag takes the same LatVariant), and a gate deep in the DAG replays on the oracle."""
     o = orc.Oracle(orc.STD128_OPT, orc.GINX)
     o.keygen(SEED)
     rng = np.random.default_rng(12)

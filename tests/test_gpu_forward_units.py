@@ -1,5 +1,5 @@
 """Forward transforms of the folded N = 1024 GINX split-transform kernel as 24 quarter units, three per wave
-(kernels.hip, ntt_forward_quarter3_low8; default for the two-workgroups-per-CU build), against the whole-row + half-row
+(kernels.hip, ntt_forward_quarter3<false>; default for the two-workgroups-per-CU build), against the whole-row + half-row
 bodies it replaces (BCE_FWD_UNITS=0, same binary) and against the oracle.
 
 Bar: word for word.  Only the assignment of butterflies to lanes changes -- same ten stages, same lazy butterfly, same

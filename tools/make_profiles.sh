@@ -17,7 +17,7 @@ import json, sys
 raw = json.load(open(sys.argv[1]))
 br = next(k for k in raw if "blind_rotate" in k)
 tails = {k: v for k, v in raw.items() if "k_tail" in k}
-label = "k_blind_rotate_lat<4,4> (split transform, 2 workgroups/CU)" if br.startswith("void bce::k_blind_rotate_lat<4, 4, false") else br
+label = "k_blind_rotate_lat<4,4> (split transform, 2 workgroups/CU)" if br.startswith("void bce::k_blind_rotate_lat<bce::LatVariant<4, false") else br
 out = {"kernel": br, "bench_kernel": label,
        "workload": "AES-expanded.txt STD128_OPT GINX instances_per_gpu=32, bootstrap-depth schedule (bench.py default; inputs encrypted FRESH so that the kernel statistics hold the timed launches only), 1 step",
        "instances_per_gpu": 32, "relevel": True,
@@ -33,7 +33,8 @@ PY
 cd /tmp
 /opt/rocm/bin/hipcc -O3 -std=c++17 -ffp-contract=off --offload-arch=gfx950 -S --cuda-device-only -o /tmp/bce_kernels.s \
     "$R/openfhe-boolean-circuit-evaluator_amd/csrc/kernels.hip" 2>/dev/null
-python3 "$R/tools/valu_model.py" /tmp/bce_kernels.s k_blind_rotate_latILi4ELi4ELb0ELb1ELb1ELb1E "$P/${PRE}_valu_issue.jsonl" "$P/${PRE}_pmc_sq_lds.json" \
+# the kernel of the bench line: two workgroups per CU, GINX, tail fused, Fwd::QuartersMfma (= 3)
+python3 "$R/tools/valu_model.py" /tmp/bce_kernels.s k_blind_rotate_latINS_10LatVariantILi4ELb0ELb1ELNS_3FwdE3EEE "$P/${PRE}_valu_issue.jsonl" "$P/${PRE}_pmc_sq_lds.json" \
     "k_blind_rotate_lat<4,4> (split transform, 2 workgroups/CU)" 4 > "$P/${PRE}_valu_model.json"
 python3 - "$P/${PRE}_valu_model.json" <<'PY'
 import json, sys

@@ -1,5 +1,5 @@
 // Lane maps of v_mfma_i32_16x16x64_i8 on gfx950, checked with exact, asymmetric integer data (the forward transforms' matrix-
-// pipe body, kernels.hip ntt_forward_quarter3_mfma, relies on them):
+// pipe body, kernels.hip ntt_forward_quarter3<true>, relies on them):
 //   A  lane l holds row l & 15,    K slots 16 (l >> 4) + b in byte b = 0..15 of its four registers
 //   B  lane l holds column l & 15, the SAME K slots
 //   D  lane l holds column l & 15, rows 4 (l >> 4) + register

@@ -4,7 +4,7 @@
 Build the ISA with the phase marks in (-DBCE_PHASE_PROF: every BCE_PROF_MARK is one s_memtime), cut the step loop of the
 named kernel at the marks and count instructions per segment.  The step loop holds both forward-transform bodies (whole
 row, waves 0..3; half rows, waves 4..7): segments are reported with their label-delimited basic blocks so that the
-either/or blocks can be told apart.  The quarter-unit builds (…<4,4,false,FUSE,FOLD,true[,MFMA]>) have ONE forward body, the same on every wave.
+either/or blocks can be told apart.  The quarter-unit builds (LatVariant<4, false, FUSE, Fwd::Quarters / Fwd::QuartersMfma>) have ONE forward body, the same on every wave.
 
 usage: phase_itemize.py <kernels_prof.s> <mangled-kernel-substring>
 """
