@@ -376,7 +376,7 @@ int build_ctx(u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 baseG, u32 ba
                                          : (c->logN == 10 && c->dG == 4 && P.lazy && P.variant != 1);  // kernels.hip, split transform
         const char* fo = std::getenv("BCE_FOLD");
         P.fold = (exact && has_kernel && !(fo && fo[0] == '0')) ? 1 : 0;
-        P.fold_ninv = (BCE_KEY_NINV && P.fold && c->is64 && P.fp64) ? 1 : 0;
+        P.fold_ninv = (P.fold && c->is64 && P.fp64) ? 1 : 0;
         // forward transforms of the folded N = 1024 GINX kernel as quarter units (kernels.hip); that build is also compiled
         // with the MAC tail of an even factor, so an odd factor keeps the whole-row + half-row bodies and the general tail.
         // BCE_FWD_UNITS=0 keeps them everywhere (development / parity knob, same binary)

@@ -140,16 +140,7 @@ __device__ __forceinline__ void block_sync_lds() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-// exchange that stays inside one wave (split inverse transform, passes 0..3).  -DBCE_STEP_BARRIERS restores the
-// workgroup barriers of the round-1 schedule for A/B runs (tools/barrier_ab.sh).
-__device__ __forceinline__ void wave_sync();
-__device__ __forceinline__ void wave_local_sync() {
-#ifdef BCE_STEP_BARRIERS
-    block_sync_lds();
-#else
-    wave_sync();
-#endif
-}
+// exchange that stays inside one wave (one transform per wave; split inverse transform, passes 0..3)
 __device__ __forceinline__ void wave_sync() {
     // LDS operations of one wave execute in order; this only pins the compiler.
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1215,7 +1206,7 @@ __device__ __forceinline__ void split_inverse_rest(const SplitInv<REGTW>& S, con
     inv_pass4(x, fa, fb, fc, Q, mu32);
 #pragma unroll
     for (int r = 0; r < 4; ++r) xb[S.s1 + 4 * r] = x[r];
-    wave_local_sync();
+    wave_sync();
     at_pass(std::integral_constant<int, 2>{});
 #pragma unroll
     for (int r = 0; r < 4; ++r) x[r] = xb[S.l2 + 20 * r];
@@ -1223,7 +1214,7 @@ __device__ __forceinline__ void split_inverse_rest(const SplitInv<REGTW>& S, con
     inv_pass4(x, fa, fb, fc, Q, mu32);
 #pragma unroll
     for (int r = 0; r < 4; ++r) xa[S.s2 + 16 * r] = x[r];
-    wave_local_sync();
+    wave_sync();
     at_pass(std::integral_constant<int, 3>{});
 #pragma unroll
     for (int r = 0; r < 4; ++r) x[r] = xa[S.l3 + 80 * r];
@@ -1512,7 +1503,7 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
         // no barrier here: the next step's passes 1..3 touch only this wave's own words of xa / xb, and its first
         // cross-wave access (pass 4, then the digit rows) sits behind the barrier inside split_inverse_rest, which
         // every wave reaches only after its MAC reads of the digit rows
-        wave_local_sync();
+        wave_sync();
         BCE_PROF_MARK(5);
     }
     BCE_PROF_FLUSH();

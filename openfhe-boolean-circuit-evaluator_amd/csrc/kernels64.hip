@@ -10,6 +10,7 @@
 // (2 + 2*dG) padded polynomials of N = 2048 u64 words already take 139 KiB of the 160 KiB LDS.
 #include <hip/hip_runtime.h>
 
+#include <iterator>
 #include <utility>
 
 #include <type_traits>
@@ -56,13 +57,14 @@ __device__ __forceinline__ u64 reduce128(U128 a, u64 Q, u64 c64, u64 mu64) {
 }
 
 __device__ __forceinline__ u32 phys(u32 j) { return j + ((j >> 6) << 2); }
+constexpr u32 padded_words(u32 logn) { return (1u << logn) + ((1u << logn) >> 6) * 4; }   // of a polynomial: phys(N)
 
 template <int LOGN>
 struct Cfg {
     static constexpr int N = 1 << LOGN;
     static constexpr int LE = LOGN - 6;
     static constexpr int E = 1 << LE;
-    static constexpr int NP = N + (N >> 6) * 4;
+    static constexpr int NP = padded_words(LOGN);
     static constexpr int F2LO = (6 > LE) ? 6 - LE : 0;
     static_assert(LOGN >= 9 && LOGN <= 11, "supported ring sizes: 512, 1024, 2048");
 };
@@ -229,24 +231,41 @@ __device__ __forceinline__ u32 gate_const(u32 op, u32 q) {
     }
 }
 
-// NBUF_ / NPRE_: depth of the key-row software pipeline (items in flight / requested before the transforms);
-// the defaults are the deepest that compile without scratch at N = 2048 (GINX items carry two keys' rows)
-// NARROW: the R digit rows are 32-bit words (Q < 2^31: a digit + Q and every normalised transform value fit), the inverse
+// LDS of one workgroup of k_blind_rotate64, in 64-bit words: used by the kernel and by blind_rotate64_lds_bytes.
+// narrow: the R digit rows are 32-bit words (Q < 2^31: a digit + Q and every normalised transform value fit), the inverse
 // transforms get a scratch of their own -- what lets N = 2048 with FOUR gadget digits (STD256, STD256_OPT: 29-bit Q, base 2^8)
 // into the 160 KiB of LDS: 2 x 17 KiB accumulator + 8 x 8.5 KiB digit rows + 2 x 17 KiB scratch instead of 10 x 17 KiB.
-template <int LOGN, int DG, bool AP, u32 NBUF_ = (AP ? 3 : 2), u32 NPRE_ = (AP ? 2 : 1), bool NARROW = false>
+struct W64Lds {
+    u32 NP, R;
+    bool narrow;
+    constexpr W64Lds(u32 logn, u32 dg, bool narrow_) : NP(padded_words(logn)), R(2 * dg), narrow(narrow_) {}
+    static constexpr u32 acc = 0;                                                   // [2][NP] evaluation form, [0, Q)
+    constexpr u32 dct() const { return 2 * NP; }                                    // [R][NP] digit rows
+    // exchange rows of the two inverse transforms: the digit rows themselves, or (narrow) two 64-bit rows behind them
+    constexpr u32 inv_tmp() const { return narrow ? dct() + R * NP / 2 : dct(); }
+    constexpr u32 av() const { return narrow ? inv_tmp() + 2 * NP : dct() + R * NP; }   // u32 a[0..n), b
+    static constexpr u32 av_words(u32 n) { return (n + 1 + 3) & ~3u; }              // (32-bit words)
+    constexpr size_t bytes(u32 n) const { return av() * sizeof(u64) + av_words(n) * sizeof(u32); }
+};
+
+// One build per (LOGN, DG, AP).  NARROW (see W64Lds): four gadget digits on N >= 1024, the contexts blind_rotate64_narrow accepts.
+// NBUF / NPRE: depth of the key-row software pipeline (items in flight / requested before the transforms): the deepest that
+// compile without scratch at N = 2048 (GINX items carry two keys' rows), one item less in the narrow N = 2048 build.
+template <int LOGN, int DG, bool AP>
 __global__ __launch_bounds__(128 * DG) void k_blind_rotate64(DevParams P, const bce_gate_desc* __restrict__ descs, u32 n_desc,
                                                               u32 slot_stride, u64* __restrict__ acc_out, u32* /*dbg_lweN: no fused tail*/, u32* /*dbg_ks*/) {
     using C = Cfg<LOGN>;
     constexpr int N = C::N, NP = C::NP, E = C::E;
     constexpr u32 R = 2 * DG, T = 64 * R;
+    constexpr bool NARROW = DG == 4 && LOGN >= 10;
+    constexpr u32 NBUF = (NARROW && LOGN == 11) ? (AP ? 2 : 1) : (AP ? 3 : 2), NPRE = NBUF - 1;
+    constexpr W64Lds L(LOGN, DG, NARROW);
     extern __shared__ __align__(16) u64 smem64[];
     using DW = std::conditional_t<NARROW, u32, u64>;
-    u64* acc = smem64;            // [2][NP] EVALUATION domain, [0, Q)
-    DW* dct = reinterpret_cast<DW*>(acc + 2 * NP);      // [R][NP]
-    // exchange rows of the two inverse transforms: the digit rows themselves, or (narrow build) two 64-bit rows behind them
-    u64* inv_tmp = reinterpret_cast<u64*>(NARROW ? dct + R * NP : dct);
-    u32* av = NARROW ? reinterpret_cast<u32*>(inv_tmp + 2 * NP) : reinterpret_cast<u32*>(dct + R * NP);
+    u64* acc = smem64 + L.acc;
+    DW* dct = reinterpret_cast<DW*>(smem64 + L.dct());
+    u64* inv_tmp = smem64 + L.inv_tmp();
+    u32* av = reinterpret_cast<u32*>(smem64 + L.av());
     const ulonglong2* __restrict__ tw = P.tw64;
 
     const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -318,8 +337,6 @@ __global__ __launch_bounds__(128 * DG) void k_blind_rotate64(DevParams P, const 
         // when item k is done.
         constexpr u32 ITEMS = (2u * (N / 2) + T - 1) / T;       // per thread, last one guarded
         constexpr u32 ROWS = AP ? R : 2 * R;
-        constexpr u32 NBUF = NBUF_;   // items in flight
-        constexpr u32 NPRE = NPRE_;   // of which requested before the transforms
         // one resource per step: base = this step's RGSW key(s), bounds = their size
         const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<u64*>(bk), 0, (int)((AP ? 1 : 2) * rgsw * sizeof(u64)), 0x00020000);
@@ -515,15 +532,7 @@ using w64::phys;
 using w64::elem_j;
 using w64::wave_sync;
 using w64::block_sync_lds;
-// exchange of the split inverse transform that stays inside one wave; -DBCE_STEP_BARRIERS = the workgroup barriers of
-// the earlier schedule (A/B runs)
-#ifdef BCE_STEP_BARRIERS
-constexpr int INV_BARRIERS = 3;
-__device__ __forceinline__ void wave_local_sync() { block_sync_lds(); }
-#else
-constexpr int INV_BARRIERS = 1;
-__device__ __forceinline__ void wave_local_sync() { wave_sync(); }
-#endif
+constexpr int INV_BARRIERS = 1;   // workgroup barriers inside split_inverse11 (its other exchanges stay inside one wave)
 using w64::for_each_index;
 using w64::gate_const;
 
@@ -967,7 +976,7 @@ __device__ __forceinline__ void split_inverse11(const double* src, double* bufA,
 #pragma unroll
         for (int r = 0; r < 8; ++r) bufA[r * 257 + t] = x[r];          // e0
     }
-    wave_local_sync();
+    wave_sync();
     {   // pass 1: p = (g << 6) | (r << 3) | l,  g = t >> 3, l = t & 7; e0 address of p: (p & 7) * 257 + (p >> 3)
         const u32 g = t >> 3, l = t & 7u;
 #pragma unroll
@@ -980,7 +989,7 @@ __device__ __forceinline__ void split_inverse11(const double* src, double* bufA,
 #pragma unroll
         for (int r = 0; r < 8; ++r) bufB[r * 264 + t] = x[r];          // e1 (t = (g << 3) | l)
     }
-    wave_local_sync();
+    wave_sync();
     {   // pass 2: p = (h << 9) | (r << 6) | m,  h = t >> 6, m = t & 63; e1 address of p: p[5:3] * 264 + ((p >> 6) << 3 | p[2:0])
         const u32 h = t >> 6, m = t & 63u;
 #pragma unroll
@@ -1015,74 +1024,101 @@ __device__ __forceinline__ void split_inverse11(const double* src, double* bufA,
     }
 }
 
-// SPLIT (N = 2048 only): 512-thread workgroup, inverse transforms on all 8 waves (split_inverse11), forward
-// transforms on waves 0..R-1, 4 MAC items per thread.
-// W16 (with SPLIT): 1024-thread workgroup = 4 waves per SIMD on the one workgroup a CU's LDS holds.  The inverse
-// transforms stay on waves 0..7 (8 coefficients per thread is what keeps them at 4 passes); the forward phase runs as
-// 12 half-transforms on waves 0..11 and the MAC as 2 items per thread on all 16 waves, so that the LDS traffic of one
-// wave (twiddles + coefficients: ~6 k cycles of the phase, profiles/r02_phase_std192_ap.log) overlaps with the
-// arithmetic of three others instead of one.  128-register budget: key rows one (GINX) / two (AP) items deep.
-// key-row pipeline depth of the 16-wave build (development knobs, tools/w16_sweep.sh).  Measured on one MI355X, STD192,
-// 256 bootstraps per launch (profiles/r02_w16_sweep.log): 8 waves 28.1 ms (AP) / 17.0 ms (GINX); 16 waves with one item
-// in flight and nothing requested before the transforms 25.9 / 18.5 ms; every deeper pipeline spills 33..81 registers of
-// the 128 a 1024-thread workgroup leaves each thread and is slower than the 8-wave build.
-// BCE_W16_EARLY (16-wave AP build): both MAC items' key rows are requested BEFORE the forward phase, where the registers
-// are free -- by waves 8..15 at the top of the step (they have no share of the inverse transforms), by waves 0..7 once
-// their digits are written -- and held through the quarter-transforms (48 registers), so that the MAC phase finds them
-// landed instead of exposing the row latency twice per step.  (Requests in front of the inverse transforms, the
-// NPRE knobs below, put 24..48 live registers into the phase that needs all 128: 33..81 spills.)
-#ifndef BCE_W16_EARLY
-#define BCE_W16_EARLY 1
-#endif
-#ifndef BCE_W16_NBUF_AP
-#define BCE_W16_NBUF_AP 1
-#define BCE_W16_NPRE_AP 0
-#define BCE_W16_NBUF_GINX 1
-#define BCE_W16_NPRE_GINX 0
-#endif
-// FOLD (with SPLIT): the lowest gadget digit is never transformed -- the key arrives with rows l >= 1 replaced by
-// ek_l - B^l ek_0 and the MAC multiplies the digit-0 rows by the evaluation-form accumulator itself (see the FOLD note of
-// k_blind_rotate_lat in kernels.hip; SignedDigitDecompose is exact for these parameters, checked by the host).  Four
-// forward transforms per step instead of six = eight half-transforms, one per wave (8-wave build), or sixteen quarter-
-// transforms, one per wave (16-wave build).  The accumulator is double-buffered between `acc` and digit rows 0, 1; the inverse transform's exchange buffers
-// move to digit rows 2..5.
-// FUSE (16-wave build): the tail of EvalBinGate runs in this kernel's epilogue (fused_tail.hpp) -- the coefficient-form
-// accumulator goes to LDS as u64 words, all 1,024 threads extract, switch the modulus, gather the N dKS key-switching rows
-// (33.6 MB for STD192) and write the refreshed ciphertext to the pool; no tail kernels, no accumulator round trip through HBM.
-template <int LOGN, int DG, bool AP, bool SPLIT = false, bool W16 = false, bool FOLD = false, bool FUSE = false,
-          u32 NBUF_ = (W16 ? (AP ? BCE_W16_NBUF_AP : BCE_W16_NBUF_GINX) : (AP ? 3 : 2)),
-          u32 NPRE_ = (W16 ? (AP ? BCE_W16_NPRE_AP : BCE_W16_NPRE_GINX) : (AP ? 2 : 1)),
-          bool PERSIST = false, typename PT = DevParams>
+// The workgroup shape of a build, i.e. who runs the transforms of a step:
+enum class Body {
+    Wave,     // any N: T = 128 DG threads, one wave per transform (ntt_inverse_wave on waves 0, 1, ntt_forward_wave on every wave),
+              // twiddles from global memory
+    Split8,   // N = 2048 only: 512 threads, inverse transforms on all 8 waves (split_inverse11), forward transforms on waves
+              // 0..R-1, 4 MAC items per thread; the first 1024 twiddles mirrored in LDS
+    Split16,  // the same on 1,024 threads = 4 waves per SIMD on the one workgroup a CU's LDS holds.  The inverse transforms stay on
+              // waves 0..7 (8 coefficients per thread is what keeps them at 4 passes); the forward phase runs as 12 half-transforms
+              // on waves 0..11 and the MAC as 2 items per thread on all 16 waves, so that the LDS traffic of one wave (twiddles +
+              // coefficients: ~6 k cycles of the phase, profiles/r02_phase_std192_ap.log) overlaps with the arithmetic of three
+              // others instead of one.  128-register budget.
+};
+constexpr u32 wd_threads(Body b, u32 dg) { return b == Body::Split16 ? 1024 : b == Body::Split8 ? 512 : 128 * dg; }
+
+// One build of bootstrap64d; everything else follows from these six.
+// FOLD (split bodies): the lowest gadget digit is never transformed -- the key arrives with rows l >= 1 replaced by
+//   ek_l - B^l ek_0 and the MAC multiplies the digit-0 rows by the evaluation-form accumulator itself (see the FOLD note of
+//   lat_bootstrap in kernels.hip; SignedDigitDecompose is exact for these parameters, checked by the host).  Four forward
+//   transforms per step instead of six = eight half-transforms, one per wave (Split8), or sixteen quarter-transforms, one
+//   per wave (Split16).  The accumulator is double-buffered between `acc` and digit rows 0, 1.
+// FUSE (Split16): the tail of EvalBinGate runs in this kernel's epilogue (fused_tail.hpp) -- the coefficient-form
+//   accumulator goes to LDS as u64 words, all 1,024 threads extract, switch the modulus, gather the N dKS key-switching rows
+//   (33.6 MB for STD192) and write the refreshed ciphertext to the pool; no tail kernels, no accumulator round trip through HBM.
+template <int LOGN_, int DG_, bool AP_, Body BODY_ = Body::Wave, bool FOLD_ = false, bool FUSE_ = false>
+struct WdVariant {
+    static constexpr int LOGN = LOGN_, DG = DG_, N = 1 << LOGN;
+    static constexpr Body BODY = BODY_;
+    static constexpr bool AP = AP_, FOLD = FOLD_, FUSE = FUSE_;
+    static constexpr bool SPLIT = BODY_ != Body::Wave, W16 = BODY_ == Body::Split16;
+    static constexpr u32 R = 2 * DG, T = wd_threads(BODY_, DG);   // digit rows, threads
+    // W1: all N twiddles in the LDS mirror as plain doubles (see Tw) instead of the first 1024 (w, w / Q) pairs
+    static constexpr bool W1 = FOLD;
+    // KN: the evaluation-form accumulator lives scaled by N^-1 -- rows l >= 1 of the key carry the factor (DevParams::fold_ninv),
+    // rows 0, 1 multiply the (scaled) accumulator itself -- so the un-normalised inverse transform of a step returns the coefficients
+    static constexpr bool KN = FOLD;
+    // exchange buffers of the split inverse transform: digit rows that are dead until the digits are written (FOLD: rows 0, 1
+    // hold the other copy of the accumulator)
+    static constexpr int XA = FOLD ? 2 : 0, XB = FOLD ? 4 : 2;
+    // key rows: the software pipeline of the integer kernel.  A thread owns ITEMS MAC items of ROWS 16-byte loads each; NBUF
+    // items are in flight, NPRE of them requested before the transforms.  Wave / Split8: the deepest that compiles without
+    // scratch.  Split16 leaves a thread 128 registers: one item in flight and nothing requested before the transforms
+    // (8 waves 28.1 ms (AP) / 17.0 ms (GINX) per 256 STD192 bootstraps, 16 waves 25.9 / 18.5 ms; every deeper pipeline spills
+    // 33..81 registers and is slower than Split8: profiles/r02_w16_sweep.log) ...
+    static constexpr u32 ITEMS = (2u * (N / 2) + T - 1) / T, ROWS = AP ? R : 2 * R;
+    // ... except EARLY (AP with the folded key; the plain-key build has six rows to transform: no room): both MAC items' key
+    // rows are requested BEFORE the forward phase, where the registers are free -- by waves 8..15 at the top of the step (they
+    // have no share of the inverse transforms), by waves 0..7 once their digits are written -- and held through the quarter-
+    // transforms (48 registers), so that the MAC phase finds them landed instead of exposing the row latency twice per step
+    // (profiles/r03_cfg5_early_request_ab.log).
+    static constexpr bool EARLY = W16 && AP && FOLD;
+    static constexpr u32 NBUF = EARLY ? ITEMS : W16 ? 1 : AP ? 3 : 2, NPRE = EARLY ? ITEMS : W16 ? 0 : AP ? 2 : 1;
+    static_assert(!SPLIT || (LOGN == 11 && R <= 8 && R >= 4), "split inverse transform: N = 2048");
+    static_assert(!W16 || R == 6, "16-wave body: three gadget digits");
+    static_assert(!FOLD || (SPLIT && R == 6), "folded gadget digit: N = 2048, three gadget digits");
+    static_assert(!FUSE || W16, "fused tail: 16-wave body");
+};
+
+// LDS of one workgroup of bootstrap64d, in doubles: used by the kernels, their launchers, blind_rotate64_lds_bytes and
+// fused_tail64_fits
+struct WdLds {
+    u32 NP, R;
+    bool mirror;
+    constexpr WdLds(u32 logn, u32 dg, Body b) : NP(w64::padded_words(logn)), R(2 * dg), mirror(b != Body::Wave) {}
+    static constexpr u32 mbox = kDagMailboxWords / 2;         // k_bootstrap_dag64: the worker's mailbox sits in front of all this
+    static constexpr u32 acc = 0;                             // [2][NP] evaluation form, |value| <= 0.6 Q
+    constexpr u32 dct() const { return 2 * NP; }              // [R][NP] digit rows
+    constexpr u32 av() const { return dct() + R * NP; }       // u32 a[0..n), b
+    static constexpr u32 av_words(u32 n) { return w64::W64Lds::av_words(n); }
+    // behind av (split bodies): LDS mirror of the twiddles, 16 of the 20 KiB left next to the polynomials
+    constexpr size_t bytes(u32 n) const { return av() * sizeof(double) + av_words(n) * sizeof(u32) + (mirror ? 1024 * sizeof(double2) : 0); }
+    constexpr size_t tail_bytes() const { return (size_t)R * NP * sizeof(double); }   // the digit rows: dead when the fused tail runs
+};
+
+// V: a WdVariant; PERSIST (dataflow kernel, k_bootstrap_dag64): called from a loop -- the thread index is opaque per call so
+// that the compiler cannot split the caller's loop on it, and nothing leaves through acc_out
+template <class V, bool PERSIST = false, typename PT = DevParams>
 __device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g, const u32 soff, const u32 boot, double* smemd,
                                              u64* __restrict__ acc_out, u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks) {
     // one gate bootstrap by one workgroup; `boot` = index of the bootstrap in the launch (acc_out / dbg rows).
-    // PERSIST (dataflow kernel, k_bootstrap_dag64): called from a loop -- the thread index is opaque per call so that the
-    // compiler cannot split the caller's loop on it, and nothing leaves through acc_out
-    static_assert(!FUSE || (W16 && SPLIT), "fused tail: 16-wave build");
+    constexpr int LOGN = V::LOGN, DG = V::DG;
+    constexpr bool AP = V::AP, SPLIT = V::SPLIT, W16 = V::W16, FOLD = V::FOLD, FUSE = V::FUSE, W1 = V::W1, KN = V::KN;
     static_assert(!PERSIST || FUSE, "persistent callers rely on the fused tail");
     using C = Cfg<LOGN>;
     constexpr int N = C::N, NP = C::NP, E = C::E;
-    constexpr u32 R = 2 * DG, T = W16 ? 1024 : (SPLIT ? 512 : 64 * R);
-    static_assert(!SPLIT || (LOGN == 11 && R <= 8 && R >= 4), "split inverse transform: N = 2048");
-    static_assert(!W16 || (SPLIT && R == 6), "16-wave variant: N = 2048, three gadget digits");
-    static_assert(!FOLD || (SPLIT && R == 6), "folded gadget digit: N = 2048, three gadget digits");
+    constexpr u32 R = V::R, T = V::T;
+    constexpr WdLds L(LOGN, DG, V::BODY);
     u32 tid_o = threadIdx.x;
     if constexpr (PERSIST) asm volatile("" : "+v"(tid_o));
-    double* acc = smemd;          // [2][NP] evaluation form, |value| <= 0.6 Q
-    double* dct = acc + 2 * NP;   // [R][NP]
-    u32* av = reinterpret_cast<u32*>(dct + R * NP);
+    double *acc = smemd + L.acc, *dct = smemd + L.dct();
+    u32* av = reinterpret_cast<u32*>(smemd + L.av());
     const double2* __restrict__ tw = P.tw64d;
-    // LDS mirror of the first 1024 twiddle entries (8-wave kernel only: 16 KiB of the 20 KiB left next to the polynomials)
-    double2* twl = reinterpret_cast<double2*>(av + ((P.n + 1 + 3) & ~3u));
-    // W1 (folded key): all N twiddles in those 16 KiB as plain doubles (see Tw); -DBCE_TWQ keeps the (w, w / Q) pairs (A/B runs)
-#ifdef BCE_TWQ
-    constexpr bool W1 = false;
-#else
-    constexpr bool W1 = FOLD && SPLIT;
-#endif
+    double2* twl = reinterpret_cast<double2*>(av + L.av_words(P.n));   // the twiddle mirror, as (w, w / Q) pairs ...
     typedef TwSel<W1> TS;
     typedef typename TS::T TV;
-    double* twl1 = reinterpret_cast<double*>(twl);
+    double* twl1 = reinterpret_cast<double*>(twl);                     // ... or (W1) as plain doubles
     if constexpr (W1) {
         for (u32 i = tid_o; i < (u32)N; i += T) twl1[i] = tw[i].x;
     } else if constexpr (SPLIT) {
@@ -1131,9 +1167,6 @@ __device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g,
     if (wave == 0) ntt_forward_wave<LOGN>(acc + NP, Tw{tw, nullptr}, lane, Q);
     __syncthreads();
     const double2 ninv = make_double2(P.Ninvd, P.Ninvd_q);
-    // KN (folded key): the evaluation-form accumulator lives scaled by N^-1 -- rows l >= 1 of the key carry the factor, rows 0, 1
-    // multiply the (scaled) accumulator itself -- so the un-normalised inverse transform of a step returns the coefficients
-    constexpr bool KN = FOLD && (BCE_KEY_NINV != 0);
     for (u32 j = tid; j < (u32)N; j += T)
         acc[NP + phys(j)] = KN ? modmul_q(acc[NP + phys(j)], ninv.x, ninv.y, Q) : modred(acc[NP + phys(j)], invQ, Q);
     __syncthreads();
@@ -1152,8 +1185,7 @@ __device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g,
     // FOLD: the step reads the evaluation-form accumulator at `cur` (also as MAC rows 0, 1) and writes the new one to `nxt`
     double* cur = acc;
     double* nxt = FOLD ? dct : acc;
-    // exchange buffers of the split inverse transform: digit rows that are dead until the digits are written
-    constexpr int XA = FOLD ? 2 : 0, XB = FOLD ? 4 : 2;
+    constexpr int XA = V::XA, XB = V::XB;
     BCE_PROF_INIT();
     for (u32 step = 0; step < nsteps; ++step) {
         u32 ap = 0;
@@ -1171,10 +1203,8 @@ __device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g,
             bk = bsk + (((size_t)i * P.baseR + a0) * P.dR + k) * rgsw;
         }
         // key rows: same software pipeline as the integer kernel
-        constexpr u32 ITEMS = (2u * (N / 2) + T - 1) / T;
-        constexpr u32 ROWS = AP ? R : 2 * R;
-        constexpr bool EARLY = W16 && AP && FOLD && (BCE_W16_EARLY != 0);   // (the plain-key build has six rows to transform: no room)
-        constexpr u32 NBUF = EARLY ? ITEMS : NBUF_, NPRE = EARLY ? ITEMS : NPRE_;
+        constexpr u32 ITEMS = V::ITEMS, ROWS = V::ROWS, NBUF = V::NBUF, NPRE = V::NPRE;
+        constexpr bool EARLY = V::EARLY;
         const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<double*>(bk), 0, (int)((AP ? 1 : 2) * rgsw * sizeof(double)), 0x00020000);
         double2 kb[NBUF][ROWS];
@@ -1405,34 +1435,70 @@ __device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g,
     }
 }
 
-template <int LOGN, int DG, bool AP, bool SPLIT = false, bool W16 = false, bool FOLD = false, bool FUSE = false>
-__global__ __launch_bounds__(W16 ? 1024 : (SPLIT ? 512 : 128 * DG)) void k_blind_rotate64d(DevParams P, const bce_gate_desc* __restrict__ descs, u32 n_desc,
-                                                               u32 slot_stride, u64* __restrict__ acc_out,
-                                                               u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks) {
+template <class V>
+__global__ __launch_bounds__(V::T) void k_blind_rotate64d(DevParams P, const bce_gate_desc* __restrict__ descs, u32 n_desc,
+                                                          u32 slot_stride, u64* __restrict__ acc_out,
+                                                          u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks) {
     extern __shared__ __align__(16) double smemd[];
-    bootstrap64d<LOGN, DG, AP, SPLIT, W16, FOLD, FUSE>(P, descs[blockIdx.x % n_desc], (blockIdx.x / n_desc) * slot_stride, blockIdx.x, smemd,
-                                                       acc_out, dbg_lweN, dbg_ks);
+    bootstrap64d<V>(P, descs[blockIdx.x % n_desc], (blockIdx.x / n_desc) * slot_stride, blockIdx.x, smemd, acc_out, dbg_lweN, dbg_ks);
 }
 
 // Dataflow evaluation on the config-5 kernel (dag_sched.hpp): one persistent 1,024-thread workgroup per CU (the LDS holds
 // one), AP, folded key, fused tail.  No XCD start gate is needed for key locality here -- an AP step reads one RGSW
 // ciphertext chosen by the ciphertext's own digit, so workgroups share few key rows even in lock-step.
-__global__ __launch_bounds__(1024) void k_bootstrap_dag64(const DevParams* Pp, const DagParams* Dp) {
+template <class V>
+__global__ __launch_bounds__(V::T) void k_bootstrap_dag64(const DevParams* Pp, const DagParams* Dp) {
     extern __shared__ __align__(16) double smemd[];
     u32* mbox = reinterpret_cast<u32*>(smemd);
     dag_worker(Dp, mbox, [&](ConstDagParams& D, u32 t, u32 k) {
-        bootstrap64d<11, 3, true, true, true, true, true, BCE_W16_NBUF_AP, BCE_W16_NPRE_AP, true>(
-            *as_constant<ConstDevParams>(Pp), D.tasks[t], D.slot_base + k * D.slot_stride, 0, smemd + kDagMailboxWords / 2, nullptr, nullptr, nullptr);
+        bootstrap64d<V, true>(*as_constant<ConstDevParams>(Pp), D.tasks[t], D.slot_base + k * D.slot_stride, 0, smemd + WdLds::mbox,
+                              nullptr, nullptr, nullptr);
     });
 }
 
-// LDS the fused tail needs inside the digit rows of the 16-wave N = 2048 kernel (T = 1024 threads)
+// LDS the fused tail needs inside the digit rows of the Split16 kernel
 bool fused_tail64_fits(const DevParams& P) {
-    const size_t N = P.N, NP = N + (N >> 6) * 4, R = 2 * P.dG, T = 1024;
+    const size_t N = P.N, T = wd_threads(Body::Split16, P.dG);
     const size_t VW = P.ksk_u16 ? 8 : 4, G = (P.n + VW) / VW, Gv = G < T ? G : T, RW = (Gv + 63) / 64, SL = (T / 64) / RW;
     const size_t need = ((N * P.dKS + 3) & ~(size_t)3) * 4 + SL * Gv * VW * 8;
-    return P.logN == 11 && (size_t)P.n + 1 <= T * VW && RW <= T / 64 && SL >= 1 && need <= R * NP * 8;
+    return P.logN == 11 && (size_t)P.n + 1 <= T * VW && RW <= T / 64 && SL >= 1 && need <= WdLds(P.logN, P.dG, Body::Split16).tail_bytes();
 }
+
+// ---- which build a launch runs ---------------------------------------------------------------------------------------
+// The builds that exist.  A new one is a line here (and, for a new shape, an enumerator of Body and a line in wd_variant()).
+struct WdBuild { u32 logn, dg; bool ap; Body body; bool fold, fuse; };
+constexpr bool operator==(const WdBuild& a, const WdBuild& b) {
+    return a.logn == b.logn && a.dg == b.dg && a.ap == b.ap && a.body == b.body && a.fold == b.fold && a.fuse == b.fuse;
+}
+constexpr WdBuild kWdBuilds[] = {
+    {9, 3, false, Body::Wave, false, false},     {9, 3, true, Body::Wave, false, false},
+    {10, 3, false, Body::Wave, false, false},    {10, 3, true, Body::Wave, false, false},
+    {9, 4, false, Body::Wave, false, false},     {9, 4, true, Body::Wave, false, false},
+    {11, 3, false, Body::Split8, false, false},  {11, 3, true, Body::Split8, false, false},
+    {11, 3, false, Body::Split8, true, false},   {11, 3, true, Body::Split8, true, false},
+    {11, 3, false, Body::Split16, false, false}, {11, 3, true, Body::Split16, false, false},
+    {11, 3, false, Body::Split16, true, false},  {11, 3, true, Body::Split16, true, false},
+    {11, 3, true, Body::Split16, true, true},
+};
+// The build for an fp64 context; want_fuse: the caller can do without the separate tail kernels.  N = 2048 with three gadget
+// digits has the split bodies: AP (BASELINE config 5) the 16-wave one (-8 % per launch); GINX keeps the 8-wave one, whose
+// two-key MAC items do not fit the 128-register budget (16 waves: +9 %).  BCE_VARIANT=2 / 3 force 8 / 16 waves.  The AP build
+// with the folded key carries the tail in its epilogue.  A combination the table does not have (a folded key on another
+// shape, another ring size) has no kernel.
+WdBuild wd_variant(const DevParams& P, bool want_fuse) {
+    const bool ap = P.method_ap != 0, fold = P.fold != 0;
+    const Body body = !(P.logN == 11 && P.dG == 3) ? Body::Wave : (P.variant == 3 || (P.variant != 2 && ap)) ? Body::Split16 : Body::Split8;
+    const bool fuse = want_fuse && body == Body::Split16 && ap && fold && P.fuse_tail && fused_tail64_fits(P);
+    return {P.logN, P.dG, ap, body, fold, fuse};
+}
+// of(integral_constant<size_t, I>) for the entry I of kWdBuilds that equals v: the kernel pointer; null if there is none
+template <size_t I = 0, class F>
+auto wd_kernel(const WdBuild& v, F of) -> decltype(of(std::integral_constant<size_t, 0>{})) {
+    if constexpr (I == std::size(kWdBuilds)) return nullptr;
+    else return kWdBuilds[I] == v ? of(std::integral_constant<size_t, I>{}) : wd_kernel<I + 1>(v, of);
+}
+template <size_t I>
+using WdTableVariant = WdVariant<kWdBuilds[I].logn, kWdBuilds[I].dg, kWdBuilds[I].ap, kWdBuilds[I].body, kWdBuilds[I].fold, kWdBuilds[I].fuse>;
 
 // key words u64 <-> double in place (exact: Q < 2^39)
 __global__ void k_words_u64_f64(u64* __restrict__ w, size_t count, int to_double) {
@@ -1461,80 +1527,63 @@ bool blind_rotate64_narrow(const DevParams& P) {
     return P.is64 && !P.fp64 && P.dG == 4 && P.logN >= 10 && P.Q64 < (1ull << 31);
 }
 
+namespace {
+using BrKernel64 = void (*)(DevParams, const bce_gate_desc*, u32, u32, u64*, u32*, u32*);
+template <int LOGN, int DG>
+BrKernel64 pick_br64(bool ap) { return ap ? w64::k_blind_rotate64<LOGN, DG, true> : w64::k_blind_rotate64<LOGN, DG, false>; }
+// the integer kernel for a context, or null: three gadget digits, four on N = 512, four on N >= 1024 for the narrow class
+// (STD256 / STD256_OPT and their N = 1024 siblings); no build reads a folded key
+BrKernel64 blind_rotate64_kernel(const DevParams& P) {
+    const bool ap = P.method_ap != 0;
+    if (P.fold) return nullptr;
+    if (P.dG == 3) return P.logN == 9 ? pick_br64<9, 3>(ap) : P.logN == 10 ? pick_br64<10, 3>(ap) : P.logN == 11 ? pick_br64<11, 3>(ap) : nullptr;
+    if (P.dG == 4 && P.logN == 9) return pick_br64<9, 4>(ap);
+    if (blind_rotate64_narrow(P)) return P.logN == 11 ? pick_br64<11, 4>(ap) : pick_br64<10, 4>(ap);
+    return nullptr;
+}
+}  // namespace
+
 size_t blind_rotate64_lds_bytes(const DevParams& P) {
-    const size_t N = P.N, NP = N + (N >> 6) * 4, R = 2 * P.dG;
-    if (blind_rotate64_narrow(P)) return 2 * NP * sizeof(u64) + R * NP * sizeof(u32) + 2 * NP * sizeof(u64) + ((P.n + 1 + 3) & ~3u) * sizeof(u32);
-    // the 8-wave double-precision kernel (N = 2048, 3 gadget digits) also mirrors the first 1024 twiddle entries
-    const size_t mirror = (P.fp64 && P.logN == 11 && P.dG == 3) ? 1024 * sizeof(double2) : 0;
-    return (2 + R) * NP * sizeof(u64) + ((P.n + 1 + 3) & ~3u) * sizeof(u32) + mirror;
+    if (P.fp64) return wd::WdLds(P.logN, P.dG, wd::wd_variant(P, false).body).bytes(P.n);
+    return w64::W64Lds(P.logN, P.dG, blind_rotate64_narrow(P)).bytes(P.n);
 }
 
-bool dag64_kernel_available(const DevParams& P) {
-    // what launch_blind_rotate64 would run with the tail fused: AP, 16 waves, folded key
-    return P.is64 && P.fp64 && P.logN == 11 && P.dG == 3 && P.method_ap && P.fold && P.fuse_tail && P.variant != 2 && wd::fused_tail64_fits(P);
-}
+bool dag64_kernel_available(const DevParams& P) { return P.is64 && P.fp64 && wd::wd_variant(P, true).fuse; }
 
 hipError_t launch_bootstrap_dag64(const DevParams& P, const DevParams* d_P, const DagParams* d_params, u32 grid, hipStream_t s) {
     if (!dag64_kernel_available(P)) return hipErrorInvalidValue;
-    const size_t lds = blind_rotate64_lds_bytes(P) + kDagMailboxWords * 4;   // + the worker's mailbox in front
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wd::k_bootstrap_dag64), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    using DagKernel = void (*)(const DevParams*, const DagParams*);
+    const wd::WdBuild v = wd::wd_variant(P, true);
+    const DagKernel k = wd::wd_kernel(v, [](auto i) -> DagKernel {
+        if constexpr (wd::kWdBuilds[i].fuse) return wd::k_bootstrap_dag64<wd::WdTableVariant<i>>;
+        else return nullptr;
+    });
+    if (!k) return hipErrorInvalidValue;
+    const size_t lds = wd::WdLds::mbox * sizeof(double) + blind_rotate64_lds_bytes(P);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wd::k_bootstrap_dag64, dim3(grid), dim3(1024), lds, s, d_P, d_params);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(wd::wd_threads(v.body, v.dg)), lds, s, d_P, d_params);
     return hipGetLastError();
 }
 
 hipError_t launch_blind_rotate64(const DevParams& P, const bce_gate_desc* d, u32 n_desc, u32 instances, u32 slot_stride,
                                  u64* acc_out, hipStream_t s, u32* dbg_lweN, u32* dbg_ks, bool* tail_fused, LaunchEvents ev) {
-    using K = void (*)(DevParams, const bce_gate_desc*, u32, u32, u64*, u32*, u32*);
-    if (tail_fused) *tail_fused = false;
-    const bool ap = P.method_ap != 0;
+    BrKernel64 kern = nullptr;
     u32 threads = 128 * P.dG;
-    K kern = nullptr;
-    if (P.fp64 && P.dG == 3) {
-        switch (P.logN) {
-            case 9: kern = ap ? wd::k_blind_rotate64d<9, 3, true> : wd::k_blind_rotate64d<9, 3, false>; break;
-            case 10: kern = ap ? wd::k_blind_rotate64d<10, 3, true> : wd::k_blind_rotate64d<10, 3, false>; break;
-            case 11: {
-                // AP (BASELINE config 5): the 16-wave build (-8 % per launch); GINX keeps the 8-wave build, whose two-key MAC
-                // items do not fit the 128-register budget (16 waves: +9 %).  BCE_VARIANT=2 / 3 force 8 / 16 waves.
-                const bool w16 = P.variant == 3 || (P.variant != 2 && ap);
-                if (w16) {
-                    // the AP build with the folded key (BASELINE config 5) carries the tail in its epilogue
-                    const bool fuse = ap && P.fold && tail_fused && P.fuse_tail && wd::fused_tail64_fits(P);
-                    if (fuse) { kern = wd::k_blind_rotate64d<11, 3, true, true, true, true, true>; *tail_fused = true; }
-                    else if (P.fold) kern = ap ? wd::k_blind_rotate64d<11, 3, true, true, true, true> : wd::k_blind_rotate64d<11, 3, false, true, true, true>;
-                    else kern = ap ? wd::k_blind_rotate64d<11, 3, true, true, true> : wd::k_blind_rotate64d<11, 3, false, true, true>;
-                    threads = 1024;
-                } else {
-                    if (P.fold) kern = ap ? wd::k_blind_rotate64d<11, 3, true, true, false, true> : wd::k_blind_rotate64d<11, 3, false, true, false, true>;
-                    else kern = ap ? wd::k_blind_rotate64d<11, 3, true, true> : wd::k_blind_rotate64d<11, 3, false, true>;
-                    threads = 512;
-                }
-                break;
-            }
-            default: break;
-        }
-    } else if (P.fp64 && P.dG == 4 && P.logN == 9) {
-        kern = ap ? wd::k_blind_rotate64d<9, 4, true> : wd::k_blind_rotate64d<9, 4, false>;
-    } else if (P.dG == 3) {
-        switch (P.logN) {
-            case 9: kern = ap ? w64::k_blind_rotate64<9, 3, true> : w64::k_blind_rotate64<9, 3, false>; break;
-            case 10: kern = ap ? w64::k_blind_rotate64<10, 3, true> : w64::k_blind_rotate64<10, 3, false>; break;
-            case 11: kern = ap ? w64::k_blind_rotate64<11, 3, true> : w64::k_blind_rotate64<11, 3, false>; break;
-            default: break;
-        }
-    } else if (P.dG == 4 && P.logN == 9) {
-        kern = ap ? w64::k_blind_rotate64<9, 4, true> : w64::k_blind_rotate64<9, 4, false>;
-    } else if (blind_rotate64_narrow(P)) {
-        // STD256 / STD256_OPT (N = 2048) and their N = 1024 siblings: 32-bit digit rows
-        if (P.logN == 11) kern = ap ? w64::k_blind_rotate64<11, 4, true, 2, 1, true> : w64::k_blind_rotate64<11, 4, false, 1, 0, true>;
-        else kern = ap ? w64::k_blind_rotate64<10, 4, true, 3, 2, true> : w64::k_blind_rotate64<10, 4, false, 2, 1, true>;
+    bool fused = false;
+    if (P.fp64) {
+        const wd::WdBuild v = wd::wd_variant(P, tail_fused != nullptr);
+        kern = wd::wd_kernel(v, [](auto i) -> BrKernel64 { return wd::k_blind_rotate64d<wd::WdTableVariant<i>>; });
+        threads = wd::wd_threads(v.body, v.dg);
+        fused = v.fuse;
+    } else {
+        kern = blind_rotate64_kernel(P);
     }
-    if (!kern || (P.fold && !(P.fp64 && P.dG == 3 && P.logN == 11))) return hipErrorInvalidValue;  // folded key: N = 2048 fp64 kernels only
+    if (tail_fused) *tail_fused = fused;
+    if (!kern) return hipErrorInvalidValue;
     const size_t lds = blind_rotate64_lds_bytes(P);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    const bool fused = tail_fused && *tail_fused;
     if (ev.start || ev.stop)
         return launch_with_events(kern, dim3(n_desc * instances), dim3(threads), lds, s, ev, P, d, n_desc, slot_stride, acc_out,
                                   fused ? dbg_lweN : nullptr, fused ? dbg_ks : nullptr);

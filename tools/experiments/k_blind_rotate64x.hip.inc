@@ -5,7 +5,7 @@
 // shader cycles per step than the 8-wave kernel (27.6 k vs 33.3 k: inverse passes + digits 11.3 k -> 6.8 k, forward
 // phase 13.2 k -> 7.5 k once the digit rows were re-padded and the twiddle blocks m >= 128 transposed), but only 5 %
 // less TIME (26.7 ms vs 28.1 ms per 256-bootstrap launch): the clock the chip holds under the denser fp64 stream fell
-// from 2.35 to 2.07 GHz.  The mixed 16-wave build that ships (k_blind_rotate64d<..., W16>: 25.9 ms) is simpler and 3 %
+// from 2.35 to 2.07 GHz.  The mixed 16-wave build that ships (k_blind_rotate64d, Body::Split16: 25.9 ms) is simpler and 3 %
 // faster.  Touching the step's key rows early with dword loads to warm L2 made it 17 % slower (31.2 ms).
 // =======================================================================================
 // k_blind_rotate64x -- N = 2048, three gadget digits, AP/DM accumulator (BASELINE config 5): every phase on 16 waves
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(1024) void k_blind_rotate64x(DevParams P, const bce
         request(std::integral_constant<u32, 0>{}, std::integral_constant<u32, PRE>{});
 #ifndef BCE_X_NOTOUCH
         // The 128-register budget has no room for the step's 48 registers of key rows across the transforms (spills, see
-        // tools/w16_sweep.sh), so the rows are only TOUCHED here: one dword per row and thread (a wave covers the 16 cache
+        // profiles/r02_w16_sweep.log), so the rows are only TOUCHED here: one dword per row and thread (a wave covers the 16 cache
         // lines of its row segment), kept alive until the MAC, where the real 16-byte loads then hit L2 instead of HBM.
         u32 touch[R];
 #pragma unroll

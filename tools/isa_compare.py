@@ -5,6 +5,9 @@
     hipcc <the flags of build.py> --cuda-device-only -S csrc/kernels.hip -o new.s     (this tree)
     python tools/isa_compare.py old.s new.s > profiles/<name>_isa_compare.txt
 
+Used on both kernel files, kernels.hip and kernels64.hip, each plain and with -DBCE_PHASE_PROF (the phase marks are device
+code too): profiles/lat_variant_isa_compare.txt, profiles/wd_variant_isa_compare.txt.
+
 A kernel's body is the text from its label to .Lfunc_end without comments, directives and blank lines, with the
 function number taken out of the local labels (.LBB<n>_ -> .LBB_).  Kernels are paired by the hash of the body, not by
 name, so renamed instantiations pair up; the table has old name, new name, hash, and VGPRs / SGPRs / spilled VGPRs /
