@@ -68,7 +68,8 @@ enum bce_br_kernel {
     BCE_BR_WAVE_PER_TRANSFORM = 0, /* k_blind_rotate: one wave per (inverse) transform, up to 3 workgroups / CU */
     BCE_BR_SPLIT_X1 = 1,           /* k_blind_rotate_lat<LatVariant<2, ...>>: split inverse transform, launches of <= #CU workgroups */
     BCE_BR_SPLIT_X2 = 2,           /* k_blind_rotate_lat<LatVariant<4, ...>>: same, register budget for two workgroups per CU */
-    BCE_BR_WORD64 = 3,             /* k_blind_rotate64: ring modulus >= 2^28 */
+    BCE_BR_WORD64 = 3,             /* ring modulus >= 2^28: the integer 64-bit and fp64 families of kernel_class() (csrc/kernels.hpp),
+                                      reported by launch_blind_rotate like the other three */
     BCE_BR_DAG = 4,                /* k_bootstrap_dag: one persistent launch per bce_dag_run (tail fused) */
     BCE_BR_GRAPH = 5,              /* bce_plan_run: the launches of a whole step schedule replayed as one hipGraph (timed as one) */
     BCE_BR_KERNELS = 6

@@ -170,27 +170,26 @@ struct bce_ctx {
 
 namespace {
 
-int build_ctx(u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 baseG, u32 baseR, int method, int device,
-              bce_ctx** out) {
-    if (!out) return BCE_ERR_ARG;
-    *out = nullptr;
-    if (method != BCE_AP && method != BCE_GINX) { g_create_error = "bad method (expect AP=1 or GINX=2)"; return BCE_ERR_ARG; }
-    if (N < 512 || N > 2048 || (N & (N - 1))) { g_create_error = "ring dimension N must be 512, 1024 or 2048"; return BCE_ERR_UNSUPPORTED; }
-    if ((q & (q - 1)) || q > 2 * (u64)N || q < 8) { g_create_error = "LWE modulus q must be a power of two dividing 2N"; return BCE_ERR_ARG; }
-    if (!is_prime_u64(Q) || (Q - 1) % (2ull * N)) { g_create_error = "Q must be a prime = 1 mod 2N"; return BCE_ERR_ARG; }
-    if (Q >= (1ull << 40)) { g_create_error = "ring modulus Q must be below 2^40"; return BCE_ERR_UNSUPPORTED; }
-    if (baseG & (baseG - 1)) { g_create_error = "gadget base must be a power of two"; return BCE_ERR_ARG; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        g_create_error = "no HIP device visible: the engine has no CPU fallback";
-        return BCE_ERR_NO_DEVICE;
-    }
-    if (device < 0 || device >= ndev) { g_create_error = "bad device ordinal"; return BCE_ERR_ARG; }
+// development / parity knobs that default to on: NAME=0 switches the feature off
+bool env_off(const char* name) {
+    const char* e = std::getenv(name);
+    return e && e[0] == '0';
+}
 
-    // partially built contexts are released through bce_ctx_destroy (frees whatever was allocated)
-    struct CtxDeleter { void operator()(bce_ctx* p) const { bce_ctx_destroy(p); } };
-    std::unique_ptr<bce_ctx, CtxDeleter> c(new bce_ctx);
-    { std::lock_guard<std::mutex> lk(g_live_mu); g_live.insert(c.get()); }
+// What derive_ctx builds on the host for upload_ctx to put on the device
+struct HostTables {
+    std::vector<uint2> twf;         // [N] (psi^brv(i), Shoup companion) in the device layout of kernels.hip (tw_pos)
+    std::vector<u32> psi, psi_r2;   // [N] psi^e in natural exponent order, and psi^e R^2 (R = 2^32)
+    std::vector<ulonglong2> tw64;   // 64-bit path: [N] (psi^brv(i), floor(. 2^64 / Q)) ...
+    std::vector<double2> tw64d;     // ... and (psi^brv(i), psi^brv(i) / Q) for the double-precision formulation
+    FwdMfmaTables fwd;              // A operands of the matrix-pipe forward stages (used when P.fwd_mfma)
+    bool xcd_gate = false;          // the per-XCD arrival counters are wanted
+};
+
+// First half of build_ctx: the rest of the validation, every scalar field of c->P and the host tables.  No HIP call, so the
+// decisions can be checked on a machine without a device; cu_count is the one thing asked of the device beforehand.
+int derive_ctx(bce_ctx* c, u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 baseG, u32 baseR, int method, int device, u32 cu_count,
+               HostTables& T) {
     c->n = n; c->N = N; c->q = q; c->Q = Q; c->qKS = qKS ? qKS : Q;
     c->baseKS = baseKS; c->baseG = baseG; c->baseR = baseR; c->method = method; c->device = device;
     while ((1u << c->logN) < N) ++c->logN;
@@ -200,59 +199,12 @@ int build_ctx(u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 baseG, u32 ba
     c->dR = digit_count((double)q, (double)baseR);
     c->is64 = Q >= (1ull << 28);
     c->wbytes = c->is64 ? 8 : 4;
-    // four gadget digits on N >= 1024 with a modulus of 28..30 bits (STD256, STD256_OPT: N = 2048, 29-bit Q, base 2^8): the
-    // integer 64-bit kernel with 32-bit digit rows (kernels64.hip, NARROW)
-    const bool narrow64 = c->is64 && c->dG == 4 && N >= 1024 && Q < (1ull << 31);
-    if (c->dG < 3 || c->dG > 4 || (N == 2048 && c->dG != 3 && !narrow64)) { g_create_error = "gadget digit count must be 3 or 4 (N = 2048: 3, or 4 with a ring modulus of 28..30 bits)"; return BCE_ERR_UNSUPPORTED; }
-    if (c->is64 && !(c->dG == 3 || (c->dG == 4 && N == 512) || narrow64)) { g_create_error = "64-bit path: four gadget digits need N = 512 or a ring modulus below 2^31"; return BCE_ERR_UNSUPPORTED; }
-    if (c->qKS > 0xFFFFFFFFull) { g_create_error = "qKS must fit 32 bits"; return BCE_ERR_UNSUPPORTED; }
-    c->psi = min_primitive_root(Q, 2ull * N);
-
-    if (hipSetDevice(device) != hipSuccess) { g_create_error = "hipSetDevice failed"; return BCE_ERR_HIP; }
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { g_create_error = "hipStreamCreate failed"; return BCE_ERR_HIP; }
-
-    // twiddle tables, OpenFHE ordering: tw[brv(i)] = psi^i
-    std::vector<uint2> twf(N);
-    std::vector<u32> psitab(N);
-    u64 p = 1;
-    for (u32 i = 0; i < N; ++i) {
-        psitab[i] = c->is64 ? 0 : (u32)p;
-        u32 r = bit_reverse(i, (int)c->logN);
-        // device layout: blocks m >= 64 transposed to [slot][lane] (kernels.hip tw_pos)
-        u32 pos = r;
-        if (r >= 64) {
-            const u32 s = 31u - (u32)__builtin_clz(r), sh = s - 6, ii = r - (1u << s);
-            pos = (1u << s) + ((ii & ((1u << sh) - 1u)) << 6) + (ii >> sh);
-        }
-        twf[pos] = c->is64 ? make_uint2(0, 0) : make_uint2((u32)p, (u32)(((u128)p << 32) / Q));
-        p = mul_mod(p, c->psi, Q);
-    }
-    if (hipMalloc(&c->d_twf, sizeof(uint2) * N) != hipSuccess) {
-        g_create_error = "hipMalloc(twiddles) failed";
-        return BCE_ERR_HIP;
-    }
-    hipMemcpy(c->d_twf, twf.data(), sizeof(uint2) * N, hipMemcpyHostToDevice);
-    if (hipMalloc(&c->d_psi, sizeof(u32) * N) != hipSuccess) { g_create_error = "hipMalloc(psi table) failed"; return BCE_ERR_HIP; }
-    hipMemcpy(c->d_psi, psitab.data(), sizeof(u32) * N, hipMemcpyHostToDevice);
-    const u64 r2modq = c->is64 ? 0 : (u64)((((u128)1) << 64) % Q);     // R^2 mod Q, R = 2^32
-    {
-        std::vector<u32> t(N);
-        for (u32 i = 0; i < N; ++i) t[i] = c->is64 ? 0 : (u32)mul_mod(psitab[i], r2modq, Q);
-        if (hipMalloc(&c->d_psi_r2, sizeof(u32) * N) != hipSuccess) { g_create_error = "hipMalloc(psi table) failed"; return BCE_ERR_HIP; }
-        hipMemcpy(c->d_psi_r2, t.data(), sizeof(u32) * N, hipMemcpyHostToDevice);
-    }
-    for (int i = 0; i < bce_ctx::kRing; ++i) hipEventCreateWithFlags(&c->ring_ev[i], hipEventDisableTiming);
 
     DevParams& P = c->P;
     P.n = n; P.N = N; P.logN = c->logN; P.q = (u32)q; P.Q = (u32)Q; P.qKS = (u32)c->qKS;
     P.baseKS = baseKS; P.dKS = c->dKS;
     P.ksk_stride = (n + 1 + 63) & ~63u;
     P.ksk_u16 = c->qKS <= 65536 ? 1 : 0;
-    {
-        const u64 ch = (((u64)1) << 32) / c->qKS;
-        if (ch < 8) { g_create_error = "qKS too large for the key-switch gather (needs qKS <= 2^29)"; return BCE_ERR_ARG; }
-        P.ks_chunk = (u32)std::min<u64>(ch & ~(u64)7, 1u << 20);
-    }
     P.gBits = c->gBits; P.dG = c->dG; P.baseR = baseR; P.dR = c->dR;
     P.method_ap = method == BCE_AP ? 1 : 0;
     P.factor = (u32)(2 * N / q);
@@ -283,26 +235,59 @@ int build_ctx(u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 baseG, u32 ba
         // REDC(y) + acc (< 2Q) < 4Q < 2^32 and one conditional subtraction of 2Q returns it to [0, 2Q)
         const u128 rmax = (sum >> 32) + 1 + Q, ymax = 2 * rmax * 2 * Q;
         const bool ok5 = ymax < ((u128)1 << 64) && (ymax >> 32) + 1 + Q <= 2 * (u128)Q && (u128)4 * Q < ((u128)1 << 32);
-        P.lazy = (ok1 && ok2 && ok3 && ok4 && ok5) ? 1 : 0;
+        P.lazy = (c->is64 || (ok1 && ok2 && ok3 && ok4 && ok5)) ? 1 : 0;   // (the 64-bit kernels have no other form)
+    }
+    P.is64 = c->is64 ? 1 : 0;
+    P.Q64 = Q;
+    {
+        const char* var = std::getenv("BCE_VARIANT");  // development knob, see DevParams::variant
+        P.variant = var ? (u32)std::atoi(var) : 0;
+        P.cu_count = cu_count;
+        P.fuse_tail = env_off("BCE_FUSE_TAIL") ? 0 : 1;  // development / parity knob: 0 keeps the separate tail kernels
+    }
+    // The kernel family and what follows from it (kernels.hpp, kernel_class).  Two requests go in and come back as granted:
+    // BCE_OCCUPANCY (development knob: 2 or 3 workgroups per CU of the one-wave-per-transform kernel) and the double-precision
+    // formulation of the 64-bit path (kernels64.hip, namespace wd): exact for Q < 2^39; BCE_FP64=0 keeps the integer kernel
+    // (development / parity knob)
+    const char* occ = std::getenv("BCE_OCCUPANCY");
+    P.occupancy_target = (occ && occ[0] == '2') ? 2 : 3;
+    P.fp64 = (c->is64 && Q < (1ull << 39) && !env_off("BCE_FP64")) ? 1 : 0;
+    const KernelClass kc = kernel_class(P);
+    P.occupancy_target = kc.occupancy_target;
+    P.fp64 = kc.fp64;
+    if (kc.error) { g_create_error = kc.error; return BCE_ERR_UNSUPPORTED; }
+    if (c->qKS > 0xFFFFFFFFull) { g_create_error = "qKS must fit 32 bits"; return BCE_ERR_UNSUPPORTED; }
+    c->psi = min_primitive_root(Q, 2ull * N);
+
+    // twiddle tables, OpenFHE ordering: tw[brv(i)] = psi^i
+    T.twf.resize(N);
+    T.psi.resize(N);
+    u64 p = 1;
+    for (u32 i = 0; i < N; ++i) {
+        T.psi[i] = c->is64 ? 0 : (u32)p;
+        u32 r = bit_reverse(i, (int)c->logN);
+        // device layout: blocks m >= 64 transposed to [slot][lane] (kernels.hip tw_pos)
+        u32 pos = r;
+        if (r >= 64) {
+            const u32 s = 31u - (u32)__builtin_clz(r), sh = s - 6, ii = r - (1u << s);
+            pos = (1u << s) + ((ii & ((1u << sh) - 1u)) << 6) + (ii >> sh);
+        }
+        T.twf[pos] = c->is64 ? make_uint2(0, 0) : make_uint2((u32)p, (u32)(((u128)p << 32) / Q));
+        p = mul_mod(p, c->psi, Q);
+    }
+    const u64 r2modq = c->is64 ? 0 : (u64)((((u128)1) << 64) % Q);     // R^2 mod Q, R = 2^32
+    T.psi_r2.resize(N);
+    for (u32 i = 0; i < N; ++i) T.psi_r2[i] = c->is64 ? 0 : (u32)mul_mod(T.psi[i], r2modq, Q);
+    {
+        const u64 ch = (((u64)1) << 32) / c->qKS;
+        if (ch < 8) { g_create_error = "qKS too large for the key-switch gather (needs qKS <= 2^29)"; return BCE_ERR_ARG; }
+        P.ks_chunk = (u32)std::min<u64>(ch & ~(u64)7, 1u << 20);
     }
     if (!c->is64) {
         u32 inv = (u32)Q;                                  // Newton: inv = Q^-1 mod 2^32 (Q odd)
         for (int i = 0; i < 5; ++i) inv *= 2u - (u32)Q * inv;
         P.qinv_neg = 0u - inv;
         P.r2_off = (u32)(Q - r2modq);
-    }
-    {
-        const char* occ = std::getenv("BCE_OCCUPANCY");  // development knob: 2 or 3 workgroups per CU
-        P.occupancy_target = (occ && occ[0] == '2') ? 2 : 3;
-        const size_t lds = (2 * (size_t)N + (2 + 2 * c->dG) * ((size_t)N + (N >> 6) * 4) + ((n + 1 + 3) & ~3u)) * 4;
-        if (3 * lds > 160 * 1024) P.occupancy_target = 2;
-        const char* var = std::getenv("BCE_VARIANT");  // development knob, see DevParams::variant
-        P.variant = var ? (u32)std::atoi(var) : 0;
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
-        P.cu_count = (u32)cus;
-        const char* ft = std::getenv("BCE_FUSE_TAIL");  // development / parity knob: 0 keeps the separate tail kernels
-        P.fuse_tail = (ft && ft[0] == '0') ? 0 : 1;
     }
     {
         u64 I = pow_mod(c->psi, N / 2, Q), v = 1;
@@ -315,50 +300,28 @@ int build_ctx(u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 baseG, u32 ba
         P.Winv_last = (u32)wl;
         P.Winv_last_s = c->is64 ? 0 : (u32)(((u128)wl << 32) / Q);
     }
-    P.tw_f = c->d_twf;
-    P.psi_tab = c->d_psi;
-    P.psi_tab_r2 = c->d_psi_r2;
-    P.xcd_gate = nullptr;
     P.xcd_gate_ticks = 10000;   // 100 us
-    if (const char* e = std::getenv("BCE_XCD_GATE"); !c->is64 && !(e && e[0] == '0')) {   // on by default (32-bit path); BCE_XCD_GATE=0: A/B runs
-        if (hipMalloc(&c->d_xcd_gate, 16 * 32 * sizeof(u32)) != hipSuccess) { g_create_error = "hipMalloc(xcd gate) failed"; return BCE_ERR_HIP; }
-        P.xcd_gate = c->d_xcd_gate;
-        if (const char* t = std::getenv("BCE_XCD_GATE_US")) P.xcd_gate_ticks = (u32)std::atoi(t) * 100u;
-    }
-    P.is64 = c->is64 ? 1 : 0;
-    P.Q64 = Q;
+    T.xcd_gate = !c->is64 && !env_off("BCE_XCD_GATE");   // on by default (32-bit path); BCE_XCD_GATE=0: A/B runs
+    if (const char* t = std::getenv("BCE_XCD_GATE_US"); t && T.xcd_gate) P.xcd_gate_ticks = (u32)std::atoi(t) * 100u;
     P.Q8p1_64 = Q / 8 + 1;
     P.mu64 = (u64)((((u128)1) << 64) / Q);
     P.c64 = (u64)((((u128)1) << 64) % Q);
     P.Ninv64 = ninv;
     P.Ninv64_s = (u64)(((u128)ninv << 64) / Q);
     if (c->is64) {
-        std::vector<ulonglong2> tw64(N);
+        T.tw64.resize(N);
         u64 pw = 1;
         for (u32 i = 0; i < N; ++i) {
-            tw64[bit_reverse(i, (int)c->logN)] = make_ulonglong2(pw, (u64)(((u128)pw << 64) / Q));
+            T.tw64[bit_reverse(i, (int)c->logN)] = make_ulonglong2(pw, (u64)(((u128)pw << 64) / Q));
             pw = mul_mod(pw, c->psi, Q);
         }
-        if (hipMalloc(&c->d_tw64, sizeof(ulonglong2) * N) != hipSuccess) { g_create_error = "hipMalloc(twiddles64) failed"; return BCE_ERR_HIP; }
-        hipMemcpy(c->d_tw64, tw64.data(), sizeof(ulonglong2) * N, hipMemcpyHostToDevice);
-        P.tw64 = c->d_tw64;
-        P.lazy = 1;
-        // double-precision formulation (kernels64.hip, namespace wd): exact for Q < 2^39; BCE_FP64=0 keeps the
-        // integer kernel (development / parity knob)
-        const char* fp = std::getenv("BCE_FP64");
-        P.fp64 = (Q < (1ull << 39) && !(fp && fp[0] == '0')) ? 1 : 0;
-        if (narrow64) P.fp64 = 0;   // no doubles kernel for this class: the key words stay 64-bit integers
-        // includes the 16 KiB twiddle mirror of the 8-wave N = 2048 kernel (n <= ~1020 there)
-        if (blind_rotate64_lds_bytes(P) > 160 * 1024) { g_create_error = "64-bit path: polynomials (+ twiddle mirror) do not fit the 160 KiB LDS"; return BCE_ERR_UNSUPPORTED; }
+        if (kc.lds_error) { g_create_error = kc.lds_error; return BCE_ERR_UNSUPPORTED; }
         P.Qd = (double)Q;
         P.invQd = 1.0 / (double)Q;
         P.Ninvd = (double)ninv;
         P.Ninvd_q = (double)ninv / (double)Q;
-        std::vector<double2> twd(N);
-        for (u32 i = 0; i < N; ++i) twd[i] = make_double2((double)tw64[i].x, (double)tw64[i].x / (double)Q);
-        if (hipMalloc(&c->d_tw64d, sizeof(double2) * N) != hipSuccess) { g_create_error = "hipMalloc(twiddles64d) failed"; return BCE_ERR_HIP; }
-        hipMemcpy(c->d_tw64d, twd.data(), sizeof(double2) * N, hipMemcpyHostToDevice);
-        P.tw64d = c->d_tw64d;
+        T.tw64d.resize(N);
+        for (u32 i = 0; i < N; ++i) T.tw64d[i] = make_double2((double)T.tw64[i].x, (double)T.tw64[i].x / (double)Q);
     }
     // Lowest gadget digit folded into the key (kernels.hip, FOLD): needs a kernel that has the variant and an EXACT
     // SignedDigitDecompose -- every centred residue d in [-(Q - Q/2), Q/2) must equal sum_l r_l B^l with dG digits
@@ -371,36 +334,93 @@ int build_ctx(u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 baseG, u32 ba
         for (u32 l = 0; l < c->dG; ++l) { span += pw; pw *= Bg; }
         const u128 hi = (Bg / 2 - 1) * span, lo = (Bg / 2) * span;       // largest / smallest (negated) representable value
         const bool exact = (u128)(Q >> 1) <= hi + 1 && (u128)(Q - (Q >> 1)) <= lo;
-        // (the folded fp64 kernels multiply a digit by a twiddle in one exact multiplication: |digit| Q <= (B / 2) Q < 2^53)
-        const bool has_kernel = c->is64 ? (P.fp64 && c->logN == 11 && c->dG == 3 && (Bg / 2) * (u128)Q < ((u128)1 << 53))   // kernels64.hip, N = 2048
-                                         : (c->logN == 10 && c->dG == 4 && P.lazy && P.variant != 1);  // kernels.hip, split transform
-        const char* fo = std::getenv("BCE_FOLD");
-        P.fold = (exact && has_kernel && !(fo && fo[0] == '0')) ? 1 : 0;
-        P.fold_ninv = (P.fold && c->is64 && P.fp64) ? 1 : 0;
+        // the folded fp64 kernels multiply a digit by a twiddle in one exact multiplication: |digit| Q <= (B / 2) Q < 2^53
+        const bool product_exact = kc.family != KernelFamily::Fp64 || (Bg / 2) * (u128)Q < ((u128)1 << 53);
+        P.fold = (exact && kc.fold_build && product_exact && !env_off("BCE_FOLD")) ? 1 : 0;
+        P.fold_ninv = (P.fold && kc.family == KernelFamily::Fp64) ? 1 : 0;
         // forward transforms of the folded N = 1024 GINX kernel as quarter units (kernels.hip); that build is also compiled
         // with the MAC tail of an even factor, so an odd factor keeps the whole-row + half-row bodies and the general tail.
         // BCE_FWD_UNITS=0 keeps them everywhere (development / parity knob, same binary)
-        const char* fu = std::getenv("BCE_FWD_UNITS");
-        P.fwd_units = (P.fold && !c->is64 && c->method == BCE_GINX && P.factor_even && !(fu && fu[0] == '0')) ? 1 : 0;
+        P.fwd_units = (P.fold && !c->is64 && c->method == BCE_GINX && P.factor_even && !env_off("BCE_FWD_UNITS")) ? 1 : 0;
         // The stages on bits 9..4 of those transforms on the matrix pipe (kernels.hip, ntt_forward_quarter3<true>): a variant of
         // the quarter units, so it needs everything they need (folded key, GINX, even factor, N = 1024, dG = 4) and the
         // arithmetic conditions of fwd_mfma.hpp (gBits <= 7, four 7-bit limbs, exact limb sums, recombined word <= 13Q).
         // Bound chain of the forward phase with this body: recombined words < 2Q + lo_max (< 4Q for STD128*), four lazy stages
         // add < 2Q each -> MAC operands < 12Q, below the 22Q = (2 logN + 2) Q that ok1..ok5 above were checked with.
         // Anything that fails keeps the quarter-unit body; BCE_FWD_MFMA=0 keeps it as well (development / parity knob).
-        P.fwd_mfma = 0; P.w14 = P.w14s = 0; P.fwd_mfma_tab = nullptr;
-        const char* fm = std::getenv("BCE_FWD_MFMA");
-        if (P.fwd_units && !(fm && fm[0] == '0')) {
-            const FwdMfmaTables T = build_fwd_mfma_tables(Q, N, c->gBits, c->dG, c->psi);
-            if (T.ok) {
-                if (hipMalloc(&c->d_fwd_mfma, sizeof(u32) * kFwdMfmaTableWords) != hipSuccess) { g_create_error = "hipMalloc(forward matrix table) failed"; return BCE_ERR_HIP; }
-                hipMemcpy(c->d_fwd_mfma, T.table.data(), sizeof(u32) * kFwdMfmaTableWords, hipMemcpyHostToDevice);
-                P.fwd_mfma = 1; P.w14 = T.w14; P.w14s = T.w14s; P.fwd_mfma_tab = c->d_fwd_mfma;
-            }
+        P.fwd_mfma = 0; P.w14 = P.w14s = 0;
+        if (P.fwd_units && !env_off("BCE_FWD_MFMA")) {
+            T.fwd = build_fwd_mfma_tables(Q, N, c->gBits, c->dG, c->psi);
+            if (T.fwd.ok) { P.fwd_mfma = 1; P.w14 = T.fwd.w14; P.w14s = T.fwd.w14s; }
         }
     }
     P.pool_stride = n + 1;
+    return BCE_OK;
+}
+
+// Second half: stream, events, and the tables of derive_ctx on the device
+int upload_ctx(bce_ctx* c, const HostTables& T) {
+    DevParams& P = c->P;
+    if (hipSetDevice(c->device) != hipSuccess) { g_create_error = "hipSetDevice failed"; return BCE_ERR_HIP; }
+    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { g_create_error = "hipStreamCreate failed"; return BCE_ERR_HIP; }
+    // device copy of a host table; what names the table in the message of a failed allocation
+    const auto up = [](auto** dst, const auto& v, const char* what) -> bool {
+        const size_t bytes = v.size() * sizeof(v[0]);
+        if (hipMalloc(reinterpret_cast<void**>(dst), bytes) != hipSuccess) { g_create_error = std::string("hipMalloc(") + what + ") failed"; return false; }
+        hipMemcpy(*dst, v.data(), bytes, hipMemcpyHostToDevice);
+        return true;
+    };
+    if (!up(&c->d_twf, T.twf, "twiddles") || !up(&c->d_psi, T.psi, "psi table") || !up(&c->d_psi_r2, T.psi_r2, "psi table")) return BCE_ERR_HIP;
+    for (int i = 0; i < bce_ctx::kRing; ++i) hipEventCreateWithFlags(&c->ring_ev[i], hipEventDisableTiming);
+    P.tw_f = c->d_twf;
+    P.psi_tab = c->d_psi;
+    P.psi_tab_r2 = c->d_psi_r2;
+    P.xcd_gate = nullptr;
+    if (T.xcd_gate) {
+        if (hipMalloc(&c->d_xcd_gate, 16 * 32 * sizeof(u32)) != hipSuccess) { g_create_error = "hipMalloc(xcd gate) failed"; return BCE_ERR_HIP; }
+        P.xcd_gate = c->d_xcd_gate;
+    }
+    if (c->is64) {
+        if (!up(&c->d_tw64, T.tw64, "twiddles64") || !up(&c->d_tw64d, T.tw64d, "twiddles64d")) return BCE_ERR_HIP;
+        P.tw64 = c->d_tw64;
+        P.tw64d = c->d_tw64d;
+    }
+    P.fwd_mfma_tab = nullptr;
+    if (P.fwd_mfma) {
+        if (!up(&c->d_fwd_mfma, T.fwd.table, "forward matrix table")) return BCE_ERR_HIP;
+        P.fwd_mfma_tab = c->d_fwd_mfma;
+    }
     c->enc_seed_ok = os_entropy(c->enc_seed);
+    return BCE_OK;
+}
+
+int build_ctx(u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 baseG, u32 baseR, int method, int device,
+              bce_ctx** out) {
+    if (!out) return BCE_ERR_ARG;
+    *out = nullptr;
+    if (method != BCE_AP && method != BCE_GINX) { g_create_error = "bad method (expect AP=1 or GINX=2)"; return BCE_ERR_ARG; }
+    if (N < 512 || N > 2048 || (N & (N - 1))) { g_create_error = "ring dimension N must be 512, 1024 or 2048"; return BCE_ERR_UNSUPPORTED; }
+    if ((q & (q - 1)) || q > 2 * (u64)N || q < 8) { g_create_error = "LWE modulus q must be a power of two dividing 2N"; return BCE_ERR_ARG; }
+    if (!is_prime_u64(Q) || (Q - 1) % (2ull * N)) { g_create_error = "Q must be a prime = 1 mod 2N"; return BCE_ERR_ARG; }
+    if (Q >= (1ull << 40)) { g_create_error = "ring modulus Q must be below 2^40"; return BCE_ERR_UNSUPPORTED; }
+    if (baseG & (baseG - 1)) { g_create_error = "gadget base must be a power of two"; return BCE_ERR_ARG; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        g_create_error = "no HIP device visible: the engine has no CPU fallback";
+        return BCE_ERR_NO_DEVICE;
+    }
+    if (device < 0 || device >= ndev) { g_create_error = "bad device ordinal"; return BCE_ERR_ARG; }
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
+
+    // partially built contexts are released through bce_ctx_destroy (frees whatever was allocated)
+    struct CtxDeleter { void operator()(bce_ctx* p) const { bce_ctx_destroy(p); } };
+    std::unique_ptr<bce_ctx, CtxDeleter> c(new bce_ctx);
+    { std::lock_guard<std::mutex> lk(g_live_mu); g_live.insert(c.get()); }
+    HostTables T;
+    int rc = derive_ctx(c.get(), n, N, q, Q, qKS, baseKS, baseG, baseR, method, device, (u32)cus, T);
+    if (rc == BCE_OK) rc = upload_ctx(c.get(), T);
+    if (rc != BCE_OK) return rc;
     *out = c.release();
     return BCE_OK;
 }
@@ -410,7 +430,7 @@ u64 rgsw_rows_total(const bce_ctx* c);
 // when the lowest gadget digit is folded (P.fold); IEEE doubles for the double-precision 64-bit kernels (exact, Q < 2^39)
 int bsk_words_to_kernel_layout(bce_ctx* c) {
     if (c->P.fold) HIP_TRY(c, launch_fold_gadget(c->P, c->d_bsk, rgsw_rows_total(c) / (2ull * c->dG), +1, c->stream));
-    if (!c->is64 || !c->P.fp64) { HIP_TRY(c, hipStreamSynchronize(c->stream)); return BCE_OK; }
+    if (!c->P.fp64) { HIP_TRY(c, hipStreamSynchronize(c->stream)); return BCE_OK; }
     HIP_TRY(c, launch_words_u64_f64(static_cast<u64*>(c->d_bsk), (size_t)c->bsk_polys * c->N, 1, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return BCE_OK;
@@ -512,14 +532,34 @@ void drain_timing(bce_ctx* c) {
 }
 
 
-// ---- word-size generic device helpers (u32: kernels.hip, u64: kernels64.hip) -----------------
+// uint64_t words of the ABI <-> words in device memory: u64 as they are (wide), u32 through a staging vector.  The
+// accumulators, key words and polynomials of a context are wide when c->is64; LWE words are always 32-bit.
+int words_to_device(bce_ctx* c, void* dev, const u64* src, size_t words, bool wide) {
+    if (wide) {
+        HIP_TRY(c, hipMemcpy(dev, src, words * 8, hipMemcpyHostToDevice));
+    } else {
+        const std::vector<u32> tmp(src, src + words);
+        HIP_TRY(c, hipMemcpy(dev, tmp.data(), words * 4, hipMemcpyHostToDevice));
+    }
+    return BCE_OK;
+}
+int words_from_device(bce_ctx* c, u64* dst, const void* dev, size_t words, bool wide) {
+    if (wide) {
+        HIP_TRY(c, hipMemcpy(dst, dev, words * 8, hipMemcpyDeviceToHost));
+    } else {
+        std::vector<u32> tmp(words);
+        HIP_TRY(c, hipMemcpy(tmp.data(), dev, words * 4, hipMemcpyDeviceToHost));
+        std::copy(tmp.begin(), tmp.end(), dst);
+    }
+    return BCE_OK;
+}
+
 int dev_ntt(bce_ctx* c, void* polys, u64 count, int inverse) {
     // count may exceed what one launch indexes comfortably; split in slabs of 2^20 polys
     const u64 slab = 1u << 20;
     for (u64 o = 0; o < count; o += slab) {
         const u32 cnt = (u32)std::min<u64>(slab, count - o);
-        if (c->is64) HIP_TRY(c, launch_ntt_batch64(c->P, static_cast<u64*>(polys) + o * c->N, cnt, inverse, c->stream));
-        else HIP_TRY(c, launch_ntt_batch(c->P, static_cast<u32*>(polys) + o * c->N, cnt, inverse, c->stream));
+        HIP_TRY(c, launch_ntt_batch(c->P, static_cast<char*>(polys) + o * c->N * c->wbytes, cnt, inverse, c->stream));
     }
     return BCE_OK;
 }
@@ -566,12 +606,7 @@ int keygen_bsk(bce_ctx* c, const KeygenParams& kp, KeygenDev& D) {
     {
         std::vector<u64> zq(N);
         for (u32 k = 0; k < N; ++k) zq[k] = lift_signed(c->z[k], Q);
-        if (c->is64) {
-            HIP_TRY(c, hipMemcpy(D.zq, zq.data(), N * 8, hipMemcpyHostToDevice));
-        } else {
-            std::vector<u32> z32(zq.begin(), zq.end());
-            HIP_TRY(c, hipMemcpy(D.zq, z32.data(), N * 4, hipMemcpyHostToDevice));
-        }
+        if (const int rc = words_to_device(c, D.zq, zq.data(), N, c->is64)) return rc;
     }
     int rc = dev_ntt(c, D.zq, 1, 0);
     if (rc) return rc;
@@ -583,8 +618,7 @@ int keygen_bsk(bce_ctx* c, const KeygenParams& kp, KeygenDev& D) {
         if ((rc = dev_ntt(c, dst, cnt * 2, 0))) return rc;
         if ((rc = dev_ntt(c, D.ta, cnt, 0))) return rc;
         // b-column (odd polys) += NTT(a) * NTT(z)
-        if (c->is64) HIP_TRY(c, launch_pointwise_mac64(c->P, (u64*)dst + N, (const u64*)D.ta, (const u64*)D.zq, (u32)cnt, 2, c->stream));
-        else HIP_TRY(c, launch_pointwise_mac(c->P, (u32*)dst + N, (const u32*)D.ta, (const u32*)D.zq, (u32)cnt, 2, c->stream));
+        HIP_TRY(c, launch_pointwise_mac(c->P, dst + N * wb, D.ta, D.zq, (u32)cnt, 2, c->stream));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return BCE_OK;
@@ -616,7 +650,7 @@ int sync_stream(bce_ctx* c) {
 int launch_bootstraps(bce_ctx* c, const bce_gate_desc* dd, u32 n, u32 instances, u32 slot_stride, void* d_acc,
                       u32* d_lweN, u32* d_ks, bool timed, bool* fused_out, u64* d_partial = nullptr) {
     const size_t nb = (size_t)n * instances;
-    int kid = BCE_BR_WORD64;
+    int kid = 0;
     bool tail_fused = false;
     const bool events = timed && c->events_on;
     EventPair e0{};
@@ -624,8 +658,7 @@ int launch_bootstraps(bce_ctx* c, const bce_gate_desc* dd, u32 n, u32 instances,
     LaunchEvents le0{};
     if (events) { e0 = get_events(c, 0); le0 = LaunchEvents{e0.a, e0.b}; }
     {   // a launch that fails hands its event pair back (it would otherwise be neither pending nor free)
-        const hipError_t e = c->is64 ? launch_blind_rotate64(c->P, dd, n, instances, slot_stride, static_cast<u64*>(d_acc), c->stream, d_lweN, d_ks, &tail_fused, le0)
-                                     : launch_blind_rotate(c->P, dd, n, instances, slot_stride, static_cast<u32*>(d_acc), c->stream, &kid, d_lweN, d_ks, &tail_fused, le0);
+        const hipError_t e = launch_blind_rotate(c->P, dd, n, instances, slot_stride, d_acc, c->stream, &kid, d_lweN, d_ks, &tail_fused, le0);
         if (e != hipSuccess) {
             if (events) c->free_events.push_back(e0);
             HIP_TRY(c, e);
@@ -710,17 +743,9 @@ int eval_impl(bce_ctx* c, u32 n_desc, const bce_gate_desc* descs, u32 instances,
         c->ring_busy[slot] = true;
         if (dbg_acc || dbg_lweN || dbg_ks) {
             HIP_TRY(c, hipStreamSynchronize(c->stream));
-            std::vector<u32> tmp;
-            auto fetch = [&](const u32* dev, size_t words, u64* dst) -> int {
-                tmp.resize(words);
-                HIP_TRY(c, hipMemcpy(tmp.data(), dev, words * 4, hipMemcpyDeviceToHost));
-                for (size_t i = 0; i < words; ++i) dst[i] = tmp[i];
-                return BCE_OK;
-            };
-            if (dbg_acc && c->is64) HIP_TRY(c, hipMemcpy(dbg_acc, c->d_acc, nb * 2 * c->N * 8, hipMemcpyDeviceToHost));
-            if (dbg_acc && !c->is64 && (rc = fetch(static_cast<const u32*>(c->d_acc), nb * 2 * c->N, dbg_acc))) return rc;
-            if (dbg_lweN && (rc = fetch(d_lweN, nb * (c->N + 1), dbg_lweN))) return rc;
-            if (dbg_ks && (rc = fetch(d_ks, nb * (c->n + 1), dbg_ks))) return rc;
+            if (dbg_acc && (rc = words_from_device(c, dbg_acc, c->d_acc, nb * 2 * c->N, c->is64))) return rc;
+            if (dbg_lweN && (rc = words_from_device(c, dbg_lweN, d_lweN, nb * (c->N + 1), false))) return rc;
+            if (dbg_ks && (rc = words_from_device(c, dbg_ks, d_ks, nb * (c->n + 1), false))) return rc;
             if (d_lweN) hipFree(d_lweN);
             if (d_ks) hipFree(d_ks);
         }
@@ -872,18 +897,11 @@ static int import_keys_impl(bce_ctx* c, const int32_t* s, const int32_t* z, cons
         // (evaluation-form words arrive in the engine's own order: OpenFHE's bit-reversed CT order for the minimal
         // primitive 2N-th root, bce_get_params()[BCE_P_psi])
         const u64 chunk = (u64)64 << 20;
-        std::vector<u32> tmp32;
         for (u64 o = 0; o < bsk_words; o += chunk) {
             const u64 cnt = std::min(chunk, bsk_words - o);
             for (u64 i = 0; i < cnt; ++i)
                 if (bsk[o + i] >= c->Q) return c->fail(BCE_ERR_ARG, "bsk word %llu not reduced mod Q", (unsigned long long)(o + i));
-            if (c->is64) {
-                HIP_TRY(c, hipMemcpy(static_cast<u64*>(c->d_bsk) + o, bsk + o, cnt * 8, hipMemcpyHostToDevice));
-            } else {
-                tmp32.resize(cnt);
-                for (u64 i = 0; i < cnt; ++i) tmp32[i] = (u32)bsk[o + i];
-                HIP_TRY(c, hipMemcpy(static_cast<u32*>(c->d_bsk) + o, tmp32.data(), cnt * 4, hipMemcpyHostToDevice));
-            }
+            if ((rc = words_to_device(c, static_cast<char*>(c->d_bsk) + o * c->wbytes, bsk + o, cnt, c->is64))) return rc;
         }
         if (!evaluation_form && (rc = dev_ntt(c, c->d_bsk, bsk_words / c->N, 0))) return rc;
         if ((rc = bsk_words_to_kernel_layout(c))) return rc;
@@ -915,7 +933,6 @@ static int export_bsk_impl(bce_ctx* c, uint64_t* bsk, bool evaluation_form) {
     void* d_tmp = nullptr;
     HIP_TRY(c, hipMalloc(&d_tmp, chunk_polys * c->N * c->wbytes));
     struct Free { void* p; ~Free() { hipFree(p); } } free_tmp{d_tmp};  // released on every return path
-    std::vector<u32> tmp32;
     for (u64 p0 = 0; p0 < words / c->N; p0 += chunk_polys) {
         const u64 cnt = std::min(chunk_polys, words / c->N - p0), w = cnt * c->N;
         const char* src = static_cast<const char*>(c->d_bsk) + p0 * c->N * c->wbytes;
@@ -924,13 +941,7 @@ static int export_bsk_impl(bce_ctx* c, uint64_t* bsk, bool evaluation_form) {
         if (c->P.fold) HIP_TRY(c, launch_fold_gadget(c->P, d_tmp, cnt / (4ull * c->dG), -1, c->stream));   // rows l >= 1 += B^l row 0
         if (!evaluation_form) { int rc = dev_ntt(c, d_tmp, cnt, 1); if (rc) return rc; }
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (c->is64) {
-            HIP_TRY(c, hipMemcpy(bsk + p0 * c->N, d_tmp, w * 8, hipMemcpyDeviceToHost));
-        } else {
-            tmp32.resize(w);
-            HIP_TRY(c, hipMemcpy(tmp32.data(), d_tmp, w * 4, hipMemcpyDeviceToHost));
-            for (u64 i = 0; i < w; ++i) bsk[p0 * c->N + i] = tmp32[i];
-        }
+        if (const int rc = words_from_device(c, bsk + p0 * c->N, d_tmp, w, c->is64)) return rc;
     }
     return BCE_OK;
 }
@@ -1490,7 +1501,7 @@ int bce_dag_run(bce_ctx* c, bce_dag* g, uint32_t instances, uint32_t slot_stride
         wps = t1 <= t2 ? 2 : 4;
     }
     if (const char* e = std::getenv("BCE_DAG_WPS")) { if (e[0] == '2') wps = 2; else if (e[0] == '4') wps = 4; }
-    if (c->P.is64) wps = 2;      // the config-5 kernel: one 1,024-thread workgroup is all a CU's LDS holds
+    if (kernel_class(c->P).wg_per_cu_full == 1) wps = 2;   // the config-5 kernel: one 1,024-thread workgroup is all a CU's LDS holds
     if (const char* e = std::getenv("BCE_DAG_PLACE")) D.policy = e[0] == '0' ? 0u : 1u;
     const char* dbg = std::getenv("BCE_DAG_DEBUG");   // development: 'r' = re-arm only, 'd' = dry run (no bootstraps)
     if (dbg && dbg[0] == 'd') D.policy |= 2u;
@@ -1562,25 +1573,17 @@ int bce_forward_mfma_tables(uint64_t Q, uint32_t N, uint32_t gBits, uint32_t dG,
 
 int bce_launch_capacity(const bce_ctx* c, uint32_t* lone, uint32_t* full) {
     if (!c || !lone || !full) return BCE_ERR_ARG;
-    const DevParams& P = c->P;
-    const u32 cu = P.cu_count;
-    u32 per_cu;
-    if (c->is64) {
-        // 64-bit kernels: LDS-bound residency (N = 2048: one workgroup per CU)
-        per_cu = (u32)std::max<size_t>(1, (160 * 1024) / blind_rotate64_lds_bytes(P));
-        if (c->logN == 11) per_cu = 1;
-    } else if (P.variant != 1 && c->logN == 10 && c->dG == 4 && P.lazy) {
-        per_cu = 2;                                    // split-transform kernel, 128-register build
-    } else {
-        per_cu = P.occupancy_target;                   // one wave per transform: 2 or 3 workgroups per CU
-    }
-    *lone = cu;
-    *full = cu * per_cu;
+    const KernelClass k = kernel_class(c->P);
+    *lone = c->P.cu_count * k.wg_per_cu_lone;
+    *full = c->P.cu_count * k.wg_per_cu_full;
     return BCE_OK;
 }
 
 int bce_bytes_per_bootstrap_parts(const bce_ctx* c, uint64_t out[3]) {
     if (!c || !out) return BCE_ERR_ARG;
+    // SURVEY.md 8(d): w_bsk*[RGSWs touched * (2dG)*2*N] + w_ks*[N*dKS*(n+1)] + w_ct*[3(n+1)] at this build's widths.
+    // GINX touches 2 RGSW ciphertexts per LWE coefficient, AP one per non-zero base-baseR digit
+    // (dR * (baseR-1)/baseR on average).
     const double rgsws = c->method == BCE_AP ? (double)c->n * c->dR * (c->baseR - 1) / c->baseR : 2.0 * c->n;
     out[0] = (u64)((double)c->wbytes * rgsws * (2 * c->dG) * 2 * c->N);
     out[1] = (c->P.ksk_u16 ? 2ull : 4ull) * c->N * c->dKS * (c->n + 1);
@@ -1589,15 +1592,8 @@ int bce_bytes_per_bootstrap_parts(const bce_ctx* c, uint64_t out[3]) {
 }
 
 uint64_t bce_bytes_per_bootstrap(const bce_ctx* c) {
-    if (!c) return 0;
-    // SURVEY.md 8(d): w_bsk*[RGSWs touched * (2dG)*2*N] + w_ks*[N*dKS*(n+1)] + w_ct*[3(n+1)] at this build's widths.
-    // GINX touches 2 RGSW ciphertexts per LWE coefficient, AP one per non-zero base-baseR digit
-    // (dR * (baseR-1)/baseR on average).
-    const double rgsws = c->method == BCE_AP ? (double)c->n * c->dR * (c->baseR - 1) / c->baseR : 2.0 * c->n;
-    const u64 bsk = (u64)((double)c->wbytes * rgsws * (2 * c->dG) * 2 * c->N);
-    const u64 ks = (c->P.ksk_u16 ? 2ull : 4ull) * c->N * c->dKS * (c->n + 1);
-    const u64 ct = 4ull * 3 * (c->n + 1);
-    return bsk + ks + ct;
+    uint64_t parts[3];
+    return bce_bytes_per_bootstrap_parts(c, parts) == BCE_OK ? parts[0] + parts[1] + parts[2] : 0;
 }
 
 int bce_debug_eval_stages(bce_ctx* c, uint32_t n_desc, const bce_gate_desc* descs, uint64_t* acc, uint64_t* lweN,
@@ -1631,29 +1627,17 @@ int bce_debug_tail(bce_ctx* c, uint32_t count, const uint64_t* acc, const uint32
     HIP_TRY(c, hipMalloc(&d_lweN, (size_t)count * (c->N + 1) * sizeof(u32)));
     HIP_TRY(c, hipMalloc(&d_ks, (size_t)count * (c->n + 1) * sizeof(u32)));
     HIP_TRY(c, hipMalloc(&d_partial, std::max<size_t>(1, tail_partial_words(c->P, count)) * sizeof(u64)));
-    std::vector<u32> tmp;
-    if (c->is64) {
-        HIP_TRY(c, hipMemcpy(d_in, acc, words * 8, hipMemcpyHostToDevice));
-    } else {
-        tmp.assign(acc, acc + words);
-        HIP_TRY(c, hipMemcpy(d_in, tmp.data(), words * 4, hipMemcpyHostToDevice));
-    }
+    int rc = words_to_device(c, d_in, acc, words, c->is64);
+    if (rc) return rc;
     bce_gate_desc* dd = nullptr;
     int slot = 0;
-    int rc = stage_descs(c, d.data(), count, &dd, &slot);
-    if (rc) return rc;
+    if ((rc = stage_descs(c, d.data(), count, &dd, &slot))) return rc;
     HIP_TRY(c, launch_tail(c->P, dd, count, 1, 0, d_in, d_partial, d_lweN, d_ks, c->stream, LaunchEvents{}));
     hipEventRecord(c->ring_ev[slot], c->stream);
     c->ring_busy[slot] = true;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    auto fetch = [&](const u32* dev, size_t n, u64* dst) -> int {
-        tmp.resize(n);
-        HIP_TRY(c, hipMemcpy(tmp.data(), dev, n * 4, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n; ++i) dst[i] = tmp[i];
-        return BCE_OK;
-    };
-    if (lweN && (rc = fetch(d_lweN, (size_t)count * (c->N + 1), lweN))) return rc;
-    if (ks && (rc = fetch(d_ks, (size_t)count * (c->n + 1), ks))) return rc;
+    if (lweN && (rc = words_from_device(c, lweN, d_lweN, (size_t)count * (c->N + 1), false))) return rc;
+    if (ks && (rc = words_from_device(c, ks, d_ks, (size_t)count * (c->n + 1), false))) return rc;
     hipFree(d_in); hipFree(d_lweN); hipFree(d_ks); hipFree(d_partial);
     return BCE_OK;
 }
@@ -1692,23 +1676,11 @@ int bce_debug_ntt(bce_ctx* c, uint64_t* polys, uint32_t count, int inverse) {
         if (polys[i] >= c->Q) return c->fail(BCE_ERR_ARG, "poly word not reduced mod Q");
     void* d = nullptr;
     HIP_TRY(c, hipMalloc(&d, words * c->wbytes));
-    std::vector<u32> tmp;
-    if (c->is64) {
-        HIP_TRY(c, hipMemcpy(d, polys, words * 8, hipMemcpyHostToDevice));
-    } else {
-        tmp.resize(words);
-        for (size_t i = 0; i < words; ++i) tmp[i] = (u32)polys[i];
-        HIP_TRY(c, hipMemcpy(d, tmp.data(), words * 4, hipMemcpyHostToDevice));
-    }
-    int rc = dev_ntt(c, d, count, inverse);
+    int rc = words_to_device(c, d, polys, words, c->is64);
+    if (!rc) rc = dev_ntt(c, d, count, inverse);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->is64) {
-        HIP_TRY(c, hipMemcpy(polys, d, words * 8, hipMemcpyDeviceToHost));
-    } else {
-        HIP_TRY(c, hipMemcpy(tmp.data(), d, words * 4, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < words; ++i) polys[i] = tmp[i];
-    }
+    if ((rc = words_from_device(c, polys, d, words, c->is64))) return rc;
     hipFree(d);
     return BCE_OK;
 }

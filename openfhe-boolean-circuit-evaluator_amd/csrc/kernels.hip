@@ -1576,9 +1576,71 @@ auto lat_kernel(const LatBuild& v, F of) -> decltype(of(std::integral_constant<s
     else return kLatBuilds[I] == v ? of(std::integral_constant<size_t, I>{}) : lat_kernel<I + 1>(v, of);
 }
 
+// ---- the one-wave-per-transform family: the builds that exist, as (log2 N, gadget digits, lazy forward transforms,
+// workgroups per CU the registers are budgeted for, AP).  The non-lazy bodies are built for two workgroups per CU; N = 2048
+// never has three (their LDS exceeds a CU's, kernel_class), so <11, 3, true, 3, *> does not exist.  The six <11, 4, ...> builds
+// cannot be launched either (the engine rejects four digits at N = 2048 for a 32-bit modulus) and are listed all the same:
+// without them the compiler emits k_blind_rotate<11, 3, false, 2, false> with the operands of four multiplications swapped
+// (profiles/br_class_isa_compare.txt), and this table came with a change that leaves every kernel's code as it was.
+struct WaveBuild { int logn, dg; bool lazy; int occ; bool ap; };
+constexpr bool operator==(const WaveBuild& a, const WaveBuild& b) {
+    return a.logn == b.logn && a.dg == b.dg && a.lazy == b.lazy && a.occ == b.occ && a.ap == b.ap;
+}
+constexpr WaveBuild kWaveBuilds[] = {
+    {9, 3, true, 3, false},  {9, 3, true, 2, false},  {9, 3, false, 2, false},  {9, 3, true, 3, true},  {9, 3, true, 2, true},  {9, 3, false, 2, true},
+    {9, 4, true, 3, false},  {9, 4, true, 2, false},  {9, 4, false, 2, false},  {9, 4, true, 3, true},  {9, 4, true, 2, true},  {9, 4, false, 2, true},
+    {10, 3, true, 3, false}, {10, 3, true, 2, false}, {10, 3, false, 2, false}, {10, 3, true, 3, true}, {10, 3, true, 2, true}, {10, 3, false, 2, true},
+    {10, 4, true, 3, false}, {10, 4, true, 2, false}, {10, 4, false, 2, false}, {10, 4, true, 3, true}, {10, 4, true, 2, true}, {10, 4, false, 2, true},
+    {11, 3, true, 2, false}, {11, 3, false, 2, false}, {11, 3, true, 2, true}, {11, 3, false, 2, true},
+    {11, 4, true, 3, false}, {11, 4, true, 2, false}, {11, 4, false, 2, false}, {11, 4, true, 3, true}, {11, 4, true, 2, true}, {11, 4, false, 2, true},
+};
+WaveBuild wave_variant(const DevParams& P) {
+    return {(int)P.logN, (int)P.dG, P.lazy != 0, (P.lazy && P.occupancy_target >= 3) ? 3 : 2, P.method_ap != 0};
+}
+using BrKernel = void (*)(DevParams, const bce_gate_desc*, u32, u32, u32*);
+// the kernel of the entry of kWaveBuilds that equals v; null if there is none
+template <size_t I = 0>
+BrKernel wave_kernel(const WaveBuild& v) {
+    if constexpr (I == std::size(kWaveBuilds)) return nullptr;
+    else {
+        constexpr WaveBuild b = kWaveBuilds[I];
+        return b == v ? k_blind_rotate<b.logn, b.dg, b.lazy, b.occ, b.ap> : wave_kernel<I + 1>(v);
+    }
+}
 size_t blind_rotate_lds_bytes(const DevParams& P) {
     const size_t N = P.N, NP = N + (N >> 6) * 4, R = 2 * P.dG;
     return (2 * N + (2 + R) * NP + ((P.n + 1 + 3) & ~3u)) * sizeof(u32);
+}
+
+// ---- the kernel-class rule (kernels.hpp): the 32-bit families here, the 64-bit ones in kernels64.hip ---------------------
+KernelClass kernel_class(const DevParams& P) {
+    // three workgroups of the one-wave-per-transform kernel per CU unless two were asked for (BCE_OCCUPANCY=2) or three do not
+    // fit (the field is set for every context; that family alone is compiled for it)
+    const u32 occupancy = (P.occupancy_target == 2 || 3 * blind_rotate_lds_bytes(P) > kLdsBytesPerCu) ? 2 : 3;
+    KernelClass k{};
+    if (P.is64) {
+        k = kernel_class64(P);
+        k.occupancy_target = occupancy;
+        return k;
+    }
+    k.occupancy_target = occupancy;
+    if (P.dG < 3 || P.dG > 4 || (P.logN == 11 && P.dG != 3)) k.error = kDigitCountError;
+    const bool ap = P.method_ap != 0;
+    // N = 1024, dG = 4 with the lazy bounds (STD128 class): the split-transform kernels, unless BCE_VARIANT=1 pins the other family
+    const bool split = P.variant != 1 && P.logN == 10 && P.dG == 4 && P.lazy;
+    k.family = split ? KernelFamily::SplitTransform : KernelFamily::WavePerTransform;
+    if (split) {
+        k.fold_build = std::any_of(std::begin(kLatBuilds), std::end(kLatBuilds), [ap](const LatBuild& b) { return b.ap == ap && b.fwd != Fwd::Rows; });
+        k.dag = fused_tail_fits(P);
+        k.wg_per_cu_lone = lat_variant(P, true).wps / 2;     // LatBuild::wps counts waves per SIMD; a workgroup brings two
+        k.wg_per_cu_full = lat_variant(P, false).wps / 2;
+        k.lds_bytes = blind_rotate_lat_lds_bytes(P, lat_variant(P, false));
+    } else {
+        k.wg_per_cu_lone = 1;
+        k.wg_per_cu_full = k.occupancy_target;
+        k.lds_bytes = blind_rotate_lds_bytes(P);
+    }
+    return k;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1636,11 +1698,6 @@ __global__ __launch_bounds__(V::T, V::WPS) void k_bootstrap_dag(const DevParams*
     });
 }
 
-bool dag_kernel_available(const DevParams& P) {
-    if (P.is64) return dag64_kernel_available(P);
-    return !P.is64 && P.variant != 1 && P.logN == 10 && P.dG == 4 && P.lazy && fused_tail_fits(P);
-}
-
 hipError_t launch_dag_rearm(const DagParams& D, hipStream_t s) {
     hipLaunchKernelGGL(k_dag_rearm, dim3(1024), dim3(256), 0, s, D);
     return hipGetLastError();
@@ -1657,51 +1714,29 @@ hipError_t launch_bootstrap_dag(const DevParams& P, const DevParams* d_P, const 
     });
     if (!k) return hipErrorInvalidValue;
     const size_t lds = blind_rotate_lat_lds_bytes(P, v) + kDagMailboxWords * 4;   // + the worker's mailbox in front
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, s, d_P, d_params);
-    return hipGetLastError();
+    return launch_kernel_lds(k, dim3(grid), dim3(512), lds, s, LaunchEvents{}, d_P, d_params);
 }
-
-
-namespace {
-using BrKernel = void (*)(DevParams, const bce_gate_desc*, u32, u32, u32*);
-template <int LOGN, int DG, bool AP>
-BrKernel pick_br(bool lazy, int occ) {
-    if (lazy) return occ >= 3 ? k_blind_rotate<LOGN, DG, true, 3, AP> : k_blind_rotate<LOGN, DG, true, 2, AP>;
-    return k_blind_rotate<LOGN, DG, false, 2, AP>;
-}
-template <int LOGN>
-BrKernel pick_br_dg(u32 dG, bool lazy, int occ, bool ap) {
-    // instantiated gadget sizes: every OpenFHE parameter set with Q < 2^28 has dG in {3, 4}
-    switch (dG) {
-        case 3: return ap ? pick_br<LOGN, 3, true>(lazy, occ) : pick_br<LOGN, 3, false>(lazy, occ);
-        case 4: return ap ? pick_br<LOGN, 4, true>(lazy, occ) : pick_br<LOGN, 4, false>(lazy, occ);
-        default: return nullptr;
-    }
-}
-}  // namespace
 
 hipError_t launch_blind_rotate(const DevParams& P, const bce_gate_desc* d, u32 n_desc, u32 instances, u32 slot_stride,
-                               u32* acc_out, hipStream_t s, int* kernel_id, u32* dbg_lweN, u32* dbg_ks, bool* tail_fused, LaunchEvents ev) {
-    if (kernel_id) *kernel_id = BCE_BR_WAVE_PER_TRANSFORM;
+                               void* acc_out, hipStream_t s, int* kernel_id, u32* dbg_lweN, u32* dbg_ks, bool* tail_fused, LaunchEvents ev) {
     if (tail_fused) *tail_fused = false;
-    const u32 R = 2 * P.dG;
-    const dim3 grid(n_desc * instances), block(64 * R);
-    const size_t lds = blind_rotate_lds_bytes(P);
-    const int occ = P.occupancy_target;
-    const bool ap = P.method_ap != 0;
-    BrKernel kern = nullptr;
-    if (P.fold && !(P.variant != 1 && P.logN == 10 && P.dG == 4 && P.lazy)) return hipErrorInvalidValue;  // folded key, no kernel for it
-    if (P.variant != 1 && P.logN == 10 && P.dG == 4 && P.lazy) {
-        // N = 1024, dG = 4 (STD128 class): the split-transform kernel, with the 256-register budget while the
-        // launch leaves every workgroup a CU of its own, else with the 128-register one (two per CU);
+    if (P.is64) {
+        if (kernel_id) *kernel_id = BCE_BR_WORD64;
+        return launch_blind_rotate64(P, d, n_desc, instances, slot_stride, static_cast<u64*>(acc_out), s, dbg_lweN, dbg_ks, tail_fused, ev);
+    }
+    if (kernel_id) *kernel_id = BCE_BR_WAVE_PER_TRANSFORM;
+    const KernelClass kc = kernel_class(P);
+    if (P.fold && !kc.fold_build) return hipErrorInvalidValue;  // folded key, no kernel for it
+    u32* const acc = static_cast<u32*>(acc_out);
+    const dim3 grid(n_desc * instances), block(128 * P.dG);
+    if (kc.family == KernelFamily::SplitTransform) {
+        // the split-transform kernel, with the 256-register budget while the launch leaves every workgroup a CU of its
+        // own, else with the 128-register one (two per CU);
         // measured against the one-wave-per-transform kernel over launch sizes 64..6144: tools/kernel_sweep.py
         using LatKernel = void (*)(DevParams, const bce_gate_desc*, u32, u32, u32*, u32*, u32*);
         const bool alone = (P.variant == 2) || (P.variant == 0 && grid.x <= P.cu_count);
         const bool x1 = alone && P.variant != 3;
         const LatBuild v = lat_variant(P, x1);   // a folded key's rows l >= 1 hold ek_l - B^l ek_0 (see the kernel's FOLD note)
-        const size_t lds_lat = blind_rotate_lat_lds_bytes(P, v);
         // saturated launches run the tail of EvalBinGate in the kernel's epilogue (fused_tail); a launch that leaves
         // CUs to themselves keeps the separate tail kernels, which spread one bootstrap's row gather over many CUs
         const bool fuse = !x1 && tail_fused && P.fuse_tail && fused_tail_fits(P);
@@ -1713,27 +1748,18 @@ hipError_t launch_blind_rotate(const DevParams& P, const bce_gate_desc* d, u32 n
         if (!lk) return hipErrorInvalidValue;
         if (kernel_id) *kernel_id = x1 ? BCE_BR_SPLIT_X1 : BCE_BR_SPLIT_X2;
         if (tail_fused) *tail_fused = fuse;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_lat);
-        if (e != hipSuccess) return e;
         DevParams Pl = P;
         if (x1 || grid.x <= 2 * P.cu_count) Pl.xcd_gate = nullptr;            // one round: every workgroup starts at once anyway
-        if (Pl.xcd_gate && (e = hipMemsetAsync(Pl.xcd_gate, 0, 16 * 32 * sizeof(u32), s)) != hipSuccess) return e;
-        if (ev.start || ev.stop) return launch_with_events(lk, grid, block, lds_lat, s, ev, Pl, d, n_desc, slot_stride, acc_out, fuse ? dbg_lweN : nullptr, fuse ? dbg_ks : nullptr);
-        hipLaunchKernelGGL(lk, grid, block, lds_lat, s, Pl, d, n_desc, slot_stride, acc_out, fuse ? dbg_lweN : nullptr, fuse ? dbg_ks : nullptr);
-        return hipGetLastError();
+        if (Pl.xcd_gate) {
+            const hipError_t e = hipMemsetAsync(Pl.xcd_gate, 0, 16 * 32 * sizeof(u32), s);
+            if (e != hipSuccess) return e;
+        }
+        return launch_kernel_lds(lk, grid, block, blind_rotate_lat_lds_bytes(P, v), s, ev, Pl, d, n_desc, slot_stride, acc,
+                                 fuse ? dbg_lweN : nullptr, fuse ? dbg_ks : nullptr);
     }
-    switch (P.logN) {
-        case 9: kern = pick_br_dg<9>(P.dG, P.lazy != 0, occ, ap); break;
-        case 10: kern = pick_br_dg<10>(P.dG, P.lazy != 0, occ, ap); break;
-        case 11: kern = (P.dG == 3) ? pick_br_dg<11>(P.dG, P.lazy != 0, 2, ap) : nullptr; break;
-        default: break;
-    }
+    const BrKernel kern = wave_kernel(wave_variant(P));
     if (!kern) return hipErrorInvalidValue;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (ev.start || ev.stop) return launch_with_events(kern, grid, block, lds, s, ev, P, d, n_desc, slot_stride, acc_out);
-    hipLaunchKernelGGL(kern, grid, block, lds, s, P, d, n_desc, slot_stride, acc_out);
-    return hipGetLastError();
+    return launch_kernel_lds(kern, grid, block, kc.lds_bytes, s, ev, P, d, n_desc, slot_stride, acc);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1901,11 +1927,7 @@ hipError_t launch_tail(const DevParams& P, const bce_gate_desc* d, u32 n_desc, u
     const size_t lds = ((LR + 3) & ~(size_t)3) * sizeof(u32) + red_words * sizeof(u64);
     const LaunchEvents first{ev.start, nullptr}, last{nullptr, ev.stop};
     // the gather carries the start timestamp, the finish the stop (plain launches when none was asked for)
-    auto go = [&](auto kern, dim3 g, size_t l, LaunchEvents e, auto... args) -> hipError_t {
-        if (e.start || e.stop) return launch_with_events(kern, g, block, l, s, e, args...);
-        hipLaunchKernelGGL(kern, g, block, l, s, args...);
-        return hipGetLastError();
-    };
+    auto go = [&](auto kern, dim3 g, size_t l, LaunchEvents e, auto... args) { return launch_kernel(kern, g, block, l, s, e, args...); };
     hipError_t rc;
     if (P.is64) {
         const u64* a = static_cast<const u64*>(acc_in);
@@ -1997,8 +2019,9 @@ __global__ __launch_bounds__(256) void k_ntt_batch(DevParams P, u32* __restrict_
     }
 }
 
-hipError_t launch_ntt_batch(const DevParams& P, u32* polys, u32 count, int inverse, hipStream_t s) {
+hipError_t launch_ntt_batch(const DevParams& P, void* polys, u32 count, int inverse, hipStream_t s) {
     if (count == 0) return hipSuccess;
+    if (P.is64) return launch_ntt_batch64(P, static_cast<u64*>(polys), count, inverse, s);
     const size_t N = P.N, NP = N + (N >> 6) * 4;
     const u32 W = 4;
     const size_t lds = (2 * N + W * NP) * sizeof(u32);
@@ -2011,7 +2034,7 @@ hipError_t launch_ntt_batch(const DevParams& P, u32* polys, u32 count, int inver
         case 11: kern = k_ntt_batch<11>; break;
         default: return hipErrorInvalidValue;
     }
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * W), lds, s, P, polys, count, inverse);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * W), lds, s, P, static_cast<u32*>(polys), count, inverse);
     return hipGetLastError();
 }
 
@@ -2025,10 +2048,11 @@ __global__ void k_pointwise_mac(DevParams P, u32* __restrict__ b, const u32* __r
     }
 }
 
-hipError_t launch_pointwise_mac(const DevParams& P, u32* b, const u32* a, const u32* z, u32 count, u32 b_step,
+hipError_t launch_pointwise_mac(const DevParams& P, void* b, const void* a, const void* z, u32 count, u32 b_step,
                                 hipStream_t s) {
     if (count == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_pointwise_mac, dim3(2048), dim3(256), 0, s, P, b, a, z, count, b_step);
+    if (P.is64) return launch_pointwise_mac64(P, static_cast<u64*>(b), static_cast<const u64*>(a), static_cast<const u64*>(z), count, b_step, s);
+    hipLaunchKernelGGL(k_pointwise_mac, dim3(2048), dim3(256), 0, s, P, static_cast<u32*>(b), static_cast<const u32*>(a), static_cast<const u32*>(z), count, b_step);
     return hipGetLastError();
 }
 

@@ -88,8 +88,31 @@ struct DevParams {
     const u32* fwd_mfma_tab;   // [4 quarters][4 tiles][64 lanes][4 words]: A operands, or null
 };
 
-// LDS bytes the blind-rotation kernel needs for these parameters
-size_t blind_rotate_lds_bytes(const DevParams& P);
+// ---- the kernel-class rule: which blind-rotation family a context runs, and everything that follows from it -----------
+// The one place that knows it.  The 32-bit part (shape rule of the split-transform family, read off kLatBuilds) lives in
+// kernels.hip, the 64-bit part (shape rule of the integer / fp64 families, read off kWdBuilds) in kernels64.hip.
+constexpr size_t kLdsBytesPerCu = 160 * 1024;
+enum class KernelFamily {
+    WavePerTransform,   // k_blind_rotate (kernels.hip): one wave per transform, every 32-bit shape the split family does not take
+    SplitTransform,     // k_blind_rotate_lat / k_bootstrap_dag (kernels.hip): N = 1024, four gadget digits, lazy bounds hold
+    Int64,              // w64::k_blind_rotate64 (kernels64.hip), with its narrow build (four digits, N >= 1024, Q < 2^31)
+    Fp64,               // wd::k_blind_rotate64d / k_bootstrap_dag64 (kernels64.hip): Q < 2^39 in doubles
+};
+struct KernelClass {
+    KernelFamily family;
+    const char* error;        // null, or why no kernel exists for this shape (what bce_ctx_create* reports; BCE_ERR_UNSUPPORTED)
+    const char* lds_error;    // null, or why the family's LDS layout does not fit a CU for this shape (same status)
+    bool fold_build;          // a build that reads the folded key exists for this shape and method (does not look at P.fold)
+    bool dag;                 // a persistent dependency-driven build (launch_bootstrap_dag) exists for P as it stands
+    u32 fp64;                 // P.fp64 as granted: the request, and the shape has a doubles kernel
+    u32 occupancy_target;     // P.occupancy_target as granted: 3 unless 2 was asked for or three workgroups' LDS exceed a CU's
+    u32 wg_per_cu_lone, wg_per_cu_full;   // workgroups a CU holds in a launch of <= cu_count workgroups / in a saturated one
+    size_t lds_bytes;         // dynamic LDS of one workgroup (of the saturated launch's build where the builds differ)
+};
+// Reads the shape (is64, Q64, logN, dG, n, method_ap, lazy, variant) and two REQUESTS the engine presets: P.fp64 (doubles
+// wanted) and P.occupancy_target (2 or 3 wanted); the engine stores the granted values back.  `error` needs the shape
+// fields alone; fold_build does not read P.fold; `dag` and lds_bytes describe P as it stands (fold, fwd_mfma, fuse_tail).
+KernelClass kernel_class(const DevParams& P);
 
 // ---- dependency-driven evaluation of a whole bootstrap DAG by ONE persistent launch (k_bootstrap_dag) ----------------
 // Replaces the manager <-> executor loop of the reference (src/circuit.cpp:575-683 ready-gate rule, :698-710 parallel
@@ -141,10 +164,7 @@ hipError_t launch_dag_rearm(const DagParams& D, hipStream_t s);
 // it needs them instead of holding kernel arguments in registers across its loop)
 hipError_t launch_bootstrap_dag(const DevParams& P, const DevParams* d_P, const DagParams* d_params, int wps, u32 grid,
                                 hipStream_t s);
-bool dag_kernel_available(const DevParams& P);
-// the config-5 class (kernels64.hip): N = 2048, Q < 2^39 in doubles, AP, folded key, fused tail; 1,024 threads, one workgroup per CU
-bool dag64_kernel_available(const DevParams& P);
-hipError_t launch_bootstrap_dag64(const DevParams& P, const DevParams* d_P, const DagParams* d_params, u32 grid, hipStream_t s);
+inline bool dag_kernel_available(const DevParams& P) { return kernel_class(P).dag; }
 
 // Timestamps of a launch without event packets of their own in the queue: start / stop are attached to the kernel's
 // dispatch (hipExtLaunchKernel) -- what hipEventRecord before and after a kernel costs on the device timeline (5-10 us of
@@ -162,14 +182,27 @@ inline hipError_t launch_with_events(void (*kern)(KA...), dim3 grid, dim3 block,
     std::apply([&](auto&... a) { size_t i = 0; ((ptrs[i++] = (void*)&a), ...); }, held);
     return hipExtLaunchKernel(reinterpret_cast<const void*>(kern), grid, block, ptrs, lds, s, ev.start, ev.stop, 0);
 }
+// kern(args...) as a plain launch, or through launch_with_events when a timestamp is attached
+template <typename... KA, typename... A>
+inline hipError_t launch_kernel(void (*kern)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t s, LaunchEvents ev, A... args) {
+    if (ev.start || ev.stop) return launch_with_events(kern, grid, block, lds, s, ev, args...);
+    hipLaunchKernelGGL(kern, grid, block, lds, s, static_cast<KA>(args)...);
+    return hipGetLastError();
+}
+// The launch idiom of the kernels whose dynamic LDS may exceed the default limit: opt in to `lds` bytes, then launch_kernel
+template <typename... KA, typename... A>
+inline hipError_t launch_kernel_lds(void (*kern)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t s, LaunchEvents ev, A... args) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    return e != hipSuccess ? e : launch_kernel(kern, grid, block, lds, s, ev, args...);
+}
 
-// acc_out: u32 [n_boot][2][N], COEFFICIENT domain, values in [0, Q)
-// *kernel_id (optional) receives the enum bce_br_kernel value of the kernel that was launched
+// acc_out: [n_boot][2][N] words of the context's width (u32, or u64 when P.is64), COEFFICIENT domain, values in [0, Q)
+// *kernel_id (optional) receives the enum bce_br_kernel value of the kernel that was launched, for every family
 // *tail_fused (optional) is set when the launched kernel also ran the tail of EvalBinGate (extract, ModSwitch,
 // KeySwitch, ModSwitch -> pool[out]) in its epilogue; the caller then skips launch_tail().  dbg_lweN / dbg_ks as
 // for launch_tail (used only when the tail is fused).
 hipError_t launch_blind_rotate(const DevParams& P, const bce_gate_desc* d_descs, u32 n_desc, u32 instances,
-                               u32 slot_stride, u32* acc_out, hipStream_t s, int* kernel_id = nullptr,
+                               u32 slot_stride, void* acc_out, hipStream_t s, int* kernel_id = nullptr,
                                u32* dbg_lweN = nullptr, u32* dbg_ks = nullptr, bool* tail_fused = nullptr, LaunchEvents ev = {});
 
 // extract + ModSwitch(Q->qKS) + KeySwitch + ModSwitch(qKS->q) -> pool[out]
@@ -180,18 +213,8 @@ hipError_t launch_tail(const DevParams& P, const bce_gate_desc* d_descs, u32 n_d
                        const void* acc_in /* u32 or u64 words by P.is64 */, u64* partial, u32* dbg_lweN, u32* dbg_ks,
                        hipStream_t s, LaunchEvents ev = {});   // ev.start on the first kernel, ev.stop on the last
 
-// 64-bit-modulus counterparts (kernels64.hip)
-size_t blind_rotate64_lds_bytes(const DevParams& P);
-bool blind_rotate64_narrow(const DevParams& P);   // integer 64-bit kernel with 32-bit digit rows (four gadget digits, N >= 1024, Q < 2^31)
-// *tail_fused (optional) is set when the launched kernel also ran the tail (then dbg_lweN / dbg_ks are its debug outputs)
-hipError_t launch_blind_rotate64(const DevParams& P, const bce_gate_desc* d_descs, u32 n_desc, u32 instances,
-                                 u32 slot_stride, u64* acc_out, hipStream_t s, u32* dbg_lweN = nullptr, u32* dbg_ks = nullptr,
-                                 bool* tail_fused = nullptr, LaunchEvents ev = {});
-hipError_t launch_ntt_batch64(const DevParams& P, u64* polys, u32 count, int inverse, hipStream_t s);
-// key words u64 <-> IEEE double in place (layout of the double-precision formulation)
+// key words u64 <-> IEEE double in place (layout of the double-precision formulation, kernels64.hip)
 hipError_t launch_words_u64_f64(u64* words, size_t count, int to_double, hipStream_t s);
-hipError_t launch_pointwise_mac64(const DevParams& P, u64* b, const u64* a, const u64* z, u32 count, u32 b_step,
-                                  hipStream_t s);
 
 // EvalNOT / COPY over pool slots
 hipError_t launch_lwe_unary(const DevParams& P, const bce_gate_desc* d_descs, u32 n_desc, u32 instances,
@@ -201,17 +224,27 @@ hipError_t launch_lwe_unary(const DevParams& P, const bce_gate_desc* d_descs, u3
 hipError_t launch_pool_pack(const DevParams& P, const bce_gate_desc* d_descs, u32 count, u32* buf, int to_pool,
                             hipStream_t s);
 
-// in-place negacyclic NTT of `count` polys, u32 [count][N] in global memory
-hipError_t launch_ntt_batch(const DevParams& P, u32* polys, u32 count, int inverse, hipStream_t s);
+// in-place negacyclic NTT of `count` polys, [count][N] words of the context's width in global memory
+hipError_t launch_ntt_batch(const DevParams& P, void* polys, u32 count, int inverse, hipStream_t s);
 
 // In place on `rgsw` RGSW ciphertexts [R = 2 dG rows][2][N] (evaluation form, integer words: u32, or u64 when P.is64):
 // dir = +1: row(2l + c) -= B^l row(c) for l = 1..dG-1 (the layout the FOLD kernels read); dir = -1 undoes it.
 hipError_t launch_fold_gadget(const DevParams& P, void* bsk, u64 rgsw, int dir, hipStream_t s);
 
-// b[p*b_step][k] += a[p][k] * z[k] mod Q for count polys (key generation)
-hipError_t launch_pointwise_mac(const DevParams& P, u32* b, const u32* a, const u32* z, u32 count, u32 b_step,
+// b[p*b_step][k] += a[p][k] * z[k] mod Q for count polys (key generation); words of the context's width
+hipError_t launch_pointwise_mac(const DevParams& P, void* b, const void* a, const void* z, u32 count, u32 b_step,
                                 hipStream_t s);
 
 // host-side decrypt helper kernels are not needed: decryption happens on the host (needs sk)
+
+// ---- internal to the kernel files: what kernels.hip dispatches to for P.is64 (kernels64.hip) ------------------------
+constexpr const char* kDigitCountError = "gadget digit count must be 3 or 4 (N = 2048: 3, or 4 with a ring modulus of 28..30 bits)";
+KernelClass kernel_class64(const DevParams& P);   // everything but occupancy_target
+hipError_t launch_bootstrap_dag64(const DevParams& P, const DevParams* d_P, const DagParams* d_params, u32 grid, hipStream_t s);
+// *tail_fused (optional) is set when the launched kernel also ran the tail (then dbg_lweN / dbg_ks are its debug outputs)
+hipError_t launch_blind_rotate64(const DevParams& P, const bce_gate_desc* d_descs, u32 n_desc, u32 instances, u32 slot_stride,
+                                 u64* acc_out, hipStream_t s, u32* dbg_lweN, u32* dbg_ks, bool* tail_fused, LaunchEvents ev);
+hipError_t launch_ntt_batch64(const DevParams& P, u64* polys, u32 count, int inverse, hipStream_t s);
+hipError_t launch_pointwise_mac64(const DevParams& P, u64* b, const u64* a, const u64* z, u32 count, u32 b_step, hipStream_t s);
 
 }  // namespace bce

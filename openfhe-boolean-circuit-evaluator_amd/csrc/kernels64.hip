@@ -10,6 +10,7 @@
 // (2 + 2*dG) padded polynomials of N = 2048 u64 words already take 139 KiB of the 160 KiB LDS.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <iterator>
 #include <utility>
 
@@ -231,7 +232,7 @@ __device__ __forceinline__ u32 gate_const(u32 op, u32 q) {
     }
 }
 
-// LDS of one workgroup of k_blind_rotate64, in 64-bit words: used by the kernel and by blind_rotate64_lds_bytes.
+// LDS of one workgroup of k_blind_rotate64, in 64-bit words: used by the kernel and by kernel_class64.
 // narrow: the R digit rows are 32-bit words (Q < 2^31: a digit + Q and every normalised transform value fit), the inverse
 // transforms get a scratch of their own -- what lets N = 2048 with FOUR gadget digits (STD256, STD256_OPT: 29-bit Q, base 2^8)
 // into the 160 KiB of LDS: 2 x 17 KiB accumulator + 8 x 8.5 KiB digit rows + 2 x 17 KiB scratch instead of 10 x 17 KiB.
@@ -248,7 +249,7 @@ struct W64Lds {
     constexpr size_t bytes(u32 n) const { return av() * sizeof(u64) + av_words(n) * sizeof(u32); }
 };
 
-// One build per (LOGN, DG, AP).  NARROW (see W64Lds): four gadget digits on N >= 1024, the contexts blind_rotate64_narrow accepts.
+// One build per (LOGN, DG, AP).  NARROW (see W64Lds): four gadget digits on N >= 1024, the build that needs Q < 2^31 (blind_rotate64_kernel).
 // NBUF / NPRE: depth of the key-row software pipeline (items in flight / requested before the transforms): the deepest that
 // compile without scratch at N = 2048 (GINX items carry two keys' rows), one item less in the narrow N = 2048 build.
 template <int LOGN, int DG, bool AP>
@@ -1081,7 +1082,7 @@ struct WdVariant {
     static_assert(!FUSE || W16, "fused tail: 16-wave body");
 };
 
-// LDS of one workgroup of bootstrap64d, in doubles: used by the kernels, their launchers, blind_rotate64_lds_bytes and
+// LDS of one workgroup of bootstrap64d, in doubles: used by the kernels, their launchers, kernel_class64 and
 // fused_tail64_fits
 struct WdLds {
     u32 NP, R;
@@ -1522,12 +1523,8 @@ hipError_t launch_words_u64_f64(u64* words, size_t count, int to_double, hipStre
     return hipGetLastError();
 }
 
-// the narrow build of the integer kernel (32-bit digit rows): four gadget digits on N >= 1024, Q < 2^31
-bool blind_rotate64_narrow(const DevParams& P) {
-    return P.is64 && !P.fp64 && P.dG == 4 && P.logN >= 10 && P.Q64 < (1ull << 31);
-}
-
-namespace {
+// the narrow build of the integer kernel (32-bit digit rows, NARROW in k_blind_rotate64): four gadget digits on N >= 1024; needs Q < 2^31
+constexpr bool w64_narrow(u32 logn, u32 dg) { return dg == 4 && logn >= 10; }
 using BrKernel64 = void (*)(DevParams, const bce_gate_desc*, u32, u32, u64*, u32*, u32*);
 template <int LOGN, int DG>
 BrKernel64 pick_br64(bool ap) { return ap ? w64::k_blind_rotate64<LOGN, DG, true> : w64::k_blind_rotate64<LOGN, DG, false>; }
@@ -1538,20 +1535,39 @@ BrKernel64 blind_rotate64_kernel(const DevParams& P) {
     if (P.fold) return nullptr;
     if (P.dG == 3) return P.logN == 9 ? pick_br64<9, 3>(ap) : P.logN == 10 ? pick_br64<10, 3>(ap) : P.logN == 11 ? pick_br64<11, 3>(ap) : nullptr;
     if (P.dG == 4 && P.logN == 9) return pick_br64<9, 4>(ap);
-    if (blind_rotate64_narrow(P)) return P.logN == 11 ? pick_br64<11, 4>(ap) : pick_br64<10, 4>(ap);
+    if (w64_narrow(P.logN, P.dG) && P.Q64 < (1ull << 31)) return P.logN == 11 ? pick_br64<11, 4>(ap) : pick_br64<10, 4>(ap);
     return nullptr;
 }
-}  // namespace
 
-size_t blind_rotate64_lds_bytes(const DevParams& P) {
-    if (P.fp64) return wd::WdLds(P.logN, P.dG, wd::wd_variant(P, false).body).bytes(P.n);
-    return w64::W64Lds(P.logN, P.dG, blind_rotate64_narrow(P)).bytes(P.n);
+// the 64-bit half of the kernel-class rule (kernels.hpp)
+KernelClass kernel_class64(const DevParams& P) {
+    KernelClass k{};
+    const bool ap = P.method_ap != 0;
+    DevParams plain = P;
+    plain.fold = 0;
+    const wd::WdBuild v = wd::wd_variant(plain, false);
+    const auto wd_has = [&](bool fold) {
+        return std::any_of(std::begin(wd::kWdBuilds), std::end(wd::kWdBuilds), [&](const wd::WdBuild& b) {
+            return b.logn == P.logN && b.dg == P.dG && b.ap == ap && b.body == v.body && b.fold == fold;
+        });
+    };
+    k.fp64 = (P.fp64 && wd_has(false)) ? 1 : 0;      // the narrow shapes have no doubles kernel: their key words stay integers
+    k.family = k.fp64 ? KernelFamily::Fp64 : KernelFamily::Int64;
+    if (!k.fp64 && !blind_rotate64_kernel(plain))
+        k.error = (P.dG < 3 || P.dG > 4 || P.logN == 11) ? kDigitCountError : "64-bit path: four gadget digits need N = 512 or a ring modulus below 2^31";
+    k.fold_build = k.fp64 && wd_has(true);
+    k.lds_bytes = k.fp64 ? wd::WdLds(P.logN, P.dG, v.body).bytes(P.n) : w64::W64Lds(P.logN, P.dG, w64_narrow(P.logN, P.dG)).bytes(P.n);
+    // includes the 16 KiB twiddle mirror of the split bodies (n <= ~1020 there)
+    if (k.lds_bytes > kLdsBytesPerCu) k.lds_error = "64-bit path: polynomials (+ twiddle mirror) do not fit the 160 KiB LDS";
+    // the config-5 class: N = 2048, Q < 2^39 in doubles, AP, folded key, fused tail; 1,024 threads
+    k.dag = k.fp64 && wd::wd_variant(P, true).fuse;
+    k.wg_per_cu_lone = 1;
+    k.wg_per_cu_full = (u32)std::max<size_t>(1, kLdsBytesPerCu / k.lds_bytes);   // LDS-bound residency (N = 2048: one workgroup per CU)
+    return k;
 }
 
-bool dag64_kernel_available(const DevParams& P) { return P.is64 && P.fp64 && wd::wd_variant(P, true).fuse; }
-
 hipError_t launch_bootstrap_dag64(const DevParams& P, const DevParams* d_P, const DagParams* d_params, u32 grid, hipStream_t s) {
-    if (!dag64_kernel_available(P)) return hipErrorInvalidValue;
+    if (!kernel_class64(P).dag) return hipErrorInvalidValue;
     using DagKernel = void (*)(const DevParams*, const DagParams*);
     const wd::WdBuild v = wd::wd_variant(P, true);
     const DagKernel k = wd::wd_kernel(v, [](auto i) -> DagKernel {
@@ -1559,11 +1575,8 @@ hipError_t launch_bootstrap_dag64(const DevParams& P, const DevParams* d_P, cons
         else return nullptr;
     });
     if (!k) return hipErrorInvalidValue;
-    const size_t lds = wd::WdLds::mbox * sizeof(double) + blind_rotate64_lds_bytes(P);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(wd::wd_threads(v.body, v.dg)), lds, s, d_P, d_params);
-    return hipGetLastError();
+    const size_t lds = wd::WdLds::mbox * sizeof(double) + kernel_class64(P).lds_bytes;
+    return launch_kernel_lds(k, dim3(grid), dim3(wd::wd_threads(v.body, v.dg)), lds, s, LaunchEvents{}, d_P, d_params);
 }
 
 hipError_t launch_blind_rotate64(const DevParams& P, const bce_gate_desc* d, u32 n_desc, u32 instances, u32 slot_stride,
@@ -1581,15 +1594,8 @@ hipError_t launch_blind_rotate64(const DevParams& P, const bce_gate_desc* d, u32
     }
     if (tail_fused) *tail_fused = fused;
     if (!kern) return hipErrorInvalidValue;
-    const size_t lds = blind_rotate64_lds_bytes(P);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (ev.start || ev.stop)
-        return launch_with_events(kern, dim3(n_desc * instances), dim3(threads), lds, s, ev, P, d, n_desc, slot_stride, acc_out,
-                                  fused ? dbg_lweN : nullptr, fused ? dbg_ks : nullptr);
-    hipLaunchKernelGGL(kern, dim3(n_desc * instances), dim3(threads), lds, s, P, d, n_desc, slot_stride, acc_out,
-                       fused ? dbg_lweN : nullptr, fused ? dbg_ks : nullptr);
-    return hipGetLastError();
+    return launch_kernel_lds(kern, dim3(n_desc * instances), dim3(threads), kernel_class64(P).lds_bytes, s, ev, P, d, n_desc, slot_stride, acc_out,
+                             fused ? dbg_lweN : nullptr, fused ? dbg_ks : nullptr);
 }
 
 hipError_t launch_ntt_batch64(const DevParams& P, u64* polys, u32 count, int inverse, hipStream_t s) {
@@ -1606,10 +1612,7 @@ hipError_t launch_ntt_batch64(const DevParams& P, u64* polys, u32 count, int inv
         case 11: kern = w64::k_ntt_batch64<11>; break;
         default: return hipErrorInvalidValue;
     }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * W), lds, s, P, polys, count, inverse);
-    return hipGetLastError();
+    return launch_kernel_lds(kern, dim3(blocks), dim3(64 * W), lds, s, LaunchEvents{}, P, polys, count, inverse);
 }
 
 hipError_t launch_pointwise_mac64(const DevParams& P, u64* b, const u64* a, const u64* z, u32 count, u32 b_step,

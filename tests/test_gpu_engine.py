@@ -792,3 +792,56 @@ def test_scattered_slots_read_and_decrypt_like_dense_ones(toy, bce):
     # a slot outside the pool is refused on both paths
     with pytest.raises(bce.BceError):
         c.lwe_read(np.array([0, stride * K + 10_000_000], dtype=np.uint32))
+
+
+# what launch_capacity() returned on an MI355X (256 compute units) for the four contexts below before the kernel-class
+# rule (csrc/kernels.hpp, kernel_class) replaced the per-family guesses of bce_launch_capacity: (lone, saturated) workgroups
+# (profiles/br_class_parent_capacity.log: this test run against the library of commit 6a65366)
+_CAPACITY_BEFORE_THE_RULE = {"toy": (256, 768), "std128": (256, 512), "std128_variant3": (256, 512), "q64_fp64_3_512": (256, 1024)}
+
+
+def test_every_family_reports_its_kernel_and_capacity(toy, std128, bce, orc, monkeypatch):
+    """One gate on a context of every kernel family: timing()["by_kernel"] must count the launch in that family's bucket
+    (and in no other), and launch_capacity() -- what the circuit scheduler sizes its frontiers with -- must be the pair
+    the engine reported before the families were described by one rule."""
+    WAVE, SPLIT_X1, SPLIT_X2, WORD64 = range(4)
+
+    def one_gate(o, c):
+        ca, cb = o.encrypt(1, 9000), o.encrypt(1, 9001)
+        c.pool_reserve(3)
+        c.lwe_write(np.arange(2, dtype=np.uint32), np.stack([ca, cb]))
+        before = [k["launches"] for k in c.timing()["by_kernel"]]
+        c.EvalGates(bce.make_descs([(bce.NAND, 0, 1, 2)]))
+        after = [k["launches"] for k in c.timing()["by_kernel"]]
+        assert np.array_equal(c.lwe_read(np.array([2], dtype=np.uint32))[0], o.eval_bingate(bce.NAND, ca, cb))
+        return [a - b for a, b in zip(after, before)]
+
+    def only(kernel):
+        return [1 if k == kernel else 0 for k in range(bce.BR_KERNELS)]
+
+    seen = {}
+    o, c = toy                                     # N = 512, three digits: one wave per transform
+    assert (c.N, c.params["dG"]) == (512, 3)
+    seen["toy"] = (one_gate(o, c), c.launch_capacity(), WAVE)
+    o, c = std128                                  # one workgroup: the split kernel with a CU to itself
+    seen["std128"] = (one_gate(o, c), c.launch_capacity(), SPLIT_X1)
+    monkeypatch.setenv("BCE_VARIANT", "3")         # pinned to the two-workgroups-per-CU build
+    c3 = bce.BinFHEContext(bce.STD128_OPT, bce.GINX)
+    c3.import_keys(o.sk(), o.z(), o.bsk(), o.ksk())
+    seen["std128_variant3"] = (one_gate(o, c3), c3.launch_capacity(), SPLIT_X2)
+    c3.close()
+    monkeypatch.delenv("BCE_VARIANT")
+    monkeypatch.setenv("BCE_FP64", "1")            # the context of test_q64_custom_context_bit_exact_stages[GINX-fp64-3-512]
+    params = _custom64(orc, 13, 512)
+    o64 = orc.Oracle(method=orc.GINX, custom=params)
+    o64.keygen(31337)
+    c64 = bce.BinFHEContext(method=bce.GINX, custom=params)
+    c64.import_keys(o64.sk(), o64.z(), o64.bsk(), o64.ksk())
+    seen["q64_fp64_3_512"] = (one_gate(o64, c64), c64.launch_capacity(), WORD64)
+    c64.close()
+    o64.close()
+    for name, (delta, capacity, kernel) in seen.items():
+        print("%s: launches by kernel %s, launch_capacity %s" % (name, delta, capacity))
+    for name, (delta, capacity, kernel) in seen.items():
+        assert delta == only(kernel), name
+        assert capacity == _CAPACITY_BEFORE_THE_RULE[name], name

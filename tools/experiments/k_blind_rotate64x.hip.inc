@@ -1,6 +1,6 @@
 // ARCHIVED EXPERIMENT (round 2) -- not compiled into the library.
 // An all-16-wave re-cut of the STD192/AP blind rotation (drop into namespace bce::wd of csrc/kernels64.hip, launch with
-// 1,024 threads and the LDS size of blind_rotate64_lds_bytes).  Bit-exact at every stage
+// 1,024 threads and the LDS size of kernel_class64().lds_bytes).  Bit-exact at every stage
 // (tests/test_gpu_engine.py::test_q64_custom_context_bit_exact_stages[...2048...AP] passed with it), and 17 % fewer
 // shader cycles per step than the 8-wave kernel (27.6 k vs 33.3 k: inverse passes + digits 11.3 k -> 6.8 k, forward
 // phase 13.2 k -> 7.5 k once the digit rows were re-padded and the twiddle blocks m >= 128 transposed), but only 5 %

@@ -166,7 +166,7 @@ __global__ __launch_bounds__(1024) void k_blind_rotate_lat16(DevParams P, const 
 }
 
 
-// ---- launcher fragment (launch_blind_rotate, before the `if (P.fold)` kernel choice) ----
+// ---- launcher fragment (launch_blind_rotate, in front of the split-transform branch) ----
 /*
         // a folded GINX key and a CU per workgroup: the 16-wave build (BCE_VARIANT=2 keeps the 8-wave one, 4 forces this one)
         const bool w16 = P.fold && !ap && ((x1 && P.variant != 2) || P.variant == 4);
