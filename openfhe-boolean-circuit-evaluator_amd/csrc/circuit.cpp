@@ -30,12 +30,9 @@ const char* op_name(GateEnum op) {
         default: return "?";
     }
 }
-uint32_t gate_weight(GateEnum op, bool xor_fast = false) {  // bootstraps per gate (src/gate.cpp:133,172,200-202)
-    switch (op) {
-        case GateEnum::AND: case GateEnum::OR: return 1;
-        case GateEnum::XOR: return xor_fast ? 1 : 3;
-        default: return 0;
-    }
+sched::Op sched_op(GateEnum op) {
+    return op == GateEnum::NOT ? sched::Op::NOT : op == GateEnum::AND ? sched::Op::AND : op == GateEnum::OR ? sched::Op::OR
+         : op == GateEnum::XOR ? sched::Op::XOR : sched::Op::OUTPUT;
 }
 }  // namespace
 
@@ -123,10 +120,10 @@ void Gate::Evaluate(const GateEvalParams& gep) {
             } else if (en) {
                 // (a AND !b) OR (!a AND b), src/gate.cpp:198-202; the NOTs are folded into the prep
                 if (tmp.size() < 2) throw std::runtime_error("gate " + name + ": XOR needs two scratch slots");
-                bce_gate_desc a[2] = {{BCE_AND, encin[0], encin[1], tmp[0], 0, 1}, {BCE_AND, encin[0], encin[1], tmp[1], 1, 0}};
-                gate_ck(gep, bce_eval_gates(gep.cc, 2, a), name);
-                bce_gate_desc o{BCE_OR, tmp[0], tmp[1], enc_dst(), 0, 0};
-                gate_ck(gep, bce_eval_gates(gep.cc, 1, &o), name);
+                bce_gate_desc x[3];
+                sched::xor_lower({0, encin[0], encin[1], enc_dst(), 0, 0}, tmp[0], tmp[1], x);
+                gate_ck(gep, bce_eval_gates(gep.cc, 2, x), name);
+                gate_ck(gep, bce_eval_gates(gep.cc, 1, &x[2]), name);
                 if (vf) verify_fix(gep, "XOR", encout[0], plainout[0], true, name);
             }
             break;
@@ -266,7 +263,6 @@ bool Circuit::ReadFile(const std::string& inFname) {
             // no-op
         }
     }
-    n_outputs = 1;
     n_output_bits.assign(1, any_out ? max_out + 1 : 0);
     {
         unsigned tot = 0;
@@ -341,7 +337,7 @@ bool Circuit::ReadBristol(const std::string& path, bool new_flag) {
         if (w < 0) throw std::runtime_error("ReadBristol: output node never driven");
         allGates.push_back(GateRec{GateEnum::OUTPUT, 1, {w, -1}, -1, (int)o, "OUTPUT:" + std::to_string(gateNo++)});
     }
-    n_outputs = 1;   // internally ONE concatenated bus (bit indices run over all output values); getOutputs() splits it
+    // internally ONE concatenated bus (bit indices run over all output values); getOutputs() splits it
     n_output_bits.assign(1, v.n_out1_bits);
     finalizeNetlist();
     return true;
@@ -358,7 +354,6 @@ void Circuit::finalizeNetlist() {
     for (size_t gi = 0; gi < G; ++gi) for (int k = 0; k < allGates[gi].nin; ++k) fan_gate_[pos[allGates[gi].in[k]]++] = (uint32_t)gi;
 
     levels_.clear();
-    gate_level_.assign(G, -1);
     std::vector<int> ready(G, 0), active;
     for (const auto& l : inputGates) active.push_back(l.wire);
     for (const auto& k : constWires_) active.push_back(k.wire);
@@ -374,7 +369,6 @@ void Circuit::finalizeNetlist() {
         std::sort(L.gates.begin(), L.gates.end());
         active.clear();
         for (int gi : L.gates) {
-            gate_level_[gi] = (int)levels_.size();
             if (allGates[gi].op == GateEnum::XOR) ++L.n_xor;
             if (allGates[gi].out >= 0) active.push_back(allGates[gi].out);
         }
@@ -383,6 +377,14 @@ void Circuit::finalizeNetlist() {
     }
     base_stride_ = stride_ = (uint32_t)W + 2 * max_level_xor_;
     inputs_set_ = false;
+    // the same netlist as the schedule module reads it: level order, OUTPUT wires in file order
+    net_ = sched::Dag{(uint32_t)W, {}, {0}, {}};
+    for (const auto& L : levels_) {
+        for (int gi : L.gates) net_.gates.push_back({sched_op(allGates[gi].op), allGates[gi].in[0], allGates[gi].nin > 1 ? allGates[gi].in[1] : -1, allGates[gi].out});
+        net_.level_off.push_back((uint32_t)net_.gates.size());
+    }
+    for (const auto& g : allGates) if (g.op == GateEnum::OUTPUT) net_.outputs.push_back(g.in[0]);
+    units_ = sched::build_units(net_, xor_fast_); tasks_ = {};
     rebuildRelevel();  // also sizes the scratch slots the re-levelled schedule needs
     buildShardPlan();
     Reset();
@@ -420,12 +422,9 @@ void Circuit::setInstances(unsigned k) {
     rebuildRelevel();   // the balanced schedule depends on K
 }
 
-void Circuit::instanceRange(unsigned& lo, unsigned& hi) const {
-    lo = 0; hi = instances_;
-    if (world_ > 1 && shard_mode_ == 0) {
-        unsigned per = instances_ / world_;
-        lo = rank_ * per; hi = lo + per;
-    }
+std::pair<unsigned, unsigned> Circuit::instanceRange() const {
+    const unsigned per = instances_ / world_;
+    return instanceSharded() ? std::make_pair(rank_ * per, rank_ * per + per) : std::make_pair(0u, instances_);
 }
 
 void Circuit::SetInput(const Inputs& input, bool verbose) { SetInput(0, input, verbose); }
@@ -438,8 +437,7 @@ void Circuit::SetInput(unsigned inst, const Inputs& input, bool verbose) {
         total_bits += input[k].size();
     }
     if (verbose) std::cout << "set input total of " << input.size() << " inputs" << std::endl;
-    unsigned lo, hi;
-    instanceRange(lo, hi);
+    const auto [lo, hi] = instanceRange();
     const bool mine = inst >= lo && inst < hi;
     std::vector<uint8_t> bits;
     std::vector<uint32_t> slots;
@@ -483,39 +481,7 @@ void Circuit::SetInput(unsigned inst, const Inputs& input, bool verbose) {
 
 // ---- sharding plan --------------------------------------------------------------------------
 void Circuit::buildShardPlan() {
-    owner_.clear();
-    xwires_.clear();
-    if (world_ <= 1 || shard_mode_ != 1) return;
-    const size_t Lc = levels_.size();
-    owner_.resize(Lc);
-    std::vector<uint8_t> gate_owner(allGates.size(), 0xFF);  // 0xFF = everyone (OUTPUT)
-    for (size_t l = 0; l < Lc; ++l) {
-        const auto& gl = levels_[l].gates;
-        uint64_t total = 0;
-        for (int gi : gl) total += 4 * gate_weight(allGates[gi].op, xor_fast_) + 1;  // NOT/OUTPUT weigh 1/4 bootstrap
-        uint64_t cum = 0;
-        owner_[l].resize(gl.size());
-        for (size_t k = 0; k < gl.size(); ++k) {
-            const auto& g = allGates[gl[k]];
-            uint8_t o = (uint8_t)std::min<uint64_t>(world_ - 1, cum * world_ / std::max<uint64_t>(total, 1));
-            cum += 4 * gate_weight(g.op, xor_fast_) + 1;
-            if (g.op == GateEnum::OUTPUT) o = 0xFF;
-            owner_[l][k] = o;
-            gate_owner[gl[k]] = o;
-        }
-    }
-    xwires_.assign(Lc, std::vector<std::vector<int>>(world_));
-    for (size_t l = 0; l < Lc; ++l) {
-        const auto& gl = levels_[l].gates;
-        for (size_t k = 0; k < gl.size(); ++k) {
-            const auto& g = allGates[gl[k]];
-            if (g.out < 0) continue;
-            const uint8_t o = owner_[l][k];
-            bool cross = false;
-            for (uint32_t e = fan_off_[g.out]; e < fan_off_[g.out + 1] && !cross; ++e) cross = gate_owner[fan_gate_[e]] != o;
-            if (cross) xwires_[l][o].push_back(g.out);
-        }
-    }
+    shard_ = gateSharded() ? sched::shard_levels(net_, world_, xor_fast_) : sched::LevelShard{};
 }
 
 uint64_t Circuit::exchangeCapacity(uint32_t world, int shard_mode, bool encrypted) const {
@@ -526,12 +492,12 @@ uint64_t Circuit::exchangeCapacity(uint32_t world, int shard_mode, bool encrypte
     if (shard_mode == 0) return std::max<uint64_t>(64, (uint64_t)(instances_ / world) * nout);
     // mode 1: widest per-rank publication over all levels (plan must be built for this world)
     uint64_t widest = 0;
-    for (const auto& lv : xwires_) for (const auto& r : lv) widest = std::max<uint64_t>(widest, r.size());
-    if (xwires_.empty()) for (const auto& lv : levels_) widest = std::max<uint64_t>(widest, lv.gates.size());
+    for (const auto& lv : shard_.publish) for (const auto& r : lv) widest = std::max<uint64_t>(widest, r.size());
+    if (shard_.publish.empty()) for (const auto& lv : levels_) widest = std::max<uint64_t>(widest, lv.gates.size());
     // bootstrap-depth schedule under gate sharding: per-step publications (before the plan exists for this world: a step's
     // outputs are at most its descriptors; slack filling under a larger world can widen steps up to the whole circuit's width)
-    for (const auto& st : relevel_xw_) for (const auto& r : st) widest = std::max<uint64_t>(widest, r.size());
-    if (relevel_xw_.empty()) for (const auto& st : relevel_plan_) widest = std::max<uint64_t>(widest, st.descs.size());
+    for (const auto& st : steps_.publish) for (const auto& r : st) widest = std::max<uint64_t>(widest, r.size());
+    if (steps_.publish.empty()) for (const auto& st : steps_.steps) widest = std::max<uint64_t>(widest, st.size());
     // (callers size their buffers with this BEFORE set_exchange and ask again afterwards: the plan for the new world may
     // publish more per step than the estimate -- dist.Exchange does)
     return std::max<uint64_t>(64, widest * instances_ * (encrypted ? W : 1));
@@ -553,21 +519,15 @@ uint64_t Circuit::planHash() const {
     uint64_t h = 0xcbf29ce484222325ull;   // FNV-1a over 64-bit words
     auto mix = [&](uint64_t v) { h = (h ^ v) * 0x100000001b3ull; };
     mix(world_); mix((uint64_t)shard_mode_); mix(stride_); mix(instances_); mix(relevel_ ? 1 : 0); mix(xor_fast_ ? 1 : 0);
-    for (const auto& lv : owner_) { mix(lv.size()); for (uint8_t o : lv) mix(o); }
-    for (const auto& lv : xwires_) for (const auto& r : lv) { mix(r.size()); for (int w : r) mix((uint64_t)w); }
-    for (const auto& st : relevel_xw_) for (const auto& r : st) { mix(r.size()); for (int w : r) mix((uint64_t)w); }
+    for (const auto& lv : shard_.owner) { mix(lv.size()); for (uint8_t o : lv) mix(o); }
+    for (const auto& lv : shard_.publish) for (const auto& r : lv) { mix(r.size()); for (int w : r) mix((uint64_t)w); }
+    for (const auto& st : steps_.publish) for (const auto& r : st) { mix(r.size()); for (int w : r) mix((uint64_t)w); }
     return h;
-}
-
-// after a level: publish wires whose consumers sit on other ranks (shard_mode 1)
-void Circuit::exchangeLevel(size_t level) {
-    if (world_ <= 1 || shard_mode_ != 1) return;
-    exchangeWires(xwires_[level]);
 }
 
 // one exchange: pub[r] = the wires rank r publishes (every rank knows every list: the plan is static)
 void Circuit::exchangeWires(const std::vector<std::vector<int>>& pub) {
-    if (world_ <= 1 || shard_mode_ != 1) return;
+    if (!gateSharded()) return;
     size_t widest = 0;
     for (uint32_t r = 0; r < world_; ++r) widest = std::max(widest, pub[r].size());
     if (widest == 0) return;
@@ -623,10 +583,9 @@ void Circuit::exchangeWires(const std::vector<std::vector<int>>& pub) {
 
 // shard_mode 0: every rank ends with the outputs of all instances
 void Circuit::gatherOutputs() {
-    if (world_ <= 1 || shard_mode_ != 0) return;
+    if (!instanceSharded()) return;
     const uint64_t nout = n_output_bits[0];
-    unsigned lo, hi;
-    instanceRange(lo, hi);
+    const auto [lo, hi] = instanceRange();
     const uint64_t bytes = (uint64_t)(hi - lo) * nout;
     if (bytes == 0) return;
     if (bytes > xcap_ || !host_send_ || !host_recv_) throw std::runtime_error("gatherOutputs: host buffers too small");
@@ -640,397 +599,78 @@ void Circuit::gatherOutputs() {
     ++stats_.exchanges;
 }
 
-// ---- re-levelled (bootstrap-depth) schedule: SURVEY 8(f2) -------------------------------------------
-// Units of the schedule: a single bootstrap (AND / OR / XOR_FAST; its output is ready one step later) or an XOR built as
-// the reference builds it (two ANDs in step s, their OR in step s + 1; ready two steps later).  ASAP placement gives the
-// bootstrap depth of the circuit, D steps.  With balance_ on, the same D steps are filled by SLACK instead: one
-// bootstrap is one workgroup, so a frontier call costs a staircase in its size (one bootstrap latency up to `lone`
-// bootstraps, then one round per `full` resident workgroups; bce_launch_capacity), and a step that holds K x count
-// bootstraps is topped up to the next stair with the ready units of least slack (ALAP order).  Units that must run now
-// (ALAP step reached) always do, so the depth stays D; which step a gate runs in does not change its ciphertext.
-void Circuit::launchCapacity(uint32_t& lone, uint32_t& full) const {
-    lone = cap_lone_; full = cap_full_;
-    if (lone == 0 || full == 0) {
-        lone = 256; full = 512;
-        if (cc) { uint32_t a = 0, b = 0; if (bce_launch_capacity(cc, &a, &b) == BCE_OK && a && b) { lone = a; full = b; } }
-    }
+// ---- re-levelled (bootstrap-depth) schedule: SURVEY 8(f2), built by the schedule module (schedule.hpp) ----------------
+// One bootstrap is one workgroup, so a frontier call costs a staircase in its size (one bootstrap latency up to `lone`
+// bootstraps, then one round per `full` resident workgroups; bce_launch_capacity): the capacities slack filling works with.
+std::pair<uint32_t, uint32_t> Circuit::launchCapacity() const {
+    if (cap_lone_ && cap_full_) return {cap_lone_, cap_full_};
+    uint32_t a = 0, b = 0;
+    return cc && bce_launch_capacity(cc, &a, &b) == BCE_OK && a && b ? std::make_pair(a, b) : std::make_pair(256u, 512u);
 }
 
-// units of the bootstrap DAG in topological order (NOT chains resolved into negation flags); returns the bootstrap depth
-uint32_t Circuit::buildUnits(std::vector<Unit>& units, std::vector<int>& base, std::vector<uint8_t>& neg) const {
-    const size_t W = wire_names_.size(), G = allGates.size();
-    // resolve NOT chains: wire -> (base wire, negated)
-    base.resize(W);
-    neg.assign(W, 0);
-    for (size_t w = 0; w < W; ++w) base[w] = (int)w;
-    // gates are in topological (file) order per level; walk levels so that bases are resolved first
-    std::vector<uint32_t> depth(W, 0);
-    units.clear();
-    std::vector<int32_t> prod(W, -1);   // base wire -> unit that produces it
-    units.reserve(G);
-    for (const auto& L : levels_)
-        for (int gi : L.gates) {
-            const GateRec& g = allGates[gi];
-            if (g.op == GateEnum::NOT) {
-                base[g.out] = base[g.in[0]];
-                neg[g.out] = neg[g.in[0]] ^ 1;
-                depth[g.out] = depth[g.in[0]];
-            } else if (g.op == GateEnum::AND || g.op == GateEnum::OR || g.op == GateEnum::XOR) {
-                const uint32_t b0 = (uint32_t)base[g.in[0]], b1 = (uint32_t)base[g.in[1]];
-                const uint32_t n0 = neg[g.in[0]], n1 = neg[g.in[1]];
-                const uint32_t d = 1 + std::max(depth[g.in[0]], depth[g.in[1]]);
-                Unit u{d, d, 1, 0, {0, b0, b1, (uint32_t)g.out, n0, n1}, prod[b0], prod[b1]};
-                if (g.op != GateEnum::XOR) {
-                    u.d.op = (uint32_t)(g.op == GateEnum::AND ? BCE_AND : BCE_OR);
-                } else if (xor_fast_) {
-                    // XOR_FAST of negated inputs: NOT a XOR NOT b = a XOR b; one negation flips the result
-                    u.d.op = (uint32_t)((n0 ^ n1) ? BCE_XNOR_FAST : BCE_XOR_FAST);
-                    u.d.neg0 = u.d.neg1 = 0;
-                } else {
-                    u.lat = 2;
-                }
-                depth[g.out] = d + u.lat - 1;
-                prod[g.out] = (int32_t)units.size();
-                units.push_back(u);
-            }
-        }
-    uint32_t D = 0;
-    for (const auto& u : units) D = std::max(D, u.asap + u.lat - 1);
-    return D;
-}
-
-// successors (CSR) and ALAP start steps of the units (which are in topological order)
-void Circuit::unitSuccessorsAlap(const std::vector<Unit>& units, uint32_t D, std::vector<uint32_t>& soff, std::vector<uint32_t>& succ,
-                                 std::vector<uint32_t>& alap) {
-    const size_t U = units.size();
-    soff.assign(U + 1, 0);
-    for (const auto& u : units) { if (u.p0 >= 0) ++soff[u.p0 + 1]; if (u.p1 >= 0 && u.p1 != u.p0) ++soff[u.p1 + 1]; }
-    for (size_t i = 0; i < U; ++i) soff[i + 1] += soff[i];
-    succ.resize(soff[U]);
-    {
-        std::vector<uint32_t> fill(soff.begin(), soff.end() - 1);
-        for (size_t i = 0; i < U; ++i) {
-            const Unit& u = units[i];
-            if (u.p0 >= 0) succ[fill[u.p0]++] = (uint32_t)i;
-            if (u.p1 >= 0 && u.p1 != u.p0) succ[fill[u.p1]++] = (uint32_t)i;
-        }
-    }
-    alap.resize(U);
-    for (size_t i = U; i-- > 0;) {
-        uint32_t a = D - units[i].lat + 1;
-        for (uint32_t k = soff[i]; k < soff[i + 1]; ++k) a = std::min(a, alap[succ[k]] - units[i].lat);
-        alap[i] = a;
-    }
-}
-
-void Circuit::dropPlan() {
-    if (plan_) { bce_plan_destroy(cc, plan_); plan_ = nullptr; }
-}
-
-bool Circuit::graphActive() const {
-    return graph_ && cc && relevel_ && !dataflowActive() && !verify_flag && !(world_ > 1 && shard_mode_ == 1);
-}
-
-void Circuit::buildRelevelPlan() {
-    dropPlan();   // the resident copy of the schedule belongs to the plan it was built from
-    const size_t W = wire_names_.size();
-    std::vector<int> base;
-    std::vector<uint8_t> neg;
-    std::vector<Unit> units;
-    const uint32_t D = buildUnits(units, base, neg);
-    const size_t U = units.size();
-    unsigned ilo, ihi;
-    instanceRange(ilo, ihi);
-    const uint64_t K = std::max(1u, ihi - ilo);
-    const bool sharded = world_ > 1 && shard_mode_ == 1;   // gate sharding: every step's units are split over the ranks
-    if (balance_ && U) {
-        uint32_t lone, full;
-        launchCapacity(lone, full);
-        if (sharded) { lone *= world_; full *= world_; }   // the stairs of world_ devices working on one step
-        std::vector<uint32_t> soff, succ, alap;
-        unitSuccessorsAlap(units, D, soff, succ, alap);
-        // list scheduling, least slack first
-        using Key = std::pair<uint32_t, uint32_t>;   // (ALAP step, unit)
-        std::priority_queue<Key, std::vector<Key>, std::greater<Key>> ready;
-        std::vector<std::vector<uint32_t>> later(D + 2);   // units that become ready at a step
-        std::vector<uint32_t> waiting(U), ready_at(U, 1);
-        for (size_t i = 0; i < U; ++i) {
-            const Unit& u = units[i];
-            waiting[i] = (u.p0 >= 0) + (u.p1 >= 0 && u.p1 != u.p0);
-            if (!waiting[i]) ready.push({alap[i], (uint32_t)i});
-        }
-        std::vector<uint32_t> ors_due(D + 2, 0);   // ORs of the XORs started one step earlier
-        std::vector<uint32_t> chosen;
-        for (uint32_t s = 1; s <= D; ++s) {
-            for (uint32_t i : later[s]) ready.push({alap[i], i});
-            chosen.clear();
-            uint64_t cnt = ors_due[s];
-            while (!ready.empty() && ready.top().first <= s) {   // no slack left
-                const uint32_t i = ready.top().second; ready.pop();
-                chosen.push_back(i); cnt += units[i].lat == 2 ? 2 : 1;
-            }
-            const uint64_t n = cnt * K;
-            const uint64_t cap = (n <= lone ? lone : (n + full - 1) / full * full) / K;
-            while (!ready.empty()) {
-                const uint32_t i = ready.top().second;
-                const uint64_t w = units[i].lat == 2 ? 2 : 1;
-                if (cnt + w > cap) break;
-                // an XOR started in the last step would put its OR beyond D only if its ALAP allowed it: it does not
-                ready.pop(); chosen.push_back(i); cnt += w;
-            }
-            for (uint32_t i : chosen) {
-                Unit& u = units[i];
-                u.start = s;
-                if (u.lat == 2) ++ors_due[s + 1];
-                for (uint32_t k = soff[i]; k < soff[i + 1]; ++k) {
-                    const uint32_t q = succ[k];
-                    ready_at[q] = std::max(ready_at[q], s + u.lat);
-                    if (--waiting[q] == 0) later[ready_at[q]].push_back(q);
-                }
-            }
-        }
-        if (!ready.empty()) throw std::logic_error("buildRelevelPlan: units left unscheduled");
-    }
-    // gate sharding: the units that start in a step are split over the ranks in netlist order by bootstrap weight (an XOR's
-    // three bootstraps stay on one rank: its temporaries are local), on top of the ORs each rank carries over from the
-    // previous step.  Every rank computes the same plan.
-    relevel_xw_.clear();
-    if (sharded) {
-        std::vector<std::vector<uint32_t>> by_step(D + 2);
-        for (size_t i = 0; i < U; ++i) by_step[units[i].start].push_back((uint32_t)i);
-        auto assign_owners = [&](bool locality) {
-        std::vector<uint64_t> carried(world_, 0), next_carried(world_, 0);
-        for (uint32_t st = 1; st <= D; ++st) {
-            uint64_t total = 0;
-            for (uint32_t r = 0; r < world_; ++r) total += carried[r];
-            for (uint32_t i : by_step[st]) total += units[i].lat == 2 ? 2 : 1;
-            std::fill(next_carried.begin(), next_carried.end(), 0);
-            if (!locality) {
-                // contiguous split in netlist order: rank r ends where the running load (carried ORs of ranks <= r + the units
-                // given out so far) reaches (r + 1) / world of the step's total (midpoint rule: within one unit of the fair share)
-                uint32_t r = 0;
-                uint64_t cum = carried[0];
-                for (uint32_t i : by_step[st]) {
-                    const uint64_t w = units[i].lat == 2 ? 2 : 1;
-                    while (r + 1 < world_ && (2 * cum + w) * world_ > 2 * (uint64_t)(r + 1) * total) { ++r; cum += carried[r]; }
-                    units[i].owner = (uint8_t)r;
-                    cum += w;
-                    if (units[i].lat == 2) ++next_carried[r];
-                }
-            } else {
-                // locality first ("schedule a gate on the GPU that produced most of its inputs"), balance as the
-                // constraint: every rank may take up to its fair share of the step's bootstraps (rounded up, + one unit so that
-                // an XOR's pair never has to split).  Units whose two producers sit on one rank choose first, then those with
-                // one producing rank, then the free ones fill the least loaded ranks.  Deterministic: every rank computes it.
-                const uint64_t share = (total + world_ - 1) / world_ + 1;
-                std::vector<uint64_t> load(carried);
-                std::vector<uint32_t> rest;
-                auto place = [&](uint32_t i, uint32_t r) {
-                    units[i].owner = (uint8_t)r;
-                    load[r] += units[i].lat == 2 ? 2 : 1;
-                    if (units[i].lat == 2) ++next_carried[r];
-                };
-                auto owner_of = [&](int32_t p) -> int { return p >= 0 ? (int)units[p].owner : -1; };
-                for (int pass = 0; pass < 2; ++pass)
-                    for (uint32_t i : by_step[st]) {
-                        const uint64_t w = units[i].lat == 2 ? 2 : 1;
-                        const int a = owner_of(units[i].p0), b = owner_of(units[i].p1);
-                        const bool both = a >= 0 && a == b;
-                        if (pass == 0) {
-                            if (both && load[a] + w <= share) place(i, (uint32_t)a);
-                            else if (!both) continue;
-                            else rest.push_back(i);
-                        } else if (!both) {
-                            // one producing rank, or two different ones: the lighter of them if it has room
-                            int c = -1;
-                            if (a >= 0 && load[a] + w <= share) c = a;
-                            if (b >= 0 && load[b] + w <= share && (c < 0 || load[b] < load[c])) c = b;
-                            if (c >= 0) place(i, (uint32_t)c); else rest.push_back(i);
-                        }
-                    }
-                std::sort(rest.begin(), rest.end());   // netlist order
-                for (uint32_t i : rest) {
-                    uint32_t r = 0;
-                    for (uint32_t k = 1; k < world_; ++k) if (load[k] < load[r]) r = k;
-                    place(i, r);
-                }
-            }
-            carried.swap(next_carried);
-        }
-        };
-        // outputs that cross ranks under an assignment (consumers elsewhere; OUTPUT gates are read by every rank either way)
-        auto crossings = [&]() {
-            std::vector<uint8_t> x(U, 0);
-            for (size_t i = 0; i < U; ++i) {
-                const Unit& u = units[i];
-                if (u.p0 >= 0 && units[u.p0].owner != u.owner) x[u.p0] = 1;
-                if (u.p1 >= 0 && units[u.p1].owner != u.owner) x[u.p1] = 1;
-            }
-            uint64_t n = 0;
-            for (uint8_t v : x) n += v;
-            return n;
-        };
-        assign_owners(false);
-        if (shard_locality_) {
-            // keep whichever split publishes less: netlist order already is a locality order for some circuits (sha256 on two
-            // ranks), input-following placement wins on others (AES-expanded on eight: 21.0 k -> 11.9 k crossing outputs)
-            const uint64_t contiguous = crossings();
-            assign_owners(true);
-            if (crossings() > contiguous) assign_owners(false);
-        }
-        // publications: an output crosses when a consumer unit sits on another rank, or when an OUTPUT gate reads it (every
-        // rank decrypts every output, as in the gate-level plan); it is published after the step that produces it
-        std::vector<uint8_t> feeds_output(W, 0);
-        for (const auto& g : allGates) if (g.op == GateEnum::OUTPUT) feeds_output[base[g.in[0]]] = 1;
-        std::vector<uint8_t> cross(U, 0);
-        for (size_t i = 0; i < U; ++i) {
-            const Unit& u = units[i];
-            if (u.p0 >= 0 && units[u.p0].owner != u.owner) cross[u.p0] = 1;
-            if (u.p1 >= 0 && units[u.p1].owner != u.owner) cross[u.p1] = 1;
-            if (feeds_output[u.d.out]) cross[i] = 1;
-        }
-        relevel_xw_.assign(D, std::vector<std::vector<int>>(world_));
-        for (size_t i = 0; i < U; ++i)
-            if (cross[i]) relevel_xw_[units[i].start + units[i].lat - 2][units[i].owner].push_back((int)units[i].d.out);
-    }
-    // temporaries of the XORs: two parity banks (a step's ANDs write one bank while the previous step's ORs read the other)
-    std::vector<uint32_t> xor_at(D + 2, 0);
-    uint32_t max_x = 0;
-    for (const auto& u : units) if (u.lat == 2 && (!sharded || u.owner == rank_)) max_x = std::max(max_x, ++xor_at[u.start]);
-    if (sharded) {   // the slot stride must be the same on every rank: size the banks for the fullest step of ANY rank
-        std::vector<uint32_t> cnt((size_t)(D + 2) * world_, 0);
-        for (const auto& u : units) if (u.lat == 2) max_x = std::max(max_x, ++cnt[(size_t)u.start * world_ + u.owner]);
-    }
-    const uint32_t tmp0 = (uint32_t)W;
-    relevel_stride_ = tmp0 + 4 * max_x;
-    relevel_plan_.assign(D, RStep{});
-    std::fill(xor_at.begin(), xor_at.end(), 0);
-    for (const auto& u : units) {
-        if (sharded && u.owner != rank_) continue;
-        if (u.lat == 1) {
-            relevel_plan_[u.start - 1].descs.push_back(u.d);
-        } else {
-            const uint32_t idx = xor_at[u.start]++;
-            const uint32_t t1 = tmp0 + (u.start & 1) * 2 * max_x + 2 * idx, t2 = t1 + 1;
-            // (a AND !b), (!a AND b) with the inputs' own negations folded in, then OR one step later
-            relevel_plan_[u.start - 1].descs.push_back({BCE_AND, u.d.in0, u.d.in1, t1, u.d.neg0, u.d.neg1 ^ 1u});
-            relevel_plan_[u.start - 1].descs.push_back({BCE_AND, u.d.in0, u.d.in1, t2, u.d.neg0 ^ 1u, u.d.neg1});
-            relevel_plan_[u.start].descs.push_back({BCE_OR, t1, t2, u.d.out, 0, 0});
-        }
-    }
-    relevel_K_ = (uint32_t)K;
-    // NOT wires consumed by OUTPUT gates need a real ciphertext (decrypt must see EvalNOT's output)
-    relevel_nots_.clear();
-    std::vector<uint8_t> done_not(W, 0);
-    for (const auto& g : allGates)
-        if (g.op == GateEnum::OUTPUT && neg[g.in[0]] && !done_not[g.in[0]]) {
-            done_not[g.in[0]] = 1;
-            relevel_nots_.push_back({BCE_OP_NOT, (uint32_t)base[g.in[0]], (uint32_t)base[g.in[0]], (uint32_t)g.in[0], 0, 0});
-        } else if (g.op == GateEnum::OUTPUT && !neg[g.in[0]] && base[g.in[0]] != g.in[0] && !done_not[g.in[0]]) {
-            done_not[g.in[0]] = 1;  // double negation: plain copy of the base
-            relevel_nots_.push_back({BCE_OP_COPY, (uint32_t)base[g.in[0]], (uint32_t)base[g.in[0]], (uint32_t)g.in[0], 0, 0});
-        }
-}
-
-// (re)build the bootstrap-depth schedule for the current K / capacities and size the per-instance slot stride for it.
-// The stride is part of the pool layout: not after SetInput.
+// (re)build the bootstrap-depth schedule for the current K / capacities / ranks (place, then lower), the dataflow task list
+// while that schedule is chosen, and size the per-instance slot stride for them.  The stride is part of the pool layout:
+// not after SetInput.
 void Circuit::rebuildRelevel() {
-    buildRelevelPlan();
-    if (dataflow_) buildDagTasks();
-    uint32_t need = std::max(base_stride_, relevel_stride_);
-    if (dataflow_) need = std::max(need, dag_stride_);
-    if (inputs_set_ && need > stride_ && balance_) {
-        // the inputs already sit in a pool laid out for a smaller stride: keep the layout, fall back to ASAP placement
-        // (whose temporaries the stride of finalizeNetlist() always covers)
-        balance_ = false;
-        buildRelevelPlan();
-        balance_ = true;
-        need = std::max(base_stride_, relevel_stride_);
-        if (dataflow_) need = std::max(need, dag_stride_);
-    }
+    dropPlan();   // the resident copies of the schedules belong to the plans they were built from
+    dropDag();
+    const auto [lo, hi] = instanceRange();
+    const uint64_t K = std::max(1u, hi - lo);
+    const uint32_t world = gateSharded() ? world_ : 1;   // gate sharding: every step's units are split over the ranks
+    if (!dataflow_ || tasks_.tasks.empty()) tasks_ = dataflow_ ? sched::lower_tasks(units_, net_.n_wires) : sched::TaskList{};   // a function of the units
+    auto plan = [&](bool by_slack) {   // returns the slot stride the schedules need
+        if (by_slack && !units_.units.empty()) {
+            const auto [lone, full] = launchCapacity();
+            sched::place_by_slack(units_, K, lone * world, full * world);   // the stairs of `world` devices working on one step
+        } else {
+            sched::place_asap(units_);
+        }
+        if (world > 1) sched::assign_owners(units_, world, shard_locality_);
+        steps_ = sched::lower_steps(units_, net_, rank_, world, K);
+        return std::max({base_stride_, steps_.stride, tasks_.stride});
+    };
+    uint32_t need = plan(balance_);
+    // the inputs already sit in a pool laid out for a smaller stride: keep the layout, fall back to ASAP placement
+    // (whose temporaries the stride of finalizeNetlist() always covers)
+    if (inputs_set_ && need > stride_ && balance_) need = plan(false);
     if (inputs_set_ && need > stride_) throw std::logic_error("the schedule needs a larger slot stride than the pool was laid out with");
     if (!inputs_set_) stride_ = need;
 }
 
-// per-step bootstrap counts of the schedule (for one instance), and a self-check: every input of every step was produced
-// by an earlier step (or is a primary input / constant), every XOR temporary is read exactly one step after it is written
+// per-step bootstrap counts of the schedule (for one instance)
 std::vector<uint32_t> Circuit::relevelStepSizes() const {
     std::vector<uint32_t> v;
-    for (const auto& st : relevel_plan_) v.push_back((uint32_t)st.descs.size());
+    for (const auto& st : steps_.steps) v.push_back((uint32_t)st.size());
     return v;
 }
 
 std::vector<uint32_t> Circuit::relevelPublications() const {
-    std::vector<uint32_t> v(relevel_plan_.size(), 0);
-    for (size_t s = 0; s < relevel_xw_.size() && s < v.size(); ++s) v[s] = (uint32_t)relevel_xw_[s][rank_].size();
+    std::vector<uint32_t> v(steps_.steps.size(), 0);
+    for (size_t s = 0; s < steps_.publish.size() && s < v.size(); ++s) v[s] = (uint32_t)steps_.publish[s][rank_].size();
     return v;
-}
-
-bool Circuit::checkRelevelPlan(std::string* why) const {
-    const size_t W = wire_names_.size();
-    std::vector<int32_t> written(relevel_stride_, -1);   // step that wrote a slot; inputs and constants: step -1 = "before"
-    std::vector<uint8_t> is_out(W, 0);
-    for (const auto& g : allGates) if ((g.op == GateEnum::AND || g.op == GateEnum::OR || g.op == GateEnum::XOR) && g.out >= 0) is_out[g.out] = 1;
-    auto fail = [&](const std::string& m) { if (why) *why = m; return false; };
-    for (size_t s = 0; s < relevel_plan_.size(); ++s) {
-        for (const auto& d : relevel_plan_[s].descs) {
-            for (uint32_t in : {d.in0, d.in1}) {
-                if (in >= relevel_stride_) return fail("input slot outside the stride");
-                if (in < W) {
-                    if (is_out[in] && (written[in] < 0 || written[in] >= (int32_t)s)) return fail("step " + std::to_string(s) + " reads register " + std::to_string(in) + " before it is written");
-                } else if (written[in] != (int32_t)s - 1) {
-                    return fail("step " + std::to_string(s) + " reads an XOR temporary that was not written in the previous step");
-                }
-            }
-        }
-        for (const auto& d : relevel_plan_[s].descs) {
-            if (d.out >= relevel_stride_) return fail("output slot outside the stride");
-            if (d.out < W && written[d.out] >= 0) return fail("register written twice");
-            if (written[d.out] == (int32_t)s) return fail("slot written twice in one step");
-            written[d.out] = (int32_t)s;
-        }
-        // gate sharding: what the other ranks publish after this step arrives before the next one
-        if (s < relevel_xw_.size())
-            for (uint32_t r = 0; r < world_; ++r) {
-                if (r == rank_) {
-                    for (int w : relevel_xw_[s][r]) if (written[w] != (int32_t)s) return fail("publishes register " + std::to_string(w) + " in a step that did not write it");
-                } else {
-                    for (int w : relevel_xw_[s][r]) { if (written[w] >= 0) return fail("receives a register it wrote itself"); written[w] = (int32_t)s; }
-                }
-            }
-    }
-    if (relevel_xw_.empty())
-        for (size_t w = 0; w < W; ++w) if (is_out[w] && written[w] < 0) return fail("register " + std::to_string(w) + " never written");
-    return true;
 }
 
 void Circuit::setXorFast(bool b) {
     xor_fast_ = gep.xor_fast = b;
+    units_ = sched::build_units(net_, xor_fast_); tasks_ = {};
     buildShardPlan();
-    rebuildRelevel();
-}
-
-void Circuit::setBalance(bool on, uint32_t lone, uint32_t full) {
-    balance_ = on; cap_lone_ = lone; cap_full_ = full;
     rebuildRelevel();
 }
 
 void Circuit::clockReleveled() {
     if (verify_flag) throw std::logic_error("re-levelled schedule is not available in verify mode");
-    unsigned lo, hi;
-    instanceRange(lo, hi);
+    const auto [lo, hi] = instanceRange();
     const uint32_t K = hi - lo;
-    if (relevel_plan_.empty() || (balance_ && relevel_K_ != std::max(1u, K))) rebuildRelevel();
-    if (relevel_stride_ > stride_) throw std::logic_error("re-levelled schedule needs more scratch slots than the pool stride");
-    const bool sharded = world_ > 1 && shard_mode_ == 1;
+    if (steps_.steps.empty() || (balance_ && steps_.K != std::max(1u, K))) rebuildRelevel();
+    if (steps_.stride > stride_) throw std::logic_error("re-levelled schedule needs more scratch slots than the pool stride");
     // the schedule's descriptors live on the device from the first Clock() on (bce_plan): a step is one call without an
     // upload; with setGraph the whole schedule is one hipGraph launch
     if (plan_ && (plan_lo_ != lo || plan_K_ != K || plan_stride_ != stride_)) dropPlan();
     if (!plan_ && K) {
         std::vector<uint32_t> sizes;
         std::vector<bce_gate_desc> all;
-        for (const auto& st : relevel_plan_)
-            if (!st.descs.empty()) { sizes.push_back((uint32_t)st.descs.size()); all.insert(all.end(), st.descs.begin(), st.descs.end()); }
+        for (const auto& st : steps_.steps)
+            if (!st.empty()) { sizes.push_back((uint32_t)st.size()); all.insert(all.end(), st.begin(), st.end()); }
         if (!sizes.empty()) {
             ck(bce_plan_create(cc, (uint32_t)sizes.size(), sizes.data(), all.data(), K, stride_, lo * stride_, &plan_), "Clock(schedule upload)");
             plan_lo_ = lo; plan_K_ = K; plan_stride_ = stride_;
@@ -1038,78 +678,35 @@ void Circuit::clockReleveled() {
     }
     if (plan_ && graphActive()) {
         ck(bce_plan_run(cc, plan_), "Clock(schedule graph)");
-        for (const auto& st : relevel_plan_) if (!st.descs.empty()) ++stats_.sublaunches;
+        for (const auto& st : steps_.steps) if (!st.empty()) ++stats_.sublaunches;
     } else {
         uint32_t ps = 0;
-        for (size_t s = 0; s < relevel_plan_.size(); ++s) {
-            if (plan_ && !relevel_plan_[s].descs.empty()) {
+        for (size_t s = 0; s < steps_.steps.size(); ++s) {
+            if (plan_ && !steps_.steps[s].empty()) {
                 ck(bce_plan_run_step(cc, plan_, ps++), "Clock(re-levelled step)");
                 ++stats_.sublaunches;
             }
-            if (sharded) exchangeWires(relevel_xw_[s]);   // outputs of this step whose consumers sit on other ranks
+            if (gateSharded()) exchangeWires(steps_.publish[s]);   // outputs of this step whose consumers sit on other ranks
         }
     }
     finishReleveled(lo, hi);
-    stats_.levels = (uint32_t)relevel_plan_.size();
+    stats_.levels = (uint32_t)steps_.steps.size();
 }
 
 // ---- dataflow schedule: the whole bootstrap DAG in one persistent launch (bce_dag_*) -------------------------------
 // Tasks = the units of the bootstrap-depth schedule in topological order, an XOR as its two ANDs and its OR with
-// temporaries of its own (SSA: the device runs independent tasks in any order, so no slot may be reused).  Priority
-// class of a task = slack of its unit (ALAP step - ASAP step): the device pulls ready tasks of the critical path first.
-void Circuit::buildDagTasks() {
-    const size_t W = wire_names_.size();
-    std::vector<int> base;
-    std::vector<uint8_t> neg;
-    std::vector<Unit> units;
-    const uint32_t D = buildUnits(units, base, neg);
-    std::vector<uint32_t> soff, succ, alap;
-    unitSuccessorsAlap(units, D, soff, succ, alap);
-    uint32_t cls[3] = {0, 1, 2};   // slack bounds of classes 0, 1, 2 (steps); development knob BCE_DAG_CLASSES=a,b,c
-                                   // (0,2,8 and 1,4,16 are 2-3 % slower on AES at K = 4 / 8)
-    if (const char* e = std::getenv("BCE_DAG_CLASSES")) std::sscanf(e, "%u,%u,%u", &cls[0], &cls[1], &cls[2]);
-    dag_tasks_.clear(); dag_prio_.clear();
-    uint32_t nx = 0;
-    for (size_t i = 0; i < units.size(); ++i) {
-        const Unit& u = units[i];
-        const uint32_t slack = alap[i] - u.asap;
-        const uint8_t pc = slack <= cls[0] ? 0 : slack <= cls[1] ? 1 : slack <= cls[2] ? 2 : 3;
-        if (u.lat == 1) {
-            dag_tasks_.push_back(u.d); dag_prio_.push_back(pc);
-        } else {
-            const uint32_t t1 = (uint32_t)W + 2 * nx, t2 = t1 + 1;
-            ++nx;
-            // (a AND !b), (!a AND b) with the inputs' own negations folded in, then their OR (src/gate.cpp:198-202)
-            dag_tasks_.push_back({BCE_AND, u.d.in0, u.d.in1, t1, u.d.neg0, u.d.neg1 ^ 1u});
-            dag_tasks_.push_back({BCE_AND, u.d.in0, u.d.in1, t2, u.d.neg0 ^ 1u, u.d.neg1});
-            dag_tasks_.push_back({BCE_OR, t1, t2, u.d.out, 0, 0});
-            dag_prio_.insert(dag_prio_.end(), 3, pc);
-        }
-    }
-    dag_stride_ = (uint32_t)W + 2 * nx;
-    dropDag();
-}
-
-void Circuit::dropDag() {
-    if (dag_) { bce_dag_destroy(cc, dag_); dag_ = nullptr; }
-}
-
+// temporaries of its own (SSA: the device runs independent tasks in any order, so no slot may be reused); sched::lower_tasks.
 void Circuit::setDataflow(bool b) {
     if (b && inputs_set_ && !dataflow_) throw std::logic_error("setDataflow: choose the dataflow schedule before SetInput (it lays the pool out with its own temporaries)");
     dataflow_ = b;
     rebuildRelevel();
 }
 
-bool Circuit::dataflowActive() const {
-    return dataflow_ && cc && !verify_flag && !(world_ > 1 && shard_mode_ == 1) && bce_dag_supported(cc) && !dag_tasks_.empty();
-}
-
 void Circuit::clockDataflow() {
-    unsigned lo, hi;
-    instanceRange(lo, hi);
-    if (dag_stride_ > stride_) throw std::logic_error("dataflow schedule needs more scratch slots than the pool stride");
-    if (relevel_plan_.empty()) rebuildRelevel();
-    if (!dag_) ck(bce_dag_create(cc, (uint32_t)dag_tasks_.size(), dag_tasks_.data(), dag_prio_.data(), &dag_), "Clock(dataflow DAG)");
+    const auto [lo, hi] = instanceRange();
+    if (tasks_.stride > stride_) throw std::logic_error("dataflow schedule needs more scratch slots than the pool stride");
+    if (steps_.steps.empty()) rebuildRelevel();
+    if (!dag_) ck(bce_dag_create(cc, (uint32_t)tasks_.tasks.size(), tasks_.tasks.data(), tasks_.prio.data(), &dag_), "Clock(dataflow DAG)");
     if (hi > lo) {
         ck(bce_dag_run(cc, dag_, hi - lo, stride_, lo * stride_), "Clock(dataflow run)");
         ++stats_.sublaunches;
@@ -1120,26 +717,49 @@ void Circuit::clockDataflow() {
 
 // NOT wires the OUTPUT gates read, OUTPUT gates (decrypt), gate counts: common end of the two DAG-level schedules
 void Circuit::finishReleveled(unsigned lo, unsigned hi) {
-    const uint32_t K = hi - lo;
-    if (!relevel_nots_.empty() && K) {
-        std::vector<bce_gate_desc> d(relevel_nots_);
-        for (auto& e : d) { e.in0 += lo * stride_; e.in1 += lo * stride_; e.out += lo * stride_; }
-        ck(bce_eval_gates_strided(cc, (uint32_t)d.size(), d.data(), K, stride_), "Clock(output NOTs)");
-        ++stats_.sublaunches;
-    }
-    // OUTPUT gates
+    evalStrided(steps_.output_nots, lo, hi - lo, "Clock(output NOTs)");
+    decryptOutputs(lo, hi, nullptr);
+    countGates(nullptr);
+}
+
+// descriptors address instance 0; a strided call replicates them K times from instance `lo` on
+std::vector<bce_gate_desc> Circuit::rebased(std::vector<bce_gate_desc> descs, unsigned lo) const {
+    for (auto& d : descs) { d.in0 += lo * stride_; d.in1 += lo * stride_; d.out += lo * stride_; }
+    return descs;
+}
+void Circuit::evalStrided(const std::vector<bce_gate_desc>& descs, unsigned lo, uint32_t K, const char* what) {
+    if (descs.empty() || !K) return;
+    const std::vector<bce_gate_desc> d = rebased(descs, lo);
+    ck(bce_eval_gates_strided(cc, (uint32_t)d.size(), d.data(), K, stride_), what);
+    ++stats_.sublaunches;
+}
+
+// retire the OUTPUT gates among `gates` (src/circuit.cpp:796-807): decrypt, or take the plaintext pass's bit
+void Circuit::decryptOutputs(unsigned lo, unsigned hi, const std::vector<int>* gates) {
     std::vector<uint32_t> oslots;
     std::vector<std::pair<unsigned, int>> obits;
-    for (const auto& g : allGates)
-        if (g.op == GateEnum::OUTPUT)
-            for (unsigned i = lo; i < hi; ++i) { oslots.push_back(i * stride_ + g.in[0]); obits.push_back({i, g.out_bit}); }
+    const size_t n = gates ? gates->size() : allGates.size();
+    for (size_t k = 0; k < n; ++k) {
+        const GateRec& g = allGates[gates ? (*gates)[k] : k];
+        if (g.op != GateEnum::OUTPUT) continue;
+        if (!encrypted_flag && !plaintext_flag) std::cerr << "Error either encrypted or plaintext flag must be set" << std::endl;
+        for (unsigned i = lo; i < hi; ++i) {
+            if (encrypted_flag) { oslots.push_back(i * stride_ + g.in[0]); obits.push_back({i, g.out_bit}); }
+            else circuitOut[i][g.out_bit] = plain_[i][g.in[0]];
+        }
+    }
     if (!oslots.empty()) {
         std::vector<uint8_t> res(oslots.size());
         ck(bce_decrypt_bits(cc, oslots.data(), (uint32_t)oslots.size(), res.data()), "Clock(Decrypt)");
         for (size_t k = 0; k < oslots.size(); ++k) circuitOut[obits[k].first][obits[k].second] = res[k];
     }
-    for (const auto& g : allGates) {
-        switch (g.op) {
+}
+
+// counters, once per evaluation (src/circuit.cpp:722-749)
+void Circuit::countGates(const std::vector<int>* gates) {
+    const size_t n = gates ? gates->size() : allGates.size();
+    for (size_t k = 0; k < n; ++k) {
+        switch (allGates[gates ? (*gates)[k] : k].op) {
             case GateEnum::OUTPUT: ++n_output_gates; break;
             case GateEnum::NOT: ++n_not_gates; break;
             case GateEnum::AND: ++n_and_gates; break;
@@ -1158,10 +778,8 @@ void Circuit::managerRound(size_t) {
 
 void Circuit::executeRound(size_t level) {
     const Level& L = levels_[level];
-    unsigned lo, hi;
-    instanceRange(lo, hi);
-    const bool sharded_gates = world_ > 1 && shard_mode_ == 1;
-    auto mine = [&](size_t k) { return !sharded_gates || owner_[level][k] == 0xFF || owner_[level][k] == rank_; };
+    const auto [lo, hi] = instanceRange();
+    auto mine = [&](size_t k) { return !gateSharded() || shard_.owner[level][k] == 0xFF || shard_.owner[level][k] == rank_; };
 
     if (plaintext_flag) {
         for (unsigned i = lo; i < hi; ++i) {
@@ -1195,9 +813,10 @@ void Circuit::executeRound(size_t level) {
                     const uint32_t t1 = tmp0 + 2 * x, t2 = t1 + 1;
                     ++x;
                     if (!me) continue;
-                    A.push_back({BCE_AND, (uint32_t)g.in[0], (uint32_t)g.in[1], t1, 0, 1});
-                    A.push_back({BCE_AND, (uint32_t)g.in[0], (uint32_t)g.in[1], t2, 1, 0});
-                    B.push_back({BCE_OR, t1, t2, (uint32_t)g.out, 0, 0});
+                    bce_gate_desc q[3];
+                    sched::xor_lower({0, (uint32_t)g.in[0], (uint32_t)g.in[1], (uint32_t)g.out, 0, 0}, t1, t2, q);
+                    A.insert(A.end(), q, q + 2);
+                    B.push_back(q[2]);
                 } else if (!me) {
                     continue;
                 } else if (g.op == GateEnum::AND || g.op == GateEnum::OR) {
@@ -1206,18 +825,8 @@ void Circuit::executeRound(size_t level) {
                     A.push_back({BCE_OP_NOT, (uint32_t)g.in[0], (uint32_t)g.in[0], (uint32_t)g.out, 0, 0});
                 }
             }
-            const uint32_t K = hi - lo;
-            if (!A.empty()) {
-                // descriptors address instance `lo`; the strided call replicates them K times
-                for (auto& d : A) { d.in0 += lo * stride_; d.in1 += lo * stride_; d.out += lo * stride_; }
-                ck(bce_eval_gates_strided(cc, (uint32_t)A.size(), A.data(), K, stride_), "Clock(stage A)");
-                ++stats_.sublaunches;
-            }
-            if (!B.empty()) {
-                for (auto& d : B) { d.in0 += lo * stride_; d.in1 += lo * stride_; d.out += lo * stride_; }
-                ck(bce_eval_gates_strided(cc, (uint32_t)B.size(), B.data(), K, stride_), "Clock(stage B)");
-                ++stats_.sublaunches;
-            }
+            evalStrided(A, lo, hi - lo, "Clock(stage A)");
+            evalStrided(B, lo, hi - lo, "Clock(stage B)");
         } else {
             // reference shape: one Gate::Evaluate per gate (src/circuit.cpp:698-710)
             GateEvalParams p = gep;
@@ -1263,33 +872,10 @@ void Circuit::executeRound(size_t level) {
             }
         }
     }
-    exchangeLevel(level);
+    if (gateSharded()) exchangeWires(shard_.publish[level]);   // wires of this level whose consumers sit on other ranks
 
-    // retire: counters (once per evaluation, src/circuit.cpp:722-749) and OUTPUT gates (:796-807)
-    std::vector<uint32_t> oslots;
-    std::vector<std::pair<unsigned, int>> obits;
-    for (size_t k = 0; k < L.gates.size(); ++k) {
-        const GateRec& g = allGates[L.gates[k]];
-        switch (g.op) {
-            case GateEnum::OUTPUT: ++n_output_gates; break;
-            case GateEnum::NOT: ++n_not_gates; break;
-            case GateEnum::AND: ++n_and_gates; break;
-            case GateEnum::OR: ++n_or_gates; break;
-            case GateEnum::XOR: ++n_xor_gates; break;
-            default: break;
-        }
-        if (g.op != GateEnum::OUTPUT) continue;
-        if (!encrypted_flag && !plaintext_flag) std::cerr << "Error either encrypted or plaintext flag must be set" << std::endl;
-        for (unsigned i = lo; i < hi; ++i) {
-            if (encrypted_flag) { oslots.push_back(i * stride_ + g.in[0]); obits.push_back({i, g.out_bit}); }
-            else circuitOut[i][g.out_bit] = plain_[i][g.in[0]];
-        }
-    }
-    if (!oslots.empty()) {
-        std::vector<uint8_t> res(oslots.size());
-        ck(bce_decrypt_bits(cc, oslots.data(), (uint32_t)oslots.size(), res.data()), "Clock(Decrypt)");
-        for (size_t k = 0; k < oslots.size(); ++k) circuitOut[obits[k].first][obits[k].second] = res[k];
-    }
+    countGates(&L.gates);
+    decryptOutputs(lo, hi, &L.gates);
 }
 
 Outputs Circuit::Clock() {
@@ -1376,15 +962,14 @@ bce_circuit_info Circuit::info() const {
     I.n_input_bits[1] = n_in_bits_.size() > 1 ? n_in_bits_[1] : 0;
     I.n_output_bits = n_output_bits.empty() ? 0 : n_output_bits[0];
     I.n_levels = (uint32_t)levels_.size();
-    I.n_relevel_steps = (uint32_t)relevel_plan_.size();
+    I.n_relevel_steps = (uint32_t)steps_.steps.size();
     I.slot_stride = stride_;
     for (const auto& L : levels_) {
         uint32_t a = 0, b = 0;
         for (int gi : L.gates) {
-            GateEnum op = allGates[gi].op;
-            if (op == GateEnum::AND || op == GateEnum::OR) ++a;
-            if (op == GateEnum::XOR && xor_fast_) ++a;
-            else if (op == GateEnum::XOR) { a += 2; ++b; }
+            const uint32_t w = sched::gate_weight(sched_op(allGates[gi].op), xor_fast_);   // 3 = XOR: two ANDs in stage A, their OR in stage B
+            a += w == 3 ? 2 : w;
+            b += w == 3;
         }
         if (a) ++I.n_sublaunches;
         if (b) ++I.n_sublaunches;

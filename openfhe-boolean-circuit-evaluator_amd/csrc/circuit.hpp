@@ -12,10 +12,12 @@
 #include <cstdint>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/bce_circuit.h"
 #include "../../include/bce_gpu.h"
+#include "schedule.hpp"
 
 namespace bce {
 
@@ -130,8 +132,8 @@ public:
     void setRelevel(bool b) { relevel_ = b; }
     bool getRelevel() const { return relevel_; }
     // the bootstrap-depth schedule fills its steps by slack up to the launch staircase of the engine (default on; see
-    // buildRelevelPlan).  lone / full = 0: ask the engine (bce_launch_capacity), else use these capacities (tests).
-    void setBalance(bool on, uint32_t lone = 0, uint32_t full = 0);
+    // sched::place_by_slack).  lone / full = 0: ask the engine (bce_launch_capacity), else use these capacities (tests).
+    void setBalance(bool on, uint32_t lone = 0, uint32_t full = 0) { balance_ = on; cap_lone_ = lone; cap_full_ = full; rebuildRelevel(); }
     // opt-in: hand the engine the whole bootstrap DAG (bce_dag_*): ONE persistent launch per Clock() in which a finished
     // bootstrap releases its consumers on the device -- the ready-gate rule of the reference's manager
     // (src/circuit.cpp:575-683) applied per gate instead of per frontier.  Same ciphertexts in every register as the
@@ -144,14 +146,14 @@ public:
     // host call per step.  Same ciphertexts.  Not with gate sharding (the per-step exchange is a host call) or verify mode.
     void setGraph(bool b) { graph_ = b; }
     bool getGraph() const { return graph_; }
-    bool graphActive() const;
-    bool dataflowActive() const;
-    const std::vector<bce_gate_desc>& dataflowTasks() const { return dag_tasks_; }
-    const std::vector<uint8_t>& dataflowPriorities() const { return dag_prio_; }
+    bool graphActive() const { return graph_ && cc && relevel_ && !dataflowActive() && !verify_flag && !gateSharded(); }
+    bool dataflowActive() const { return dataflow_ && cc && !verify_flag && !gateSharded() && bce_dag_supported(cc) && !tasks_.tasks.empty(); }
+    const std::vector<bce_gate_desc>& dataflowTasks() const { return tasks_.tasks; }
+    const std::vector<uint8_t>& dataflowPriorities() const { return tasks_.prio; }
     bool getBalance() const { return balance_; }
     std::vector<uint32_t> relevelStepSizes() const;          // bootstraps per step, one instance
     std::vector<uint32_t> relevelPublications() const;       // registers this rank publishes per step (gate sharding)
-    bool checkRelevelPlan(std::string* why = nullptr) const; // every step reads only what earlier steps wrote
+    bool checkRelevelPlan(std::string* why = nullptr) const { return sched::check(steps_, net_, rank_, gateSharded() ? world_ : 1, why); }
     bool getXorFast() const { return xor_fast_; }
     void setQuiet(bool q) { quiet_ = q; }
     // re-arm for another Clock() on the SAME inputs: keeps mode flags and the input ciphertexts
@@ -207,9 +209,7 @@ private:
     std::map<uint32_t, int> wire_of_reg_;
     std::vector<uint32_t> fan_off_, fan_gate_;  // CSR wire -> consumer gates
     std::vector<Level> levels_;
-    std::vector<int> gate_level_;
     uint32_t max_level_xor_ = 0, stride_ = 0;
-    unsigned n_outputs = 1;
     std::vector<unsigned> n_output_bits;
     std::vector<unsigned> n_in_bits_;      // width of every input bus (In1, In2, ...)
     std::vector<unsigned> out_bus_bits_;   // width of every output bus; output bit indices run over their concatenation
@@ -232,48 +232,43 @@ private:
     uint64_t xcap_ = 0;
     bool rccl_ = false;  // device payloads through bce_rccl_allgather on the engine stream (no host sync, no callback)
     bool shard_locality_ = true;  // gate sharding on the bootstrap-depth schedule: a unit goes to the rank that produced its inputs
-    std::vector<std::vector<uint8_t>> owner_;                 // [level][k] owner rank of levels_[level].gates[k]
-    std::vector<std::vector<std::vector<int>>> xwires_;       // [level][rank] -> wires that rank must publish
+    sched::LevelShard shard_;     // gate-level rounds under gate sharding: owner of levels_[level].gates[k], publications per level
+    bool gateSharded() const { return world_ > 1 && shard_mode_ == 1; }       // every step's / level's gates are split over the ranks
+    bool instanceSharded() const { return world_ > 1 && shard_mode_ == 0; }   // every rank evaluates its share of the instances
 
     int addWire(uint32_t reg);
     int wireOf(uint32_t reg, const char* what, unsigned lineNo) const;
     void finalizeNetlist();
     void buildShardPlan();
-    void instanceRange(unsigned& lo, unsigned& hi) const;
-    struct RStep { std::vector<bce_gate_desc> descs; };
+    std::pair<unsigned, unsigned> instanceRange() const;   // [lo, hi): the instances this rank evaluates
     bool relevel_ = true;   // the bootstrap-depth schedule is the default since round 4 (identical registers, 416 instead of 496
                             // dependent launches on AES-expanded); setRelevel(false) = the reference's gate-level rounds, src/circuit.cpp:532-573
-    std::vector<RStep> relevel_plan_;          // bootstrap-depth schedule (built lazily)
-    std::vector<bce_gate_desc> relevel_nots_;  // NOT wires that OUTPUT gates read: materialised at the end
-    uint32_t relevel_stride_ = 0, base_stride_ = 0, relevel_K_ = 0;
+    sched::Dag net_;          // the levelised netlist as the schedule module reads it
+    sched::Units units_;      // rebuilt when the netlist or xor_fast_ changes
+    sched::StepPlan steps_;   // bootstrap-depth schedule: redone when K, capacities, world, locality or balance change
+    sched::TaskList tasks_;   // dataflow schedule: held only while it is chosen
+    uint32_t base_stride_ = 0;
     bool balance_ = true;
     uint32_t cap_lone_ = 0, cap_full_ = 0;
-    void launchCapacity(uint32_t& lone, uint32_t& full) const;
-    struct Unit { uint32_t asap, start; uint8_t lat, owner; bce_gate_desc d; int32_t p0, p1; };   // XOR (lat 2): d holds (in0, in1, out, n0, n1)
-    uint32_t buildUnits(std::vector<Unit>& units, std::vector<int>& base, std::vector<uint8_t>& neg) const;
-    static void unitSuccessorsAlap(const std::vector<Unit>& units, uint32_t D, std::vector<uint32_t>& soff, std::vector<uint32_t>& succ,
-                                   std::vector<uint32_t>& alap);
+    std::pair<uint32_t, uint32_t> launchCapacity() const;   // (lone, full) of the launch staircase: set by the caller, else the engine's
     bool dataflow_ = false;
     bce_dag* dag_ = nullptr;
     bool graph_ = false;
     bce_plan* plan_ = nullptr;                 // the schedule's descriptors resident on the device (and its captured graph)
     uint32_t plan_lo_ = 0, plan_K_ = 0, plan_stride_ = 0;
-    void dropPlan();
-    std::vector<bce_gate_desc> dag_tasks_;
-    std::vector<uint8_t> dag_prio_;
-    uint32_t dag_stride_ = 0;
-    void buildDagTasks();
-    void dropDag();
+    void dropPlan() { if (plan_) { bce_plan_destroy(cc, plan_); plan_ = nullptr; } }
+    void dropDag() { if (dag_) { bce_dag_destroy(cc, dag_); dag_ = nullptr; } }
     void clockDataflow();
     void finishReleveled(unsigned lo, unsigned hi);
-    void buildRelevelPlan();
     void rebuildRelevel();
+    std::vector<bce_gate_desc> rebased(std::vector<bce_gate_desc> descs, unsigned lo) const;   // descriptors of instance 0 -> instance lo
+    void evalStrided(const std::vector<bce_gate_desc>& descs, unsigned lo, uint32_t K, const char* what);   // one launch, if any
+    void decryptOutputs(unsigned lo, unsigned hi, const std::vector<int>* gates);   // OUTPUT gates among `gates` (nullptr: all) -> circuitOut
+    void countGates(const std::vector<int>* gates);
     void clockReleveled();
     void managerRound(size_t level);
     void executeRound(size_t level);
-    void exchangeLevel(size_t level);
     void exchangeWires(const std::vector<std::vector<int>>& pub);
-    std::vector<std::vector<std::vector<int>>> relevel_xw_;  // [step][rank] -> wires that rank publishes after the step (gate sharding)
     void gatherOutputs();
     void requireEngine(const char* what) const;
     void ck(int rc, const char* what) const;

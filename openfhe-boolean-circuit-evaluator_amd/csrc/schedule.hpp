@@ -1,0 +1,71 @@
+// schedule.hpp -- host-only scheduling of a gate DAG: which bootstrap runs in which step, on which rank, in which slot.
+// Pure functions over plain data: no engine call, no environment, no output.  From the engine's header only the
+// descriptor struct and the BCE_* op codes are used, so the module compiles and is tested on its own
+// (tests/integration/schedule_selftest.cpp).
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/bce_gpu.h"
+
+namespace bce::sched {
+
+enum class Op : uint8_t { NOT, AND, OR, XOR, OUTPUT };
+struct DagGate { Op op; int in0, in1, out; };   // in1 = -1 for NOT / OUTPUT, out = -1 for OUTPUT
+struct Dag {
+    uint32_t n_wires = 0;
+    std::vector<DagGate> gates;        // level order, file order within a level
+    std::vector<uint32_t> level_off;   // gates[level_off[l] .. level_off[l + 1]) = level l
+    std::vector<int> outputs;          // the wires the OUTPUT gates read, in FILE order
+};
+
+uint32_t gate_weight(Op op, bool xor_fast);   // bootstraps per gate (src/gate.cpp:133,172,200-202)
+// the ONE place that spells the XOR: (a AND !b) -> t1, (!a AND b) -> t2 with u's own negations folded in, then t1 OR t2 -> u.out
+void xor_lower(const bce_gate_desc& u, uint32_t t1, uint32_t t2, bce_gate_desc out[3]);
+
+// Units of the schedule: a single bootstrap (AND / OR / XOR_FAST; its output is ready one step later) or an XOR built as
+// the reference builds it (lat 2: two ANDs in step `start`, their OR in step start + 1; d holds in0, in1, out, neg0, neg1).
+struct Unit {
+    uint32_t asap, start;
+    uint8_t lat, owner;
+    bce_gate_desc d;
+    int32_t p0, p1;   // producing units of the inputs, -1 = primary input / constant
+    uint32_t weight() const { return lat == 2 ? 2 : 1; }   // bootstraps in the unit's start step
+};
+struct Units {   // a function of (netlist, xor_fast) except Unit::start and Unit::owner, which placement and assign_owners set
+    std::vector<Unit> units;             // topological order
+    std::vector<int> base;               // wire -> wire at the bottom of its NOT chain
+    std::vector<uint8_t> neg;            // wire -> parity of that chain
+    uint32_t depth = 0;                  // bootstrap depth D = steps of the schedule
+    std::vector<uint32_t> soff, succ, alap;   // successors (CSR) and ALAP start steps
+};
+Units build_units(const Dag&, bool xor_fast);
+inline void place_asap(Units& S) { for (auto& u : S.units) u.start = u.asap; }
+// the same D steps filled by SLACK: a step of K x count bootstraps is topped up to the next stair of the launch staircase
+// (`lone` bootstraps cost one latency, then one round per `full`) with the ready units of least slack
+void place_by_slack(Units&, uint64_t K, uint32_t lone, uint32_t full);
+// gate sharding: split every step's units over `world` ranks; locality = follow the inputs' ranks unless that publishes more
+void assign_owners(Units&, uint32_t world, bool locality);
+std::vector<uint8_t> crossing(const Units&);   // per unit: a consumer unit sits on another rank
+
+struct StepPlan {
+    std::vector<std::vector<bce_gate_desc>> steps;
+    std::vector<bce_gate_desc> output_nots;                  // NOT wires that OUTPUT gates read: materialised at the end
+    std::vector<std::vector<std::vector<int>>> publish;      // [step][rank] -> wires that rank publishes after the step
+    uint32_t stride = 0, K = 0;
+};
+StepPlan lower_steps(const Units&, const Dag&, uint32_t rank, uint32_t world, uint64_t K);   // world 1 = not sharded
+struct TaskList { std::vector<bce_gate_desc> tasks; std::vector<uint8_t> prio; uint32_t stride = 0; };
+TaskList lower_tasks(const Units&, uint32_t n_wires);   // SSA: every XOR owns its temporaries; prio = slack class
+// every step reads only what earlier steps wrote (or received), every XOR temporary is read one step after it is written
+bool check(const StepPlan&, const Dag&, uint32_t rank, uint32_t world, std::string* why = nullptr);
+
+// gate sharding of the gate-LEVEL rounds: owner of every gate of a level (0xFF = everyone: OUTPUT), publications after it
+struct LevelShard {
+    std::vector<std::vector<uint8_t>> owner;                 // [level][k]
+    std::vector<std::vector<std::vector<int>>> publish;      // [level][rank]
+};
+LevelShard shard_levels(const Dag&, uint32_t world, bool xor_fast);
+
+}  // namespace bce::sched
