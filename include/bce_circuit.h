@@ -100,7 +100,8 @@ int bce_circuit_set_xor_fast(bce_circuit*, int on);
  * 0.82 s instead of 1.02 s).  DEFAULT ON since round 4: a caller that writes the reference's own sequence (Circuit; ReadFile;
  * Reset; setEncrypted; SetInput; Clock -- src/test_aes.cpp:338-343) gets it with slack-filled steps and the schedule's
  * descriptors resident on the device.  on = 0 restores the reference's Clock rounds (src/circuit.cpp:532-573: one round per
- * gate level, NOT gates materialised).  Gate-level rounds also run whenever a plaintext pass rides along (verify mode) or
+ * gate level, NOT gates materialised).  Gate-level rounds also run whenever a plaintext pass rides along (verify mode, unless its
+ * checks run on the device: bce_circuit_set_device_verify) or
  * with bce_circuit_set_batched(0).  Registers of NOT gates hold a ciphertext only under the gate-level rounds (or when an
  * OUTPUT gate reads them). */
 int bce_circuit_set_relevel(bce_circuit*, int on);
@@ -134,9 +135,27 @@ int bce_circuit_dataflow_active(const bce_circuit*);   /* 1 if the next encrypte
 /* Opt-in for the bootstrap-depth schedule (set_relevel): its launches are captured once into a hipGraph and every
  * Clock() replays them with one launch (bce_plan_run) -- no per-step host call between the dependent kernels.  Same
  * ciphertexts.  Without it the same resident descriptors are walked step by step (bce_plan_run_step).  Not with gate
- * sharding (the per-step exchange is a host call), verify mode or the dataflow schedule: bce_circuit_graph_active tells. */
+ * sharding (the per-step exchange is a host call), verify mode on the host path (with bce_circuit_set_device_verify the checks
+ * are captured with the steps) or the dataflow schedule: bce_circuit_graph_active tells. */
 int bce_circuit_set_graph(bce_circuit*, int on);
 int bce_circuit_graph_active(const bce_circuit*);
+/* Opt-in (default off): verify mode -- the reference's harnesses all run with setVerify(true): every gate output is
+ * decrypted, compared with the plaintext pass, reported as "Bad <OP> fixing" and replaced, src/gate.cpp:153-160 -- with the
+ * check ON THE DEVICE, between the steps of the bootstrap-depth schedule (bce_plan_set_checks of bce_gpu.h), instead of the
+ * gate-level rounds with one host decryption per level.  Active (bce_circuit_device_verify_active) when it is on, verify is
+ * on, launches are batched, the bootstrap-depth schedule is selected and there is no gate sharding; otherwise the host path
+ * runs unchanged.  Clock() then runs the plaintext pass for all levels first, hands its bits to the plan as expected values,
+ * runs the plan step by step (or as one hipGraph under bce_circuit_set_graph), reads the report once, prints one
+ * "Bad <OP> fixing" line per logged mismatch to stderr and adds the mismatches to verify_fixes; OUTPUT gates are compared
+ * after decryption and counted, not repaired, as on the host path.  Two deliberate differences to the host path:
+ *   - a repaired register holds the TRIVIAL ciphertext (0, ..., 0, bit q/4) instead of a fresh cc.Encrypt(sk, bit);
+ *   - NOT gates have no register on this schedule, so a wrong NOT input shows up at its consumer: fix counts can differ
+ *     from the gate-level path for that reason. */
+int bce_circuit_set_device_verify(bce_circuit*, int on);
+int bce_circuit_device_verify_active(const bce_circuit*);
+/* The device's report of the last Clock() on that path (all zero otherwise): checks, mismatches, repairs and the phase
+ * error statistics of every checked gate output (noise margin = q/8 - max_abs_err). */
+int bce_circuit_get_check_report(const bce_circuit*, bce_check_report* out);
 /* The task list of the dataflow schedule (what bce_dag_create receives): gates in topological order with SSA slots for
  * ONE instance (slot < slot_stride of bce_circuit_get_info) and their priority classes.  Writes min(*n_tasks, cap)
  * entries to each non-NULL array and sets *n_tasks to the number of tasks (= bootstraps of one evaluation). */

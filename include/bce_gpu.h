@@ -199,6 +199,42 @@ int bce_plan_run_step(bce_ctx*, bce_plan*, uint32_t step);
 int bce_plan_run(bce_ctx*, bce_plan*);
 void bce_plan_destroy(bce_ctx*, bce_plan*);
 
+/* ---- verify mode on the device -------------------------------------------------------------------------
+ * The reference's harnesses run their encrypted pass with setVerify(true): every gate output is decrypted, compared with
+ * the plaintext pass and, on a mismatch, logged ("Bad <OP> fixing") and replaced (src/gate.cpp:113-120,153-160,174-181,
+ * 206-213).  The check is one inner product of n words per ciphertext; here it runs on the engine's stream, between the
+ * steps of a schedule, against a device copy of the LWE secret (int8, uploaded with the keys):
+ *   phase = b - <a, s> mod q;  got = Round(4 phase / q);  err = phase - expect q/4, centred into (-q/2, q/2];
+ *   a check is a MISMATCH iff got != expect.
+ * Counters accumulate in one report block per context until bce_check_reset; the first BCE_CHECK_LOG_CAP mismatches are
+ * also logged (`mismatches` keeps counting beyond that).  err of EVERY checked ciphertext enters max_abs_err / sum_err /
+ * sum_sq_err: the measured noise of the run (margin = q/8 - max_abs_err).
+ * repair != 0 overwrites a mismatching ciphertext with the TRIVIAL encryption (0, ..., 0, expect q/4).  This deviates from
+ * the reference's cc.Encrypt(sk, bit) on purpose: it needs no device PRNG and no host round trip and makes repaired runs
+ * bit-reproducible; verify mode holds the secret key and the plaintext anyway, so nothing is disclosed. */
+enum { BCE_CHECK_LOG_CAP = 4096 };
+typedef struct bce_check_report { uint64_t checked, mismatches, repaired; int64_t sum_err; uint64_t sum_sq_err;
+                                  uint32_t max_abs_err, log_count; } bce_check_report;
+typedef struct bce_check_entry  { uint32_t tag, index, instance, slot; int32_t err; uint8_t got, expect, pad[2]; } bce_check_entry;
+/* Check i of instance k reads slot slots[i] + k * slot_stride against expect[k * count + i] (0..3); the slots of one call
+ * are distinct.  Asynchronous, stream-ordered with the gate calls; `tag` comes back in the log entries.
+ * BCE_ERR_NO_KEYS without keys, BCE_ERR_POOL for a slot outside the pool, BCE_ERR_ARG for expect > 3 or null pointers. */
+int bce_check_slots(bce_ctx*, uint32_t count, const uint32_t* slots, const uint8_t* expect, uint32_t instances,
+                    uint32_t slot_stride, int repair, uint32_t tag);
+/* Checks attached to a plan: step s checks check_sizes[s] slots (0 allowed), `slots` = the instance-0 numbers of all steps
+ * back to back (the plan's slot_base is added).  The lists stay resident next to the plan's descriptors; from then on
+ * bce_plan_run_step(s) and the graph of bce_plan_run launch the check after the kernels of step s, with tag = s.  A plan
+ * that was already captured is captured again at its next bce_plan_run.  All sizes 0 (or check_sizes NULL) detaches. */
+int bce_plan_set_checks(bce_ctx*, bce_plan*, const uint32_t* check_sizes /*[n_steps]*/, const uint32_t* slots, int repair);
+/* The expected bits of the next run(s), expect[instances][sum(check_sizes)], copied into one fixed device buffer of the
+ * plan (a captured graph stays valid from one run to the next).  A plan with checks that is run before this call:
+ * BCE_ERR_STATE. */
+int bce_plan_set_expected(bce_ctx*, bce_plan*, const uint8_t* expect);
+int bce_check_reset(bce_ctx*);
+/* synchronises; log (may be NULL with log_cap 0) receives min(report->log_count, log_cap) entries, in no particular order;
+ * report->log_count = entries the device logged (<= BCE_CHECK_LOG_CAP) */
+int bce_check_get(bce_ctx*, bce_check_report*, bce_check_entry* log, uint32_t log_cap);
+
 /* ---- the hot path, dependency-driven ------------------------------------------------------------------
  * The reference alternates Circuit::_ManageGates (a gate is ready when every input wire has arrived,
  * src/circuit.cpp:575-683) with Circuit::_ExecuteGates (src/circuit.cpp:685-817) once per frontier.  A bce_dag

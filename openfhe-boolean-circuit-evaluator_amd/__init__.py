@@ -55,6 +55,27 @@ class Timing(C.Structure):
                 ("fused_tail_launches", C.c_uint64)]
 
 
+class CheckReport(C.Structure):
+    _fields_ = [("checked", C.c_uint64), ("mismatches", C.c_uint64), ("repaired", C.c_uint64), ("sum_err", C.c_int64),
+                ("sum_sq_err", C.c_uint64), ("max_abs_err", C.c_uint32), ("log_count", C.c_uint32)]
+
+
+class CheckEntry(C.Structure):
+    _fields_ = [("tag", C.c_uint32), ("index", C.c_uint32), ("instance", C.c_uint32), ("slot", C.c_uint32),
+                ("err", C.c_int32), ("got", C.c_uint8), ("expect", C.c_uint8), ("pad", C.c_uint8 * 2)]
+
+
+CHECK_LOG_CAP = 4096
+
+
+def _report_dict(r, q):
+    """counters of a bce_check_report + the measured noise: rms of the phase error and the margin left to a wrong bit"""
+    d = {k: int(getattr(r, k)) for k, _ in CheckReport._fields_}
+    d["noise_rms"] = (d["sum_sq_err"] / d["checked"]) ** 0.5 if d["checked"] else 0.0
+    d["margin"] = q // 8 - d["max_abs_err"]
+    return d
+
+
 ENGINE_SYMBOLS = [
     "bce_ctx_create", "bce_ctx_create_custom", "bce_ctx_destroy", "bce_last_error", "bce_get_params",
     "bce_keygen", "bce_import_keys", "bce_import_keys_eval", "bce_export_bsk_eval", "bce_import_keys_file", "bce_export_keys_file", "bce_bsk_words", "bce_ksk_words", "bce_export_sk", "bce_export_bsk",
@@ -64,6 +85,7 @@ ENGINE_SYMBOLS = [
     "bce_rccl_shutdown", "bce_debug_eval_stages", "bce_debug_ntt", "bce_debug_tail",
     "bce_dag_supported", "bce_dag_create", "bce_dag_run", "bce_dag_destroy", "bce_dag_set_limits", "bce_dag_last_run", "bce_dag_debug_block_task",
     "bce_plan_create", "bce_plan_run_step", "bce_plan_run", "bce_plan_destroy",
+    "bce_check_slots", "bce_plan_set_checks", "bce_plan_set_expected", "bce_check_reset", "bce_check_get",
 ]
 
 _lib = None
@@ -166,6 +188,11 @@ def lib():
     L.bce_plan_run.argtypes = [vp, vp]
     L.bce_plan_destroy.argtypes = [vp, vp]
     L.bce_plan_destroy.restype = None
+    L.bce_check_slots.argtypes = [vp, u32, vp, vp, u32, u32, i32, u32]
+    L.bce_plan_set_checks.argtypes = [vp, vp, vp, vp, i32]
+    L.bce_plan_set_expected.argtypes = [vp, vp, vp]
+    L.bce_check_reset.argtypes = [vp]
+    L.bce_check_get.argtypes = [vp, C.POINTER(CheckReport), C.POINTER(CheckEntry), u32]
     _lib = L
     return L
 
@@ -402,6 +429,36 @@ class BinFHEContext:
     def plan_destroy(self, plan):
         self._L.bce_plan_destroy(self.h, plan)
 
+    # --- verify mode on the device: decrypt, compare, repair (bce_check_*) ---
+    def check_slots(self, slots, expect, instances=1, slot_stride=0, repair=False, tag=0):
+        """expect[instances][len(slots)]: asynchronous check of slots[i] + k * slot_stride against expect[k][i]"""
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        expect = np.ascontiguousarray(expect, dtype=np.uint8)
+        assert expect.size == slots.size * int(instances)
+        self._ck(self._L.bce_check_slots(self.h, slots.size, _p(slots), _p(expect), int(instances), int(slot_stride), int(bool(repair)), int(tag)))
+
+    def plan_set_checks(self, plan, checks, repair=False):
+        """checks: per step of the plan, the instance-0 slots to check after it (may be empty)"""
+        sizes = np.array([len(st) for st in checks], dtype=np.uint32)
+        slots = np.array([s for st in checks for s in st] or [0], dtype=np.uint32)
+        self._ck(self._L.bce_plan_set_checks(self.h, plan, _p(sizes), _p(slots), int(bool(repair))))
+
+    def plan_set_expected(self, plan, expect):
+        """expect[instances][total checks] of the next run(s)"""
+        expect = np.ascontiguousarray(expect, dtype=np.uint8)
+        self._ck(self._L.bce_plan_set_expected(self.h, plan, _p(expect)))
+
+    def check_reset(self):
+        self._ck(self._L.bce_check_reset(self.h))
+
+    def check_get(self):
+        """(report dict incl. noise_rms and margin, log entries as dicts); synchronises"""
+        r = CheckReport()
+        log = (CheckEntry * CHECK_LOG_CAP)()
+        self._ck(self._L.bce_check_get(self.h, C.byref(r), log, CHECK_LOG_CAP))
+        keys = ("tag", "index", "instance", "slot", "err", "got", "expect")
+        return _report_dict(r, self.params["q"]), [{k: int(getattr(log[i], k)) for k in keys} for i in range(r.log_count)]
+
     def dag_debug_block_task(self, dag, t):
         self._ck(self._L.bce_dag_debug_block_task(dag, int(t)))
 
@@ -516,7 +573,7 @@ CIRCUIT_SYMBOLS = [
     "bce_circuit_create", "bce_circuit_destroy", "bce_circuit_last_error", "bce_circuit_read_file",
     "bce_circuit_read_bristol", "bce_circuit_get_info", "bce_circuit_reset", "bce_circuit_rearm", "bce_circuit_set_plaintext",
     "bce_circuit_set_encrypted", "bce_circuit_set_verify", "bce_circuit_get_flags", "bce_circuit_set_batched",
-    "bce_circuit_set_encrypt_mode", "bce_circuit_get_encrypt_mode", "bce_circuit_plan_hash", "bce_circuit_set_shard_locality", "bce_circuit_set_xor_fast", "bce_circuit_set_relevel", "bce_circuit_get_relevel", "bce_circuit_set_dataflow", "bce_circuit_dataflow_active", "bce_circuit_set_graph", "bce_circuit_graph_active", "bce_circuit_dataflow_plan", "bce_circuit_set_balance", "bce_circuit_relevel_steps", "bce_circuit_relevel_publications", "bce_circuit_check_relevel", "bce_circuit_set_instances", "bce_circuit_set_input", "bce_circuit_clock",
+    "bce_circuit_set_encrypt_mode", "bce_circuit_get_encrypt_mode", "bce_circuit_plan_hash", "bce_circuit_set_shard_locality", "bce_circuit_set_xor_fast", "bce_circuit_set_relevel", "bce_circuit_get_relevel", "bce_circuit_set_dataflow", "bce_circuit_dataflow_active", "bce_circuit_set_graph", "bce_circuit_graph_active", "bce_circuit_set_device_verify", "bce_circuit_device_verify_active", "bce_circuit_get_check_report", "bce_circuit_dataflow_plan", "bce_circuit_set_balance", "bce_circuit_relevel_steps", "bce_circuit_relevel_publications", "bce_circuit_check_relevel", "bce_circuit_set_instances", "bce_circuit_set_input", "bce_circuit_clock",
     "bce_circuit_get_output", "bce_circuit_get_buses", "bce_circuit_get_counts", "bce_circuit_get_stats", "bce_circuit_dump",
     "bce_circuit_set_exchange", "bce_circuit_enable_rccl", "bce_circuit_exchange_capacity", "bce_assemble_bristol", "bce_pool_gather",
     "bce_pool_scatter",
@@ -549,6 +606,9 @@ def _bind_circuit():
     L.bce_circuit_set_dataflow.argtypes = [vp, i32]
     L.bce_circuit_set_graph.argtypes = [vp, i32]
     L.bce_circuit_graph_active.argtypes = [vp]
+    L.bce_circuit_set_device_verify.argtypes = [vp, i32]
+    L.bce_circuit_device_verify_active.argtypes = [vp]
+    L.bce_circuit_get_check_report.argtypes = [vp, C.POINTER(CheckReport)]
     L.bce_circuit_get_encrypt_mode.argtypes = [vp]
     L.bce_circuit_get_relevel.argtypes = [vp]
     L.bce_circuit_set_shard_locality.argtypes = [vp, i32]
@@ -733,6 +793,21 @@ class Circuit:
 
     def graphActive(self):
         return bool(self._L.bce_circuit_graph_active(self.h))
+
+    def setDeviceVerify(self, b):
+        """opt-in: verify mode's decrypt / compare / repair on the device, between the steps of the bootstrap-depth schedule
+        (src/gate.cpp:153-160); a repaired register holds the trivial ciphertext of the right bit"""
+        self._ck(self._L.bce_circuit_set_device_verify(self.h, int(b)))
+
+    def deviceVerifyActive(self):
+        return bool(self._L.bce_circuit_device_verify_active(self.h))
+
+    def check_report(self):
+        """the device's report of the last Clock() in device verify mode, with noise_rms = sqrt(sum_sq_err / checked) and
+        margin = q/8 - max_abs_err"""
+        r = CheckReport()
+        self._ck(self._L.bce_circuit_get_check_report(self.h, C.byref(r)))
+        return _report_dict(r, self.cc.params["q"] if self.cc is not None else 0)
 
     def dataflowActive(self):
         return bool(self._L.bce_circuit_dataflow_active(self.h))

@@ -657,25 +657,30 @@ void Circuit::setXorFast(bool b) {
     rebuildRelevel();
 }
 
-void Circuit::clockReleveled() {
-    if (verify_flag) throw std::logic_error("re-levelled schedule is not available in verify mode");
-    const auto [lo, hi] = instanceRange();
-    const uint32_t K = hi - lo;
+// the schedule's descriptors on the device (bce_plan), for the instances [lo, lo + K)
+void Circuit::ensurePlan(bce_plan*& plan, unsigned lo, uint32_t K) {
     if (steps_.steps.empty() || (balance_ && steps_.K != std::max(1u, K))) rebuildRelevel();
     if (steps_.stride > stride_) throw std::logic_error("re-levelled schedule needs more scratch slots than the pool stride");
     // the schedule's descriptors live on the device from the first Clock() on (bce_plan): a step is one call without an
     // upload; with setGraph the whole schedule is one hipGraph launch
-    if (plan_ && (plan_lo_ != lo || plan_K_ != K || plan_stride_ != stride_)) dropPlan();
-    if (!plan_ && K) {
+    if ((plan_ || vplan_) && (plan_lo_ != lo || plan_K_ != K || plan_stride_ != stride_)) dropPlan();
+    if (!plan && K) {
         std::vector<uint32_t> sizes;
         std::vector<bce_gate_desc> all;
         for (const auto& st : steps_.steps)
             if (!st.empty()) { sizes.push_back((uint32_t)st.size()); all.insert(all.end(), st.begin(), st.end()); }
         if (!sizes.empty()) {
-            ck(bce_plan_create(cc, (uint32_t)sizes.size(), sizes.data(), all.data(), K, stride_, lo * stride_, &plan_), "Clock(schedule upload)");
+            ck(bce_plan_create(cc, (uint32_t)sizes.size(), sizes.data(), all.data(), K, stride_, lo * stride_, &plan), "Clock(schedule upload)");
             plan_lo_ = lo; plan_K_ = K; plan_stride_ = stride_;
         }
     }
+}
+
+void Circuit::clockReleveled() {
+    if (verify_flag) throw std::logic_error("re-levelled schedule is not available in verify mode");
+    const auto [lo, hi] = instanceRange();
+    const uint32_t K = hi - lo;
+    ensurePlan(plan_, lo, K);
     if (plan_ && graphActive()) {
         ck(bce_plan_run(cc, plan_), "Clock(schedule graph)");
         for (const auto& st : steps_.steps) if (!st.empty()) ++stats_.sublaunches;
@@ -690,6 +695,74 @@ void Circuit::clockReleveled() {
         }
     }
     finishReleveled(lo, hi);
+    stats_.levels = (uint32_t)steps_.steps.size();
+}
+
+// ---- verify mode on the bootstrap-depth schedule: decrypt, compare, repair on the device (bce_plan_set_checks) -------
+// The reference checks every gate as it evaluates it (src/gate.cpp:113-120,153-160,174-181,206-213).  Here the plaintext
+// pass runs first for all levels, its bits become the expected values of the plan's per-step check lists, and the encrypted
+// pass stays on the resident plan (step by step or as one hipGraph); the report is read once, after the last step.
+void Circuit::clockDeviceVerify() {
+    const auto [lo, hi] = instanceRange();
+    const uint32_t K = hi - lo;
+    for (size_t l = 0; l < levels_.size(); ++l) plainRound(l);
+    ensurePlan(vplan_, lo, K);   // a plan of its own: the verify-off runs keep theirs (and its captured graph)
+    check_report_ = bce_check_report{};
+    if (vplan_) {
+        if (!vplan_checks_) {
+            const sched::CheckLists all = sched::check_lists(steps_, net_);
+            checks_ = {};
+            std::vector<uint32_t> sizes, slots;
+            for (size_t s = 0; s < steps_.steps.size(); ++s) {
+                if (steps_.steps[s].empty()) continue;   // the plan holds the non-empty steps
+                checks_.wires.push_back(all.wires[s]);
+                checks_.gates.push_back(all.gates[s]);
+                sizes.push_back((uint32_t)all.wires[s].size());
+                slots.insert(slots.end(), all.wires[s].begin(), all.wires[s].end());
+            }
+            ck(bce_plan_set_checks(cc, vplan_, sizes.data(), slots.data(), 1), "Clock(check lists)");
+            vplan_checks_ = true;
+        }
+        std::vector<uint8_t> expect;
+        for (unsigned i = lo; i < hi; ++i)
+            for (const auto& st : checks_.wires)
+                for (uint32_t w : st) expect.push_back(plain_[i][w]);
+        ck(bce_check_reset(cc), "Clock(check reset)");
+        if (!expect.empty()) ck(bce_plan_set_expected(cc, vplan_, expect.data()), "Clock(expected bits)");
+        if (graphActive()) {
+            ck(bce_plan_run(cc, vplan_), "Clock(schedule graph)");
+            stats_.sublaunches += (uint32_t)checks_.wires.size();
+        } else {
+            for (uint32_t ps = 0; ps < checks_.wires.size(); ++ps) {
+                ck(bce_plan_run_step(cc, vplan_, ps), "Clock(re-levelled step)");
+                ++stats_.sublaunches;
+            }
+        }
+        std::vector<bce_check_entry> log(BCE_CHECK_LOG_CAP);
+        ck(bce_check_get(cc, &check_report_, log.data(), (uint32_t)log.size()), "Clock(check report)");
+        for (uint32_t k = 0; k < check_report_.log_count; ++k) {
+            const bce_check_entry& e = log[k];
+            const char* name = "?";
+            if (e.tag < checks_.gates.size() && e.index < checks_.gates[e.tag].size()) {
+                const sched::Op op = net_.gates[checks_.gates[e.tag][e.index]].op;
+                name = op == sched::Op::AND ? "AND" : op == sched::Op::OR ? "OR" : "XOR";
+            }
+            std::cerr << "Bad " << name << " fixing" << std::endl;
+        }
+        if (check_report_.mismatches > check_report_.log_count)
+            std::cerr << "(" << (check_report_.mismatches - check_report_.log_count) << " more mismatches than the device log holds)" << std::endl;
+        stats_.verify_fixes += (uint32_t)check_report_.mismatches;
+    }
+    finishReleveled(lo, hi);
+    // OUTPUT gates: compared, counted and reported, not repaired (as the gate-level path does)
+    for (const GateRec& g : allGates) {
+        if (g.op != GateEnum::OUTPUT) continue;
+        for (unsigned i = lo; i < hi; ++i) {
+            if (circuitOut[i][g.out_bit] == plain_[i][g.in[0]]) continue;
+            std::cerr << "Bad OUTPUT fixing" << std::endl;
+            ++stats_.verify_fixes;
+        }
+    }
     stats_.levels = (uint32_t)steps_.steps.size();
 }
 
@@ -776,27 +849,33 @@ void Circuit::managerRound(size_t) {
     // (src/circuit.cpp:575-683: scanning waitingGates for every active wire) has no counterpart.
 }
 
+// the plaintext pass of one gate level, for this rank's instances (and, under gate sharding, its gates)
+void Circuit::plainRound(size_t level) {
+    const Level& L = levels_[level];
+    const auto [lo, hi] = instanceRange();
+    auto mine = [&](size_t k) { return !gateSharded() || shard_.owner[level][k] == 0xFF || shard_.owner[level][k] == rank_; };
+    for (unsigned i = lo; i < hi; ++i) {
+        auto& pv = plain_[i];
+        for (size_t k = 0; k < L.gates.size(); ++k) {
+            if (!mine(k)) continue;
+            const GateRec& g = allGates[L.gates[k]];
+            switch (g.op) {
+                case GateEnum::NOT: pv[g.out] = !pv[g.in[0]]; break;
+                case GateEnum::AND: pv[g.out] = pv[g.in[0]] && pv[g.in[1]]; break;
+                case GateEnum::OR: pv[g.out] = pv[g.in[0]] || pv[g.in[1]]; break;
+                case GateEnum::XOR: pv[g.out] = pv[g.in[0]] ^ pv[g.in[1]]; break;
+                default: break;
+            }
+        }
+    }
+}
+
 void Circuit::executeRound(size_t level) {
     const Level& L = levels_[level];
     const auto [lo, hi] = instanceRange();
     auto mine = [&](size_t k) { return !gateSharded() || shard_.owner[level][k] == 0xFF || shard_.owner[level][k] == rank_; };
 
-    if (plaintext_flag) {
-        for (unsigned i = lo; i < hi; ++i) {
-            auto& pv = plain_[i];
-            for (size_t k = 0; k < L.gates.size(); ++k) {
-                if (!mine(k)) continue;
-                const GateRec& g = allGates[L.gates[k]];
-                switch (g.op) {
-                    case GateEnum::NOT: pv[g.out] = !pv[g.in[0]]; break;
-                    case GateEnum::AND: pv[g.out] = pv[g.in[0]] && pv[g.in[1]]; break;
-                    case GateEnum::OR: pv[g.out] = pv[g.in[0]] || pv[g.in[1]]; break;
-                    case GateEnum::XOR: pv[g.out] = pv[g.in[0]] ^ pv[g.in[1]]; break;
-                    default: break;
-                }
-            }
-        }
-    }
+    if (plaintext_flag) plainRound(level);
     if (encrypted_flag) {
         requireEngine("Clock");
         const uint32_t tmp0 = (uint32_t)wire_names_.size();
@@ -895,10 +974,11 @@ Outputs Circuit::Clock() {
     size_t done_gates = 0;
     // gate-level rounds (the reference's Clock loop) whenever a plaintext pass rides along (verify mode) or the caller asked for
     // one Gate::Evaluate per gate (setBatched(false)); otherwise the bootstrap-depth schedule, unless setRelevel(false)
-    const bool releveled = (relevel_ || dataflow_) && encrypted_flag && !plaintext_flag && batched_;
+    // (or its checks run on the device: setDeviceVerify)
+    const bool releveled = ((relevel_ || dataflow_) && encrypted_flag && !plaintext_flag && batched_) || deviceVerifyActive();
     if (releveled) {
         auto t0 = Clock_t::now();
-        if (dataflowActive()) clockDataflow(); else clockReleveled();
+        if (deviceVerifyActive()) clockDeviceVerify(); else if (dataflowActive()) clockDataflow(); else clockReleveled();
         execution += ms_since(t0);
         done_gates = allGates.size();
     }

@@ -143,10 +143,21 @@ public:
     void setDataflow(bool b);
     bool getDataflow() const { return dataflow_; }
     // opt-in: replay the bootstrap-depth schedule's launches as ONE hipGraph per Clock() (bce_plan_run) instead of one
-    // host call per step.  Same ciphertexts.  Not with gate sharding (the per-step exchange is a host call) or verify mode.
+    // host call per step.  Same ciphertexts.  Not with gate sharding (the per-step exchange is a host call) or verify mode on
+    // the host path (setDeviceVerify: the checks are captured with the steps).
     void setGraph(bool b) { graph_ = b; }
     bool getGraph() const { return graph_; }
-    bool graphActive() const { return graph_ && cc && relevel_ && !dataflowActive() && !verify_flag && !gateSharded(); }
+    bool graphActive() const { return graph_ && cc && relevel_ && !dataflowActive() && (!verify_flag || deviceVerifyActive()) && !gateSharded(); }
+    // opt-in: verify mode (src/gate.cpp:153-160: decrypt every gate output, compare with the plaintext pass, "Bad <OP> fixing",
+    // replace) checked ON THE DEVICE between the steps of the bootstrap-depth schedule (bce_plan_set_checks) instead of the
+    // gate-level rounds with one host decryption per level.  Active with verify on, batched launches, the bootstrap-depth
+    // schedule and no gate sharding; otherwise the host path runs as before.  Differences to the host path: a repaired
+    // register holds the trivial ciphertext of the right bit (bce_gpu.h), and NOT gates have no register on this schedule, so
+    // a wrong NOT input is caught at its consumer -- fix counts can differ from the gate-level path for that reason.
+    void setDeviceVerify(bool b) { device_verify_ = b; }
+    bool getDeviceVerify() const { return device_verify_; }
+    bool deviceVerifyActive() const { return device_verify_ && verify_flag && encrypted_flag && cc && batched_ && relevel_ && !gateSharded(); }
+    const bce_check_report& checkReport() const { return check_report_; }   // of the last Clock() on the device path
     bool dataflowActive() const { return dataflow_ && cc && !verify_flag && !gateSharded() && bce_dag_supported(cc) && !tasks_.tasks.empty(); }
     const std::vector<bce_gate_desc>& dataflowTasks() const { return tasks_.tasks; }
     const std::vector<uint8_t>& dataflowPriorities() const { return tasks_.prio; }
@@ -256,7 +267,9 @@ private:
     bool graph_ = false;
     bce_plan* plan_ = nullptr;                 // the schedule's descriptors resident on the device (and its captured graph)
     uint32_t plan_lo_ = 0, plan_K_ = 0, plan_stride_ = 0;
-    void dropPlan() { if (plan_) { bce_plan_destroy(cc, plan_); plan_ = nullptr; } }
+    bce_plan* vplan_ = nullptr;                // the same schedule with the check lists of device verify mode attached (its own capture)
+    bool vplan_checks_ = false;                // ... once they are attached
+    void dropPlan() { for (bce_plan** p : {&plan_, &vplan_}) if (*p) { bce_plan_destroy(cc, *p); *p = nullptr; } vplan_checks_ = false; }
     void dropDag() { if (dag_) { bce_dag_destroy(cc, dag_); dag_ = nullptr; } }
     void clockDataflow();
     void finishReleveled(unsigned lo, unsigned hi);
@@ -266,6 +279,12 @@ private:
     void decryptOutputs(unsigned lo, unsigned hi, const std::vector<int>* gates);   // OUTPUT gates among `gates` (nullptr: all) -> circuitOut
     void countGates(const std::vector<int>* gates);
     void clockReleveled();
+    bool device_verify_ = false;
+    sched::CheckLists checks_;                 // of vplan_: per NON-EMPTY step of steps_ (= per step of the plan)
+    bce_check_report check_report_{};
+    void ensurePlan(bce_plan*& plan, unsigned lo, uint32_t K);  // the schedule's descriptors resident on the device
+    void clockDeviceVerify();
+    void plainRound(size_t level);             // the plaintext pass of one gate level
     void managerRound(size_t level);
     void executeRound(size_t level);
     void exchangeWires(const std::vector<std::vector<int>>& pub);

@@ -91,6 +91,13 @@ int bce_circuit_set_dataflow(bce_circuit* h, int on) { return guarded(h, [&] { h
 int bce_circuit_dataflow_active(const bce_circuit* h) { return h && h->c.dataflowActive() ? 1 : 0; }
 int bce_circuit_set_graph(bce_circuit* h, int on) { return guarded(h, [&] { h->c.setGraph(on != 0); }); }
 int bce_circuit_graph_active(const bce_circuit* h) { return h && h->c.graphActive() ? 1 : 0; }
+int bce_circuit_set_device_verify(bce_circuit* h, int on) { return guarded(h, [&] { h->c.setDeviceVerify(on != 0); }); }
+int bce_circuit_device_verify_active(const bce_circuit* h) { return h && h->c.deviceVerifyActive() ? 1 : 0; }
+int bce_circuit_get_check_report(const bce_circuit* h, bce_check_report* out) {
+    if (!h || !out) return BCE_ERR_ARG;
+    *out = h->c.checkReport();
+    return BCE_OK;
+}
 int bce_circuit_dataflow_plan(const bce_circuit* h, bce_gate_desc* tasks, uint8_t* prio, uint32_t cap, uint32_t* n_tasks) {
     if (!h || !n_tasks) return BCE_ERR_ARG;
     const auto& t = h->c.dataflowTasks();

@@ -30,6 +30,8 @@
 
 using namespace bce;
 
+static_assert(sizeof(bce_check_report) == 48 && sizeof(bce_check_entry) == 24, "layout of the check structs (include/bce_gpu.h; the kernel writes them)");
+
 namespace {
 
 thread_local std::string g_create_error;
@@ -134,6 +136,15 @@ struct bce_ctx {
     hipEvent_t ring_ev[kRing] = {nullptr, nullptr, nullptr, nullptr};
     bool ring_busy[kRing] = {false, false, false, false};
     int ring_pos = 0;
+    // verify mode on the device (bce_check_*): the LWE secret as int8[n padded to 64] (uploaded wherever `s` is set), the
+    // report block followed by the mismatch log, and the staging pair of bce_check_slots (slot list + expected bits)
+    int8_t* d_s8 = nullptr;
+    bce_check_report* d_check = nullptr;
+    bce_check_entry* d_check_log = nullptr;
+    char *d_chk_stage = nullptr, *h_chk_stage = nullptr;
+    size_t chk_cap = 0;
+    hipEvent_t chk_ev = nullptr;
+    bool chk_busy = false;
     // timing
     std::vector<EventPair> pending, free_events;
     bce_timing timing{};
@@ -472,6 +483,30 @@ int upload_ksk(bce_ctx* c, const u32* ksk) {
     return BCE_OK;
 }
 
+// the LWE secret as the device-side check reads it (k_lwe_check): int8[n], padded with zeros to a multiple of 64.  The
+// buffer is allocated once per context, so a captured plan's pointer to it survives a key import.
+int upload_secret(bce_ctx* c) {
+    const size_t padded = ((size_t)c->n + 63) / 64 * 64;
+    std::vector<int8_t> s8(padded, 0);
+    for (u32 k = 0; k < c->n; ++k) s8[k] = (int8_t)c->s[k];
+    if (!c->d_s8) HIP_TRY(c, hipMalloc(&c->d_s8, padded));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(c->d_s8, s8.data(), padded, hipMemcpyHostToDevice));
+    return BCE_OK;
+}
+
+// report block + mismatch log of the device-side checks: one allocation per context, zeroed
+int ensure_check(bce_ctx* c) {
+    if (c->d_check) return BCE_OK;
+    const size_t bytes = sizeof(bce_check_report) + (size_t)kCheckLogCap * sizeof(bce_check_entry);
+    void* p = nullptr;
+    HIP_TRY(c, hipMalloc(&p, bytes));
+    if (hipMemset(p, 0, bytes) != hipSuccess) { hipFree(p); return c->fail(BCE_ERR_HIP, "hipMemset(check report) failed"); }
+    c->d_check = static_cast<bce_check_report*>(p);
+    c->d_check_log = reinterpret_cast<bce_check_entry*>(static_cast<char*>(p) + sizeof(bce_check_report));
+    return BCE_OK;
+}
+
 int ensure_acc(bce_ctx* c, size_t boots) {
     if (boots <= c->acc_cap) return BCE_OK;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -805,6 +840,7 @@ void bce_ctx_destroy(bce_ctx* c) {
         if (c->ring_ev[i]) hipEventDestroy(c->ring_ev[i]);
     }
     hipFree(c->d_io); if (c->h_io) hipHostFree(c->h_io);
+    hipFree(c->d_s8); hipFree(c->d_check); hipFree(c->d_chk_stage); if (c->h_chk_stage) hipHostFree(c->h_chk_stage); if (c->chk_ev) hipEventDestroy(c->chk_ev);
     hipFree(c->d_P); if (c->h_dag_status) hipHostFree(c->h_dag_status); if (c->h_dag_stage) hipHostFree(c->h_dag_stage);
     hipFree(c->d_twf); hipFree(c->d_fwd_mfma); hipFree(c->d_psi); hipFree(c->d_psi_r2); hipFree(c->d_xcd_gate); hipFree(c->d_tw64); hipFree(c->d_tw64d); hipFree(c->d_bsk); hipFree(c->d_ksk); hipFree(c->d_pool); hipFree(c->d_acc); hipFree(c->d_tail_partial);
     if (c->stream) hipStreamDestroy(c->stream);
@@ -852,6 +888,7 @@ int bce_keygen(bce_ctx* c, const uint8_t seed_in[32]) {
     c->z.resize(N);
     { ChaChaStream st(seed, kDomSK, 0); for (u32 i = 0; i < n; ++i) c->s[i] = draw_ternary(st); }
     { ChaChaStream st(seed, kDomZ, 0); for (u32 i = 0; i < N; ++i) c->z[i] = draw_ternary(st); }
+    if ((rc = upload_secret(c))) return rc;
 
     KeygenDev D;
     KeygenParams kp{};
@@ -893,6 +930,7 @@ static int import_keys_impl(bce_ctx* c, const int32_t* s, const int32_t* z, cons
     c->s.assign(s, s + c->n);
     if (z) c->z.assign(z, z + c->N); else c->z.clear();
     std::memset(c->seed, 0, sizeof c->seed);   // imported keys have no generation seed
+    if ((rc = upload_secret(c))) return rc;
     {   // words -> device words, chunked; coefficient-domain words are then transformed in place on the device
         // (evaluation-form words arrive in the engine's own order: OpenFHE's bit-reversed CT order for the minimal
         // primitive 2N-th root, bce_get_params()[BCE_P_psi])
@@ -1152,7 +1190,7 @@ int bce_synchronize(bce_ctx* c) {
 
 struct bce_plan {
     std::vector<u32> off, cnt;                 // step s = descriptors [off[s], off[s] + cnt[s])
-    u32 instances = 0, slot_stride = 0;
+    u32 instances = 0, slot_stride = 0, slot_base = 0;
     u32 max_step = 0;                          // descriptors of the largest step
     u64 boots_per_run = 0;
     bce_gate_desc* d_descs = nullptr;          // all steps, resident
@@ -1166,6 +1204,16 @@ struct bce_plan {
     // the captured kernels hold the context's device pointers and kernel choices by value: what they were at capture
     const void* cap_ptrs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     u32 cap_flags[3] = {0, 0, 0};
+    // device-side checks (bce_plan_set_checks): step s checks the slots [chk_off[s], chk_off[s] + chk_cnt[s]) of d_chk_slots
+    // against the same range of every instance's row of d_expect ([instances][chk_total], one fixed buffer: the captured
+    // graph points into it; bce_plan_set_expected refills it through the pinned h_expect)
+    std::vector<u32> chk_off, chk_cnt;
+    u32 chk_total = 0;
+    int chk_repair = 0;
+    bool expected_set = false, expect_busy = false;
+    u32* d_chk_slots = nullptr;
+    uint8_t *d_expect = nullptr, *h_expect = nullptr;
+    hipEvent_t expect_ev = nullptr;
 };
 
 namespace {
@@ -1174,13 +1222,36 @@ bool plan_capture_is_current(const bce_ctx* c, const bce_plan* p) {
     const u32 flags[3] = {c->P.variant, c->P.fuse_tail, c->P.fold};
     return std::memcmp(now, p->cap_ptrs, sizeof now) == 0 && std::memcmp(flags, p->cap_flags, sizeof flags) == 0;
 }
+void plan_drop_capture(bce_plan* p) {
+    if (p->exec) { hipGraphExecDestroy(p->exec); p->exec = nullptr; }
+    if (p->graph) { hipGraphDestroy(p->graph); p->graph = nullptr; }
+}
+void plan_free_checks(bce_plan* p) {
+    hipFree(p->d_chk_slots); hipFree(p->d_expect);
+    if (p->h_expect) hipHostFree(p->h_expect);
+    if (p->expect_ev) hipEventDestroy(p->expect_ev);
+    p->d_chk_slots = nullptr; p->d_expect = nullptr; p->h_expect = nullptr; p->expect_ev = nullptr;
+    p->chk_off.clear(); p->chk_cnt.clear();
+    p->chk_total = 0; p->expected_set = p->expect_busy = false;
+}
+// the checks of plan step s, after its kernels (no allocation, no synchronisation: also runs under stream capture)
+int plan_check_step(bce_ctx* c, const bce_plan* p, size_t s) {
+    if (!p->chk_total || !p->chk_cnt[s]) return BCE_OK;
+    HIP_TRY(c, launch_lwe_check(c->P, c->d_s8, p->d_chk_slots + p->chk_off[s], p->d_expect + p->chk_off[s], p->chk_cnt[s], p->chk_total,
+                                p->instances, p->slot_stride, p->chk_repair, (u32)s, c->d_check, c->d_check_log, c->stream));
+    return BCE_OK;
+}
+int plan_checks_ready(bce_ctx* c, const bce_plan* p, const char* who) {
+    if (p->chk_total && !p->expected_set) return c->fail(BCE_ERR_STATE, "%s: the plan has checks but bce_plan_set_expected has not been called", who);
+    return BCE_OK;
+}
 }  // namespace
 
 extern "C" {
 
 static void plan_free(bce_plan* p) {
-    if (p->exec) hipGraphExecDestroy(p->exec);
-    if (p->graph) hipGraphDestroy(p->graph);
+    plan_drop_capture(p);
+    plan_free_checks(p);
     hipFree(p->d_descs); hipFree(p->d_acc); hipFree(p->d_partial);
     delete p;
 }
@@ -1206,7 +1277,7 @@ int bce_plan_create(bce_ctx* c, uint32_t n_steps, const uint32_t* step_sizes, co
     struct Deleter { bce_ctx* c; void operator()(bce_plan* p) const { bce_plan_destroy(c, p); } };
     std::unique_ptr<bce_plan, Deleter> p(new bce_plan, Deleter{c});
     { std::lock_guard<std::mutex> lk(g_live_mu); c->plans.insert(p.get()); }
-    p->instances = instances; p->slot_stride = slot_stride;
+    p->instances = instances; p->slot_stride = slot_stride; p->slot_base = slot_base;
     u64 total = 0;
     for (u32 s = 0; s < n_steps; ++s) {
         if (step_sizes[s] == 0) return c->fail(BCE_ERR_ARG, "bce_plan_create: step %u is empty", s);
@@ -1237,11 +1308,13 @@ int bce_plan_run_step(bce_ctx* c, bce_plan* p, uint32_t step) {
     if (!c || !p) return BCE_ERR_ARG;
     if (step >= p->cnt.size()) return c->fail(BCE_ERR_ARG, "bce_plan_run_step: step %u of %zu", step, p->cnt.size());
     if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "bce_keygen / bce_import_keys has not been called");
+    if (const int rc = plan_checks_ready(c, p, "bce_plan_run_step")) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const int rc = ensure_acc(c, (size_t)p->cnt[step] * p->instances);
     if (rc) return rc;
     const int rc2 = launch_bootstraps(c, p->d_descs + p->off[step], p->cnt[step], p->instances, p->slot_stride, c->d_acc, nullptr, nullptr, true, nullptr);
     if (rc2) return rc2;
+    if (const int rc3 = plan_check_step(c, p, step)) return rc3;
     if (c->pending.size() > 4096) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         drain_timing(c);
@@ -1252,12 +1325,12 @@ int bce_plan_run_step(bce_ctx* c, bce_plan* p, uint32_t step) {
 int bce_plan_run(bce_ctx* c, bce_plan* p) {
     if (!c || !p) return BCE_ERR_ARG;
     if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "bce_keygen / bce_import_keys has not been called");
+    if (const int rc = plan_checks_ready(c, p, "bce_plan_run")) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if (p->exec && !plan_capture_is_current(c, p)) {
         // the pool grew (bce_pool_reserve) or keys were re-imported since the capture: the graph's kernel arguments are stale
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        hipGraphExecDestroy(p->exec); p->exec = nullptr;
-        hipGraphDestroy(p->graph); p->graph = nullptr;
+        plan_drop_capture(p);
     }
     if (!p->exec) {
         // scratch of the captured launches, sized for the largest step
@@ -1273,6 +1346,7 @@ int bce_plan_run(bce_ctx* c, bce_plan* p) {
             bool f = false;
             rc = launch_bootstraps(c, p->d_descs + p->off[s], p->cnt[s], p->instances, p->slot_stride, p->d_acc, nullptr, nullptr, false, &f, p->d_partial);
             fused += f ? 1 : 0;
+            if (rc == BCE_OK) rc = plan_check_step(c, p, s);
         }
         hipGraph_t g = nullptr;
         const hipError_t e = hipStreamEndCapture(c->stream, &g);   // always end the capture, also after a failed launch
@@ -1299,6 +1373,114 @@ int bce_plan_run(bce_ctx* c, bce_plan* p) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         drain_timing(c);
     }
+    return BCE_OK;
+}
+
+// ---- verify mode on the device (include/bce_gpu.h, "verify mode on the device") -----------------------------------
+int bce_check_slots(bce_ctx* c, uint32_t count, const uint32_t* slots, const uint8_t* expect, uint32_t instances,
+                    uint32_t slot_stride, int repair, uint32_t tag) {
+    if (!c) return BCE_ERR_ARG;
+    if (!slots || !expect) return c->fail(BCE_ERR_ARG, "bce_check_slots: null pointer");
+    if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "bce_keygen / bce_import_keys has not been called");
+    if (count == 0 || instances == 0) return BCE_OK;
+    const u64 items = (u64)count * instances;
+    if (items > (1ull << 31)) return c->fail(BCE_ERR_ARG, "bce_check_slots: too many checks");
+    const u64 span = (u64)(instances - 1) * slot_stride;
+    for (u32 i = 0; i < count; ++i)
+        if (slots[i] + span >= c->pool_slots) return c->fail(BCE_ERR_POOL, "bce_check_slots: check %u: slot %llu outside the pool (%u slots)", i, (unsigned long long)(slots[i] + span), c->pool_slots);
+    for (u64 i = 0; i < items; ++i)
+        if (expect[i] > 3) return c->fail(BCE_ERR_ARG, "bce_check_slots: expect[%llu] = %u is not a message (0..3)", (unsigned long long)i, expect[i]);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = ensure_check(c)) return rc;
+    const size_t slot_bytes = (size_t)count * sizeof(u32), bytes = slot_bytes + items;
+    if (c->chk_busy) { HIP_TRY(c, hipEventSynchronize(c->chk_ev)); c->chk_busy = false; }   // the last upload has left the pinned buffer
+    if (bytes > c->chk_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        hipFree(c->d_chk_stage); if (c->h_chk_stage) hipHostFree(c->h_chk_stage);
+        c->d_chk_stage = c->h_chk_stage = nullptr; c->chk_cap = 0;
+        const size_t cap = std::max(bytes, (size_t)1 << 16);
+        HIP_TRY(c, hipMalloc(&c->d_chk_stage, cap));
+        HIP_TRY(c, hipHostMalloc(&c->h_chk_stage, cap));
+        c->chk_cap = cap;
+    }
+    if (!c->chk_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->chk_ev, hipEventDisableTiming));
+    std::memcpy(c->h_chk_stage, slots, slot_bytes);
+    std::memcpy(c->h_chk_stage + slot_bytes, expect, items);
+    HIP_TRY(c, hipMemcpyAsync(c->d_chk_stage, c->h_chk_stage, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(c->chk_ev, c->stream));
+    c->chk_busy = true;
+    HIP_TRY(c, launch_lwe_check(c->P, c->d_s8, reinterpret_cast<const u32*>(c->d_chk_stage), reinterpret_cast<const uint8_t*>(c->d_chk_stage + slot_bytes),
+                                count, count, instances, slot_stride, repair, tag, c->d_check, c->d_check_log, c->stream));
+    return BCE_OK;
+}
+
+int bce_plan_set_checks(bce_ctx* c, bce_plan* p, const uint32_t* check_sizes, const uint32_t* slots, int repair) {
+    if (!c || !p) return BCE_ERR_ARG;
+    if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "bce_keygen / bce_import_keys has not been called");
+    const size_t n_steps = p->cnt.size();
+    u64 total = 0;
+    for (size_t s = 0; check_sizes && s < n_steps; ++s) total += check_sizes[s];
+    if (total && !slots) return c->fail(BCE_ERR_ARG, "bce_plan_set_checks: null slot list");
+    if (total * p->instances > (1ull << 31)) return c->fail(BCE_ERR_ARG, "bce_plan_set_checks: too many checks");
+    const u64 span = (u64)p->slot_base + (u64)(p->instances - 1) * p->slot_stride;   // the span rule of bce_plan_create
+    std::vector<u32> shifted(total);
+    for (u64 i = 0; i < total; ++i) {
+        if (slots[i] + span >= c->pool_slots) return c->fail(BCE_ERR_POOL, "bce_plan_set_checks: check %llu: slot %llu outside the pool (%u slots)", (unsigned long long)i, (unsigned long long)(slots[i] + span), c->pool_slots);
+        shifted[i] = slots[i] + p->slot_base;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    plan_drop_capture(p);   // its launches would miss (or still hold) the old lists: captured again at the next bce_plan_run
+    plan_free_checks(p);
+    if (total == 0) return BCE_OK;
+    if (const int rc = ensure_check(c)) return rc;
+    for (size_t s = 0, at = 0; s < n_steps; ++s) { p->chk_off.push_back((u32)at); p->chk_cnt.push_back(check_sizes[s]); at += check_sizes[s]; }
+    const size_t ebytes = (size_t)total * p->instances;
+    HIP_TRY(c, hipMalloc(&p->d_chk_slots, total * sizeof(u32)));
+    HIP_TRY(c, hipMemcpy(p->d_chk_slots, shifted.data(), total * sizeof(u32), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMalloc(&p->d_expect, ebytes));
+    HIP_TRY(c, hipHostMalloc(&p->h_expect, ebytes));
+    HIP_TRY(c, hipEventCreateWithFlags(&p->expect_ev, hipEventDisableTiming));
+    p->chk_total = (u32)total;
+    p->chk_repair = repair;
+    return BCE_OK;
+}
+
+int bce_plan_set_expected(bce_ctx* c, bce_plan* p, const uint8_t* expect) {
+    if (!c || !p) return BCE_ERR_ARG;
+    if (!expect) return c->fail(BCE_ERR_ARG, "bce_plan_set_expected: null pointer");
+    if (!p->chk_total) return c->fail(BCE_ERR_STATE, "bce_plan_set_expected: the plan has no checks (bce_plan_set_checks)");
+    const size_t bytes = (size_t)p->chk_total * p->instances;
+    for (size_t i = 0; i < bytes; ++i)
+        if (expect[i] > 3) return c->fail(BCE_ERR_ARG, "bce_plan_set_expected: expect[%zu] = %u is not a message (0..3)", i, expect[i]);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (p->expect_busy) { HIP_TRY(c, hipEventSynchronize(p->expect_ev)); p->expect_busy = false; }
+    std::memcpy(p->h_expect, expect, bytes);
+    HIP_TRY(c, hipMemcpyAsync(p->d_expect, p->h_expect, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(p->expect_ev, c->stream));
+    p->expect_busy = true;
+    p->expected_set = true;
+    return BCE_OK;
+}
+
+int bce_check_reset(bce_ctx* c) {
+    if (!c) return BCE_ERR_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = ensure_check(c)) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->d_check, 0, sizeof(bce_check_report), c->stream));
+    return BCE_OK;
+}
+
+int bce_check_get(bce_ctx* c, bce_check_report* out, bce_check_entry* log, uint32_t log_cap) {
+    if (!c) return BCE_ERR_ARG;
+    if (!out || (log_cap && !log)) return c->fail(BCE_ERR_ARG, "bce_check_get: null pointer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = ensure_check(c)) return rc;
+    if (const int rc = sync_stream(c)) return rc;
+    HIP_TRY(c, hipMemcpy(out, c->d_check, sizeof *out, hipMemcpyDeviceToHost));
+    out->log_count = std::min<u32>(out->log_count, kCheckLogCap);   // the device counter goes on counting past the log's end
+    const u32 n = std::min(out->log_count, log_cap);
+    if (n) HIP_TRY(c, hipMemcpy(log, c->d_check_log, (size_t)n * sizeof *log, hipMemcpyDeviceToHost));
     return BCE_OK;
 }
 

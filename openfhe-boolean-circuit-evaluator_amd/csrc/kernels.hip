@@ -1982,6 +1982,86 @@ hipError_t launch_pool_pack(const DevParams& P, const bce_gate_desc* d, u32 coun
 }
 
 // ---------------------------------------------------------------------------------------
+// verify mode on the device: decrypt, compare with the plaintext pass, repair (src/gate.cpp:153-160)
+// ---------------------------------------------------------------------------------------
+// One wave per (check, instance) item at a time, kCheckWaves waves per workgroup, each wave walking the items with the
+// grid's stride.  Lane l loads words l, l + 64, ... of the row (rows are 4-byte aligned only: n + 1 words apart), so
+// word n = b falls to lane n % 64 of the last pass.  q is a power of two: 32-bit wrap-around sums are exact mod q.
+// The counters of a wave's items are summed in registers and reach the report block as one set of agent-scope atomics per
+// wave; the report is read by the host after the stream has drained, nothing in this launch reads it.
+// No LDS, no barrier.  Repair writes the TRIVIAL ciphertext (0, ..., 0, expect q/4) with vector stores.
+__global__ __launch_bounds__(64 * kCheckWaves) void k_lwe_check(u32* __restrict__ pool, u32 pool_stride, u32 n, u32 q,
+                                                               const int8_t* __restrict__ s, const u32* __restrict__ slots,
+                                                               const uint8_t* __restrict__ expect, u32 count, u32 expect_stride,
+                                                               u32 items, u32 slot_stride, int repair, u32 tag,
+                                                               bce_check_report* __restrict__ rep, bce_check_entry* __restrict__ log) {
+    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u32 qm = q - 1;
+    u32 checked = 0, bad_n = 0, fixed_n = 0, max_abs = 0;
+    int64_t sum = 0;
+    uint64_t sum_sq = 0;
+    for (u32 i = blockIdx.x * kCheckWaves + wave; i < items; i += gridDim.x * kCheckWaves) {   // wave-uniform
+        const u32 index = i % count, inst = i / count;
+        const u32 slot = slots[index] + inst * slot_stride;
+        const u32 want = expect[(size_t)inst * expect_stride + index];
+        u32* row = pool + (size_t)slot * pool_stride;
+        u32 acc = 0;
+        for (u32 k = lane; k <= n; k += 64) {
+            const u32 w = row[k];
+            acc += k < n ? 0u - w * (u32)(int)s[k] : w;   // b - sum a_k s_k
+        }
+        for (int off = 32; off; off >>= 1) acc += __shfl_down(acc, off);
+        const u32 phase = __shfl(acc, 0) & qm;
+        // bo_decrypt / bo_noise of the oracle, bce_decrypt_bits: Round(4 phase / q), and the centred distance to want q/4
+        const u32 got = (4 * ((phase + q / 8) & qm)) / q;
+        const u32 d = (phase - want * (q / 4)) & qm;
+        const int err = d > q / 2 ? (int)d - (int)q : (int)d;
+        const bool bad = got != want;
+        const u32 a = (u32)(err < 0 ? -err : err);
+        ++checked;
+        sum += err;
+        sum_sq += (uint64_t)a * a;
+        max_abs = a > max_abs ? a : max_abs;
+        if (bad) {
+            ++bad_n;
+            if (lane == 0) {
+                const u32 at = __hip_atomic_fetch_add(&rep->log_count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (at < kCheckLogCap) {
+                    bce_check_entry e;
+                    e.tag = tag; e.index = index; e.instance = inst; e.slot = slot; e.err = err;
+                    e.got = (uint8_t)got; e.expect = (uint8_t)want; e.pad[0] = e.pad[1] = 0;
+                    log[at] = e;
+                }
+            }
+            if (repair) {
+                ++fixed_n;
+                for (u32 k = lane; k <= n; k += 64) row[k] = k < n ? 0u : want * (q / 4);
+            }
+        }
+    }
+    if (lane == 0 && checked) {
+        __hip_atomic_fetch_add(&rep->checked, (uint64_t)checked, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (bad_n) __hip_atomic_fetch_add(&rep->mismatches, (uint64_t)bad_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (fixed_n) __hip_atomic_fetch_add(&rep->repaired, (uint64_t)fixed_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(&rep->sum_err, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(&rep->sum_sq_err, sum_sq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_max(&rep->max_abs_err, max_abs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+hipError_t launch_lwe_check(const DevParams& P, const int8_t* s, const u32* d_slots, const uint8_t* d_expect, u32 count,
+                            u32 expect_stride, u32 instances, u32 slot_stride, int repair, u32 tag, bce_check_report* d_report,
+                            bce_check_entry* d_log, hipStream_t stream) {
+    const u64 items = (u64)count * instances;
+    if (items == 0) return hipSuccess;
+    if (items > (1ull << 31)) return hipErrorInvalidValue;   // the item counter of a wave is 32 bits wide and steps past `items`
+    const u32 blocks = (u32)std::min<u64>((items + kCheckWaves - 1) / kCheckWaves, 4096);
+    hipLaunchKernelGGL(k_lwe_check, dim3(blocks), dim3(64 * kCheckWaves), 0, stream, P.pool, P.pool_stride, P.n, P.q, s, d_slots,
+                       d_expect, count, expect_stride, (u32)items, slot_stride, repair, tag, d_report, d_log);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
 // batched NTT over global memory (key import / key generation / debug), one wave per poly
 // ---------------------------------------------------------------------------------------
 template <int LOGN>

@@ -224,6 +224,20 @@ hipError_t launch_lwe_unary(const DevParams& P, const bce_gate_desc* d_descs, u3
 hipError_t launch_pool_pack(const DevParams& P, const bce_gate_desc* d_descs, u32 count, u32* buf, int to_pool,
                             hipStream_t s);
 
+// Verify mode on the device (k_lwe_check; reference: the decrypt-compare-repair of every gate output, src/gate.cpp:153-160).
+// Item i = (check i % count, instance i / count) reads pool row d_slots[i % count] + (i / count) * slot_stride and the
+// expected bit d_expect[(i / count) * expect_stride + i % count]; phase = b - <a, s> mod q with s = int8[n] in {-1, 0, 1},
+// got = Round(4 phase / q), err = centred(phase - expect q/4).  Counters go to *d_report with agent-scope atomics, every
+// mismatch (got != expect) to d_log[kCheckLogCap] while it has room.  repair != 0: a mismatching row is overwritten with the
+// TRIVIAL ciphertext (0, ..., 0, expect q/4) -- not the reference's Encrypt(sk, bit): no device PRNG, no host round trip,
+// repaired runs are bit-reproducible, and verify mode holds key and plaintext anyway.  The rows of one launch are distinct.
+// No allocation, no synchronisation, counters are never reset here: the launch can be captured into a hipGraph.
+constexpr u32 kCheckLogCap = 4096;
+constexpr u32 kCheckWaves = 4;       // items a workgroup works on at a time (one wave each)
+hipError_t launch_lwe_check(const DevParams& P, const int8_t* d_s, const u32* d_slots, const uint8_t* d_expect, u32 count,
+                            u32 expect_stride, u32 instances, u32 slot_stride, int repair, u32 tag, bce_check_report* d_report,
+                            bce_check_entry* d_log, hipStream_t s);
+
 // in-place negacyclic NTT of `count` polys, [count][N] words of the context's width in global memory
 hipError_t launch_ntt_batch(const DevParams& P, void* polys, u32 count, int inverse, hipStream_t s);
 

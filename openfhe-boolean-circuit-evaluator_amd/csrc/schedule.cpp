@@ -311,6 +311,25 @@ bool check(const StepPlan& P, const Dag& dag, uint32_t rank, uint32_t world, std
     return true;
 }
 
+CheckLists check_lists(const StepPlan& P, const Dag& dag) {
+    CheckLists C;
+    std::vector<int32_t> owner(dag.n_wires, -1);   // wire -> the bootstrapped gate that drives it
+    for (size_t j = 0; j < dag.gates.size(); ++j) {
+        const DagGate& g = dag.gates[j];
+        if ((g.op == Op::AND || g.op == Op::OR || g.op == Op::XOR) && g.out >= 0) owner[g.out] = (int32_t)j;
+    }
+    C.wires.resize(P.steps.size());
+    C.gates.resize(P.steps.size());
+    for (size_t s = 0; s < P.steps.size(); ++s)
+        for (const bce_gate_desc& d : P.steps[s]) {
+            if (d.out >= dag.n_wires) continue;   // an XOR's temporary
+            if (owner[d.out] < 0) throw std::logic_error("check_lists: a step writes a register no gate drives");
+            C.wires[s].push_back(d.out);
+            C.gates[s].push_back((uint32_t)owner[d.out]);
+        }
+    return C;
+}
+
 LevelShard shard_levels(const Dag& dag, uint32_t world, bool xor_fast) {
     LevelShard L;
     const size_t Lc = dag.level_off.empty() ? 0 : dag.level_off.size() - 1;

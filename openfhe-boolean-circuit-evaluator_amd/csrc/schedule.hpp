@@ -61,6 +61,16 @@ TaskList lower_tasks(const Units&, uint32_t n_wires);   // SSA: every XOR owns i
 // every step reads only what earlier steps wrote (or received), every XOR temporary is read one step after it is written
 bool check(const StepPlan&, const Dag&, uint32_t rank, uint32_t world, std::string* why = nullptr);
 
+// Verify mode on the step schedule (the reference decrypts and compares every GATE output, src/gate.cpp:153-160): per step,
+// the descriptors whose `out` is a netlist wire -- AND, OR, the final OR of a lowered XOR, XOR_FAST / XNOR_FAST -- as the
+// register they write and the gate (index into Dag::gates) that owns it.  An XOR's two temporaries are not listed.  NOT
+// gates have no register on this schedule: a wrong NOT input shows at its consumer.
+struct CheckLists {
+    std::vector<std::vector<uint32_t>> wires;   // [step] -> registers written in that step, in descriptor order
+    std::vector<std::vector<uint32_t>> gates;   // [step] -> owning gate of each
+};
+CheckLists check_lists(const StepPlan&, const Dag&);
+
 // gate sharding of the gate-LEVEL rounds: owner of every gate of a level (0xFF = everyone: OUTPUT), publications after it
 struct LevelShard {
     std::vector<std::vector<uint8_t>> owner;                 // [level][k]
