@@ -294,6 +294,11 @@ uint32_t bce_forward_units(const bce_ctx*);
  * the four 7-bit limbs of one constant 64 x 64 matrix (needs the quarter units, gadget base <= 2^7 and the bounds of
  * csrc/fwd_mfma.hpp for this Q); 0: the quarter-unit body, in other contexts or with BCE_FWD_MFMA=0 at context creation. */
 uint32_t bce_forward_mfma(const bce_ctx*);
+/* 1 when the context was granted the lazy arithmetic of the 32-bit kernels (forward transforms without corrections, 64-bit
+ * MAC sums, Montgomery MAC tail: the bounds ok1..ok5 of derive_ctx, csrc/engine.cpp, hold for this Q, N and digit count);
+ * 0: the corrected forms.  Always 1 for Q >= 2^28 (the 64-bit kernels have one form).  Read-only; for tests that look for the
+ * largest modulus of a class. */
+uint32_t bce_lazy_arithmetic(const bce_ctx*);
 /* The host-built tables of that body, without a context or a device (tests).  Any output pointer may be null.
  * psi: the 2N-th root used; M6[64][64]: the six stages as a matrix over the positions p >> 4; C[64]: the balance words of
  * the raw-digit form (the kernel multiplies signed digits and needs none); table[4096]: the device image (A operands per

@@ -81,7 +81,7 @@ ENGINE_SYMBOLS = [
     "bce_keygen", "bce_import_keys", "bce_import_keys_eval", "bce_export_bsk_eval", "bce_import_keys_file", "bce_export_keys_file", "bce_bsk_words", "bce_ksk_words", "bce_export_sk", "bce_export_bsk",
     "bce_export_ksk", "bce_pool_reserve", "bce_pool_slots", "bce_lwe_write", "bce_lwe_read",
     "bce_encrypt_bits", "bce_set_encrypt_seed", "bce_decrypt_bits", "bce_eval_gates", "bce_eval_gates_strided", "bce_synchronize",
-    "bce_timing_reset", "bce_timing_get", "bce_timing_set_events", "bce_bytes_per_bootstrap", "bce_bytes_per_bootstrap_parts", "bce_forward_transforms_per_step", "bce_forward_units", "bce_forward_mfma", "bce_forward_mfma_tables", "bce_launch_capacity", "bce_rccl_available", "bce_rccl_version", "bce_rccl_unique_id", "bce_rccl_init", "bce_rccl_allgather", "bce_rccl_comm_info",
+    "bce_timing_reset", "bce_timing_get", "bce_timing_set_events", "bce_bytes_per_bootstrap", "bce_bytes_per_bootstrap_parts", "bce_forward_transforms_per_step", "bce_forward_units", "bce_forward_mfma", "bce_lazy_arithmetic", "bce_forward_mfma_tables", "bce_launch_capacity", "bce_rccl_available", "bce_rccl_version", "bce_rccl_unique_id", "bce_rccl_init", "bce_rccl_allgather", "bce_rccl_comm_info",
     "bce_rccl_shutdown", "bce_debug_eval_stages", "bce_debug_ntt", "bce_debug_tail",
     "bce_dag_supported", "bce_dag_create", "bce_dag_run", "bce_dag_destroy", "bce_dag_set_limits", "bce_dag_last_run", "bce_dag_debug_block_task",
     "bce_plan_create", "bce_plan_run_step", "bce_plan_run", "bce_plan_destroy",
@@ -164,6 +164,8 @@ def lib():
     L.bce_forward_units.restype = C.c_uint32
     L.bce_forward_mfma.argtypes = [vp]
     L.bce_forward_mfma.restype = C.c_uint32
+    L.bce_lazy_arithmetic.argtypes = [vp]
+    L.bce_lazy_arithmetic.restype = C.c_uint32
     L.bce_forward_mfma_tables.argtypes = [u64, u32, u32, u32, vp, vp, vp, vp, vp, vp]
     L.bce_forward_mfma_tables.restype = i32
     L.bce_launch_capacity.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -516,6 +518,10 @@ class BinFHEContext:
     def forward_mfma(self):
         """1: the quarter units run the stages on bits 9..4 as i8 matrix products (BCE_FWD_MFMA=0: the quarter-unit body)"""
         return int(self._L.bce_forward_mfma(self.h))
+
+    def lazy_arithmetic(self):
+        """1: the 32-bit kernels run their lazy forms (the bounds of derive_ctx hold for this Q); 0: the corrected forms"""
+        return int(self._L.bce_lazy_arithmetic(self.h))
 
     def launch_capacity(self):
         lone, full = C.c_uint32(), C.c_uint32()

@@ -1740,6 +1740,7 @@ int bce_timing_get(bce_ctx* c, bce_timing* out) {
 uint32_t bce_forward_transforms_per_step(const bce_ctx* c) { return c ? 2 * c->dG - (c->P.fold ? 2 : 0) : 0; }
 uint32_t bce_forward_units(const bce_ctx* c) { return c ? c->P.fwd_units : 0; }
 uint32_t bce_forward_mfma(const bce_ctx* c) { return c ? c->P.fwd_mfma : 0; }
+uint32_t bce_lazy_arithmetic(const bce_ctx* c) { return c ? c->P.lazy : 0; }
 int bce_forward_mfma_tables(uint64_t Q, uint32_t N, uint32_t gBits, uint32_t dG, uint64_t* psi, uint32_t* M6, uint32_t* C, uint32_t* table,
                             uint32_t* w14, uint64_t* bounds) {
     const FwdMfmaTables T = build_fwd_mfma_tables(Q, N, gBits, dG);

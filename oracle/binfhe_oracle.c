@@ -522,6 +522,32 @@ void bo_keygen(bo_ctx* c, const uint8_t seed[32]) {
     c->have_keys = 1;
 }
 
+/* Test hook: install caller-made keys.  bsk_eval is in EVALUATION form in this file's own layout (what bo_export_bsk
+ * returns with every polynomial passed through bo_ntt_forward; the layout bce_import_keys_eval takes), ksk in
+ * bo_export_ksk's layout.  The words are copied as they are and the seed is cleared (bo_encrypt then draws from the
+ * all-zero seed).  Returns 0, or -1 when a pointer is null or a word is not reduced mod Q / qKS (nothing is installed). */
+int bo_import_keys_eval(bo_ctx* c, const int32_t* s, const int32_t* z, const uint64_t* bsk_eval, const uint32_t* ksk) {
+    if (!c || !s || !z || !bsk_eval || !ksk) return -1;
+    const u32 R = 2 * c->dG;
+    const u64 polys = c->method == BO_GINX ? (u64)c->n * 2 * R * 2 : (u64)c->n * c->baseR * c->dR * R * 2;
+    const u64 bw = polys * c->N, kw = bo_ksk_words(c);
+    for (u64 i = 0; i < bw; i++) if (bsk_eval[i] >= c->Q) return -1;
+    for (u64 i = 0; i < kw; i++) if (ksk[i] >= c->qKS) return -1;
+    free(c->s); free(c->z); free(c->bsk); free(c->ksk);
+    c->s = (int32_t*)malloc(sizeof(int32_t) * c->n);
+    c->z = (int32_t*)malloc(sizeof(int32_t) * c->N);
+    c->bsk = (u64*)malloc(sizeof(u64) * bw);
+    c->ksk = (u32*)malloc(sizeof(u32) * kw);
+    memcpy(c->s, s, sizeof(int32_t) * c->n);
+    memcpy(c->z, z, sizeof(int32_t) * c->N);
+    memcpy(c->bsk, bsk_eval, sizeof(u64) * bw);
+    memcpy(c->ksk, ksk, sizeof(u32) * kw);
+    c->bsk_polys = polys;
+    memset(c->seed, 0, sizeof c->seed);
+    c->have_keys = 1;
+    return 0;
+}
+
 void bo_export_sk(const bo_ctx* c, int32_t* s) { memcpy(s, c->s, sizeof(int32_t) * c->n); }
 void bo_export_z(const bo_ctx* c, int32_t* z) { memcpy(z, c->z, sizeof(int32_t) * c->N); }
 uint64_t bo_bsk_words(const bo_ctx* c) { return c->bsk_polys * c->N; }

@@ -90,6 +90,11 @@ void bo_export_bsk(const bo_ctx*, uint64_t* out);     /* [i][..][row][col][N], C
 uint64_t bo_ksk_words(const bo_ctx*);
 void bo_export_ksk(const bo_ctx*, uint32_t* out);     /* [i][v][j][n+1] (a..., b) mod qKS */
 
+/* install caller-made keys (test hook): bsk_eval = EVALUATION form in bo_export_bsk's layout (every polynomial of it through
+ * bo_ntt_forward; what bce_import_keys_eval takes), ksk in bo_export_ksk's layout.  Words are copied as they are, the
+ * seed is cleared.  0, or -1 for a null pointer or a word not reduced mod Q / qKS. */
+int bo_import_keys_eval(bo_ctx*, const int32_t* s, const int32_t* z, const uint64_t* bsk_eval, const uint32_t* ksk);
+
 /* LWE layer. ct = u64[n+1] : a[0..n), b */
 void bo_encrypt(const bo_ctx*, int bit, uint64_t enc_index, uint64_t* ct);
 int  bo_decrypt(const bo_ctx*, const uint64_t* ct);

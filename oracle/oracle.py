@@ -67,6 +67,8 @@ def lib():
         L.bo_ksk_words.restype = C.c_uint64
         L.bo_ksk_words.argtypes = [C.c_void_p]
         L.bo_export_ksk.argtypes = [C.c_void_p, C.c_void_p]
+        L.bo_import_keys_eval.restype = C.c_int
+        L.bo_import_keys_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.bo_encrypt.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]
         L.bo_decrypt.restype = C.c_int
         L.bo_decrypt.argtypes = [C.c_void_p, C.c_void_p]
@@ -153,6 +155,24 @@ class Oracle:
         out = np.zeros(w, dtype=np.uint32)
         lib().bo_export_ksk(self.h, _p(out))
         return out
+
+    def import_keys_eval(self, s, z, bsk_eval, ksk):
+        """Install caller-made keys: bsk_eval in EVALUATION form in bsk()'s layout (the layout the engine's
+        import_keys_eval takes), ksk in ksk()'s layout.  Words are copied as they are; unreduced words are rejected."""
+        s = np.ascontiguousarray(s, dtype=np.int32)
+        z = np.ascontiguousarray(z, dtype=np.int32)
+        bsk = np.ascontiguousarray(bsk_eval, dtype=np.uint64)
+        ksk = np.ascontiguousarray(ksk, dtype=np.uint32)
+        if s.size != self.n or z.size != self.N or bsk.size != self.bsk_words() or ksk.size != lib().bo_ksk_words(self.h):
+            raise ValueError("key sizes do not match the parameter set")
+        if lib().bo_import_keys_eval(self.h, _p(s), _p(z), _p(bsk), _p(ksk)) != 0:
+            raise ValueError("key word not reduced mod Q / qKS")
+
+    def bsk_words(self):
+        """words of the bootstrapping key of this parameter set (with or without keys)"""
+        p = self.params
+        rows = 2 * p["dG"] * 2
+        return self.n * (2 if p["method"] == GINX else p["baseR"] * p["dR"]) * rows * self.N
 
     # -- LWE ------------------------------------------------------------
     def ct(self):

@@ -354,3 +354,112 @@ def test_oracle_alone_aes_expanded_vector_0(orc, toy):
     out, boots = W.evaluate(orc, toy, nl, ins, enc_index=10000)
     assert boots == 66415 + 1536
     assert out == want
+
+
+# ---- caller-made keys (bo_import_keys_eval) and the largest moduli the engine admits --------------------------------------
+def _bsk_eval(o):
+    """bsk() (coefficient form) with every polynomial passed through ntt_forward: the oracle's own evaluation-form layout"""
+    polys = o.bsk().reshape(-1, o.N)
+    return np.stack([o.ntt_forward(p) for p in polys]).reshape(-1)
+
+
+@pytest.mark.parametrize("method,custom", [
+    ("GINX", None),                                                              # TOY
+    ("AP", (12, 512, 512, 134215681, 1 << 14, 32, 1 << 9, 23)),
+    ("GINX", (8, 512, 1024, 549755809793, 1 << 14, 32, 1 << 13, 32)),            # 39-bit Q, inexact gadget, odd exponents
+])
+def test_reimported_keys_give_identical_outputs(orc, method, custom):
+    """A keygen'd oracle's keys, re-imported into a second oracle in evaluation form: same eval_bingate, same stages."""
+    m = getattr(orc, method)
+    a = orc.Oracle(orc.TOY, m) if custom is None else orc.Oracle(method=m, custom=custom)
+    b = orc.Oracle(orc.TOY, m) if custom is None else orc.Oracle(method=m, custom=custom)
+    a.keygen(77)
+    ev = _bsk_eval(a)
+    assert ev.size == a.bsk_words()
+    b.import_keys_eval(a.sk(), a.z(), ev, a.ksk())
+    assert np.array_equal(b.sk(), a.sk()) and np.array_equal(b.z(), a.z()) and np.array_equal(b.ksk(), a.ksk())
+    assert np.array_equal(b.bsk(), a.bsk())
+    for gate in range(6):
+        c0, c1 = a.encrypt(gate & 1, 10 + gate), a.encrypt(1, 20 + gate)
+        assert np.array_equal(a.eval_bingate(gate, c0, c1), b.eval_bingate(gate, c0, c1))
+        prep = a.gate_prep(gate, c0, c1)
+        acc = a.blind_rotate(gate, prep)
+        assert np.array_equal(b.blind_rotate(gate, prep), acc)
+        lweN = a.extract_modswitch(acc)
+        assert np.array_equal(b.extract_modswitch(acc), lweN)
+        assert np.array_equal(b.keyswitch(lweN), a.keyswitch(lweN))
+        assert b.decrypt(b.eval_bingate(gate, c0, c1)) == _truth(gate, gate & 1, 1)
+    assert np.array_equal(a.bootstrap(c0), b.bootstrap(c0))
+
+
+def test_import_rejects_unreduced_words_and_wrong_sizes(orc):
+    o = orc.Oracle(method=orc.GINX, custom=(4, 512, 512, 134215681, 1 << 14, 32, 1 << 9, 23))
+    Q, qks = o.params["Q"], o.params["qKS"]
+    s, z = np.zeros(o.n, np.int32), np.zeros(o.N, np.int32)
+    bsk = np.zeros(o.bsk_words(), np.uint64)
+    ksk = np.zeros(o.N * o.params["baseKS"] * o.params["dKS"] * (o.n + 1), np.uint32)
+    o.import_keys_eval(s, z, bsk, ksk)
+    bsk[-1] = Q - 1
+    ksk[-1] = qks - 1
+    o.import_keys_eval(s, z, bsk, ksk)
+    assert o.ksk()[-1] == qks - 1
+    for bad_bsk, bad_ksk in ((Q, qks - 1), (Q - 1, qks)):
+        bsk[-1], ksk[-1] = bad_bsk, bad_ksk
+        with pytest.raises(ValueError):
+            o.import_keys_eval(s, z, bsk, ksk)
+    assert o.ksk()[-1] == qks - 1                      # a rejected import installs nothing
+    with pytest.raises(ValueError):
+        o.import_keys_eval(s, z, bsk[:-1], ksk)
+
+
+def _largest_prime_below(L, limit, N):
+    return int(L.bo_previous_prime((limit // (2 * N)) * 2 * N + 1, 2 * N))
+
+
+@pytest.mark.parametrize("bits,gbits", [(27, 9), (28, 10), (31, 8), (39, 13), (39, 14), (40, 14), (40, 10)])
+def test_products_at_the_largest_moduli_equal_bigint_schoolbook(orc, bits, gbits):
+    """At the largest prime below 2^bits (N = 512): (1) the transform product of two dense polynomials holding runs of Q - 1
+    equals the negacyclic schoolbook product in Python integers; (2) one AP accumulator step under an imported key holding
+    runs of Q - 1 -- the oracle's own 128-bit multiply-accumulate and Barrett reduction -- equals
+    sum_l schoolbook(digit row l, key row l)."""
+    L = orc.lib()
+    N = 512
+    Q = _largest_prime_below(L, 1 << bits, N)
+    assert Q < (1 << bits) and Q.bit_length() == bits
+    if bits == 40:
+        assert Q == 1099511592961
+    o = orc.Oracle(method=orc.AP, custom=(2, N, 512, Q, 1 << 14, 32, 1 << gbits, 32))
+    rng = np.random.default_rng(bits * 100 + gbits)
+
+    def runs():
+        p = rng.integers(0, Q, N, dtype=np.uint64)
+        p[:40] = Q - 1
+        p[100:140] = Q - 1
+        p[N - 24:] = Q - 1
+        return p
+
+    a, b = runs(), runs()
+    fa, fb = o.ntt_forward(a), o.ntt_forward(b)
+    prod = np.array([(int(x) * int(y)) % Q for x, y in zip(fa, fb)], dtype=np.uint64)
+    assert [int(x) for x in o.ntt_inverse(prod)] == _negacyclic_schoolbook([int(x) for x in a], [int(x) for x in b], Q)
+
+    dG, br, dr = o.params["dG"], o.params["baseR"], o.params["dR"]
+    R = 2 * dG
+    bsk = np.zeros((o.n, br, dr, R, 2, N), dtype=np.uint64)
+    key = np.stack([np.stack([runs(), runs()]) for _ in range(R)])          # coefficient form [R][2][N]
+    bsk[0, 1, 0] = np.stack([np.stack([o.ntt_forward(key[r, j]) for j in range(2)]) for r in range(R)])
+    ksk = np.zeros(o.N * o.params["baseKS"] * o.params["dKS"] * (o.n + 1), np.uint32)
+    o.import_keys_eval(np.zeros(o.n, np.int32), np.zeros(N, np.int32), bsk, ksk)
+    prep = np.array([o.params["q"] - 1, 0, 3], dtype=np.uint64)             # -a_0 = 1: the one step uses key (0, 1, 0)
+    zero = np.array([0, 0, 3], dtype=np.uint64)
+    m = o.blind_rotate(orc.AND, zero)                                        # no step: (0, test vector)
+    assert not m[:N].any()
+    digits = o.signed_digit_decompose(m)
+    want = [[0] * N, [0] * N]
+    for r in range(R):
+        d = [int(x) for x in digits[r]]
+        for j in range(2):
+            t = _negacyclic_schoolbook(d, [int(x) for x in key[r, j]], Q)
+            want[j] = [(x + y) % Q for x, y in zip(want[j], t)]
+    got = o.blind_rotate(orc.AND, prep)
+    assert [int(x) for x in got[:N]] == want[0] and [int(x) for x in got[N:]] == want[1]
