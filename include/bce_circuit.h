@@ -127,9 +127,11 @@ int bce_circuit_check_relevel(bce_circuit*);
  * and one Clock() is ONE persistent kernel launch in which a finished bootstrap releases its consumers on the device:
  * the ready-gate rule of Circuit::_ManageGates (src/circuit.cpp:575-683) applied per gate, not per frontier, with no
  * kernel boundary between dependent gates.  Same ciphertexts in every register.  XOR temporaries get slots of their
- * own, so call it before SetInput.  Ignored under gate sharding and for parameter classes without the persistent kernel
- * (the bootstrap-depth step schedule runs instead); verify mode carries a plaintext pass and therefore runs the reference's
- * gate-level rounds whatever schedule was chosen.  bce_circuit_dataflow_active tells. */
+ * own, so call it before SetInput (switching it off and on again afterwards keeps that layout).  Ignored under gate
+ * sharding and for parameter classes without the persistent kernel (the bootstrap-depth step schedule runs instead); verify
+ * mode carries a plaintext pass and therefore runs the reference's gate-level rounds whatever schedule was chosen -- unless
+ * bce_circuit_set_device_verify is on too: then the checks run inside the persistent kernel (below).
+ * bce_circuit_dataflow_active tells. */
 int bce_circuit_set_dataflow(bce_circuit*, int on);
 int bce_circuit_dataflow_active(const bce_circuit*);   /* 1 if the next encrypted Clock() takes the dataflow path */
 /* Opt-in for the bootstrap-depth schedule (set_relevel): its launches are captured once into a hipGraph and every
@@ -150,7 +152,10 @@ int bce_circuit_graph_active(const bce_circuit*);
  * after decryption and counted, not repaired, as on the host path.  Two deliberate differences to the host path:
  *   - a repaired register holds the TRIVIAL ciphertext (0, ..., 0, bit q/4) instead of a fresh cc.Encrypt(sk, bit);
  *   - NOT gates have no register on this schedule, so a wrong NOT input shows up at its consumer: fix counts can differ
- *     from the gate-level path for that reason. */
+ *     from the gate-level path for that reason.
+ * Together with bce_circuit_set_dataflow (both ..._active calls answer 1) the same checks run on the dataflow schedule instead:
+ * the workgroup that ran a bootstrap checks and repairs its output before it releases the consumers (bce_dag_set_checks of
+ * bce_gpu.h), one persistent launch per Clock(); same report, log lines, fix counts and registers as on the step schedule. */
 int bce_circuit_set_device_verify(bce_circuit*, int on);
 int bce_circuit_device_verify_active(const bce_circuit*);
 /* The device's report of the last Clock() on that path (all zero otherwise): checks, mismatches, repairs and the phase

@@ -203,7 +203,8 @@ void bce_plan_destroy(bce_ctx*, bce_plan*);
  * The reference's harnesses run their encrypted pass with setVerify(true): every gate output is decrypted, compared with
  * the plaintext pass and, on a mismatch, logged ("Bad <OP> fixing") and replaced (src/gate.cpp:113-120,153-160,174-181,
  * 206-213).  The check is one inner product of n words per ciphertext; here it runs on the engine's stream, between the
- * steps of a schedule, against a device copy of the LWE secret (int8, uploaded with the keys):
+ * steps of a schedule (or, on the dataflow schedule, inside the persistent kernel: bce_dag_set_checks), against a device
+ * copy of the LWE secret (int8, uploaded with the keys):
  *   phase = b - <a, s> mod q;  got = Round(4 phase / q);  err = phase - expect q/4, centred into (-q/2, q/2];
  *   a check is a MISMATCH iff got != expect.
  * Counters accumulate in one report block per context until bce_check_reset; the first BCE_CHECK_LOG_CAP mismatches are
@@ -254,6 +255,18 @@ int bce_dag_create(bce_ctx*, uint32_t n_tasks, const bce_gate_desc* tasks, const
 /* instance k of a run uses the DAG's slot numbers shifted by slot_base + k * slot_stride */
 int bce_dag_run(bce_ctx*, bce_dag*, uint32_t instances, uint32_t slot_stride, uint32_t slot_base);
 void bce_dag_destroy(bce_ctx*, bce_dag*);
+/* Checks attached to a DAG (verify mode on the dataflow schedule): check i belongs to task tasks[i] (distinct indices into
+ * the DAG's task list).  From then on the workgroup that ran such a task decrypts the task's `out` register when the
+ * bootstrap has finished, compares it with the expected message and, with repair != 0, replaces a wrong one BEFORE it
+ * releases the task's consumers -- the point at which the reference's Gate::Evaluate does it (src/gate.cpp:153-160); no
+ * extra launch.  Report and log: the context's block, bce_check_reset / bce_check_get, as for plans; a log entry carries
+ * tag = task index, index = check number.  n_checks == 0 detaches.  Synchronises.  BCE_ERR_NO_KEYS without keys,
+ * BCE_ERR_ARG for a task index >= n_tasks, a duplicate task index or a null pointer. */
+int bce_dag_set_checks(bce_ctx*, bce_dag*, uint32_t n_checks, const uint32_t* tasks /*[n_checks], distinct*/, int repair);
+/* The expected messages (0..3) of the next run(s) of `instances` instances, expect[instances][n_checks]; asynchronous
+ * (pinned staging, stream order).  BCE_ERR_ARG for a value above 3 or a null pointer, BCE_ERR_STATE for a DAG without
+ * checks.  bce_dag_run on a DAG with checks: BCE_ERR_STATE before this call, or with another `instances` than it named. */
+int bce_dag_set_expected(bce_ctx*, bce_dag*, uint32_t instances, const uint8_t* expect /*[instances][n_checks]*/);
 /* workgroups_per_cu: 0 = choose by the work per dependency level, 1 or 2 = force; placement: 1 = idle compute
  * units claim ready bootstraps first (default), 0 = first poller wins; lazy_us: how long a half-busy compute unit
  * leaves a short queue to idle ones; stall_ms: no completion anywhere for this long abandons the run. */

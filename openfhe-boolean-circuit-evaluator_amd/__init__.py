@@ -84,6 +84,7 @@ ENGINE_SYMBOLS = [
     "bce_timing_reset", "bce_timing_get", "bce_timing_set_events", "bce_bytes_per_bootstrap", "bce_bytes_per_bootstrap_parts", "bce_forward_transforms_per_step", "bce_forward_units", "bce_forward_mfma", "bce_lazy_arithmetic", "bce_forward_mfma_tables", "bce_launch_capacity", "bce_rccl_available", "bce_rccl_version", "bce_rccl_unique_id", "bce_rccl_init", "bce_rccl_allgather", "bce_rccl_comm_info",
     "bce_rccl_shutdown", "bce_debug_eval_stages", "bce_debug_ntt", "bce_debug_tail",
     "bce_dag_supported", "bce_dag_create", "bce_dag_run", "bce_dag_destroy", "bce_dag_set_limits", "bce_dag_last_run", "bce_dag_debug_block_task",
+    "bce_dag_set_checks", "bce_dag_set_expected",
     "bce_plan_create", "bce_plan_run_step", "bce_plan_run", "bce_plan_destroy",
     "bce_check_slots", "bce_plan_set_checks", "bce_plan_set_expected", "bce_check_reset", "bce_check_get",
 ]
@@ -185,6 +186,8 @@ def lib():
     L.bce_dag_set_limits.argtypes = [vp, i32, i32, u32, u32]
     L.bce_dag_last_run.argtypes = [vp, C.POINTER(u64)]
     L.bce_dag_debug_block_task.argtypes = [vp, u32]
+    L.bce_dag_set_checks.argtypes = [vp, vp, u32, vp, i32]
+    L.bce_dag_set_expected.argtypes = [vp, vp, u32, vp]
     L.bce_plan_create.argtypes = [vp, u32, vp, vp, u32, u32, u32, C.POINTER(vp)]
     L.bce_plan_run_step.argtypes = [vp, vp, u32]
     L.bce_plan_run.argtypes = [vp, vp]
@@ -460,6 +463,18 @@ class BinFHEContext:
         self._ck(self._L.bce_check_get(self.h, C.byref(r), log, CHECK_LOG_CAP))
         keys = ("tag", "index", "instance", "slot", "err", "got", "expect")
         return _report_dict(r, self.params["q"]), [{k: int(getattr(log[i], k)) for k in keys} for i in range(r.log_count)]
+
+    def dag_set_checks(self, dag, tasks, repair=False):
+        """tasks: distinct task indices of the DAG; check i decrypts the `out` register of tasks[i] inside the persistent
+        kernel, before the task's consumers are released.  An empty list detaches the checks."""
+        tasks = np.ascontiguousarray(tasks, dtype=np.uint32).ravel()
+        self._ck(self._L.bce_dag_set_checks(self.h, dag, tasks.size, _p(tasks) if tasks.size else None, int(bool(repair))))
+
+    def dag_set_expected(self, dag, expect):
+        """expect[instances][n_checks] of the next run(s)"""
+        expect = np.ascontiguousarray(expect, dtype=np.uint8)
+        assert expect.ndim == 2
+        self._ck(self._L.bce_dag_set_expected(self.h, dag, expect.shape[0], _p(expect)))
 
     def dag_debug_block_task(self, dag, t):
         self._ck(self._L.bce_dag_debug_block_task(dag, int(t)))
@@ -802,7 +817,8 @@ class Circuit:
 
     def setDeviceVerify(self, b):
         """opt-in: verify mode's decrypt / compare / repair on the device, between the steps of the bootstrap-depth schedule
-        (src/gate.cpp:153-160); a repaired register holds the trivial ciphertext of the right bit"""
+        (src/gate.cpp:153-160); a repaired register holds the trivial ciphertext of the right bit.  With setDataflow the
+        same checks run inside the persistent kernel, before a finished bootstrap releases its consumers"""
         self._ck(self._L.bce_circuit_set_device_verify(self.h, int(b)))
 
     def deviceVerifyActive(self):

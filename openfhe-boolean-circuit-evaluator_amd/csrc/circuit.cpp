@@ -738,23 +738,37 @@ void Circuit::clockDeviceVerify() {
                 ++stats_.sublaunches;
             }
         }
-        std::vector<bce_check_entry> log(BCE_CHECK_LOG_CAP);
-        ck(bce_check_get(cc, &check_report_, log.data(), (uint32_t)log.size()), "Clock(check report)");
-        for (uint32_t k = 0; k < check_report_.log_count; ++k) {
-            const bce_check_entry& e = log[k];
-            const char* name = "?";
-            if (e.tag < checks_.gates.size() && e.index < checks_.gates[e.tag].size()) {
-                const sched::Op op = net_.gates[checks_.gates[e.tag][e.index]].op;
-                name = op == sched::Op::AND ? "AND" : op == sched::Op::OR ? "OR" : "XOR";
-            }
-            std::cerr << "Bad " << name << " fixing" << std::endl;
-        }
-        if (check_report_.mismatches > check_report_.log_count)
-            std::cerr << "(" << (check_report_.mismatches - check_report_.log_count) << " more mismatches than the device log holds)" << std::endl;
-        stats_.verify_fixes += (uint32_t)check_report_.mismatches;
+        reportChecks(&checks_.gates, nullptr);
     }
     finishReleveled(lo, hi);
-    // OUTPUT gates: compared, counted and reported, not repaired (as the gate-level path does)
+    compareOutputs(lo, hi);
+    stats_.levels = (uint32_t)steps_.steps.size();
+}
+
+// the report of the run, read once: one "Bad <OP> fixing" line per logged mismatch, all mismatches into verify_fixes.  The
+// owning gate of a log entry: by_tag[tag][index] (step schedule: tag = step) or by_index[index] (dataflow: tag = task)
+void Circuit::reportChecks(const std::vector<std::vector<uint32_t>>* by_tag, const std::vector<uint32_t>* by_index) {
+    std::vector<bce_check_entry> log(BCE_CHECK_LOG_CAP);
+    ck(bce_check_get(cc, &check_report_, log.data(), (uint32_t)log.size()), "Clock(check report)");
+    for (uint32_t k = 0; k < check_report_.log_count; ++k) {
+        const bce_check_entry& e = log[k];
+        const char* name = "?";
+        int64_t gate = -1;
+        if (by_tag && e.tag < by_tag->size() && e.index < (*by_tag)[e.tag].size()) gate = (*by_tag)[e.tag][e.index];
+        if (by_index && e.index < by_index->size()) gate = (*by_index)[e.index];
+        if (gate >= 0) {
+            const sched::Op op = net_.gates[gate].op;
+            name = op == sched::Op::AND ? "AND" : op == sched::Op::OR ? "OR" : "XOR";
+        }
+        std::cerr << "Bad " << name << " fixing" << std::endl;
+    }
+    if (check_report_.mismatches > check_report_.log_count)
+        std::cerr << "(" << (check_report_.mismatches - check_report_.log_count) << " more mismatches than the device log holds)" << std::endl;
+    stats_.verify_fixes += (uint32_t)check_report_.mismatches;
+}
+
+// OUTPUT gates: compared, counted and reported, not repaired (as the gate-level path does)
+void Circuit::compareOutputs(unsigned lo, unsigned hi) {
     for (const GateRec& g : allGates) {
         if (g.op != GateEnum::OUTPUT) continue;
         for (unsigned i = lo; i < hi; ++i) {
@@ -763,14 +777,24 @@ void Circuit::clockDeviceVerify() {
             ++stats_.verify_fixes;
         }
     }
-    stats_.levels = (uint32_t)steps_.steps.size();
 }
 
 // ---- dataflow schedule: the whole bootstrap DAG in one persistent launch (bce_dag_*) -------------------------------
 // Tasks = the units of the bootstrap-depth schedule in topological order, an XOR as its two ANDs and its OR with
 // temporaries of its own (SSA: the device runs independent tasks in any order, so no slot may be reused); sched::lower_tasks.
 void Circuit::setDataflow(bool b) {
-    if (b && inputs_set_ && !dataflow_) throw std::logic_error("setDataflow: choose the dataflow schedule before SetInput (it lays the pool out with its own temporaries)");
+    if (inputs_set_) {
+        // the pool layout is fixed.  The schedule can be switched off and on again while that layout has room for its
+        // temporaries (it was chosen when the inputs were set; tools/verify_cost.py alternates the schedules on one set of
+        // input ciphertexts): only the choice changes, the schedules and their resident plans and DAGs stay as they are
+        if (b && tasks_.tasks.empty()) {
+            sched::TaskList t = sched::lower_tasks(units_, net_.n_wires);
+            if (t.stride > stride_) throw std::logic_error("setDataflow: choose the dataflow schedule before SetInput (it lays the pool out with its own temporaries)");
+            tasks_ = std::move(t);
+        }
+        dataflow_ = b;
+        return;
+    }
     dataflow_ = b;
     rebuildRelevel();
 }
@@ -785,6 +809,39 @@ void Circuit::clockDataflow() {
         ++stats_.sublaunches;
     }
     finishReleveled(lo, hi);
+    stats_.levels = 1;
+}
+
+// ---- verify mode on the dataflow schedule: the checks of clockDeviceVerify inside the persistent kernel ---------------
+// setDataflow + setDeviceVerify + setVerify.  The plaintext pass runs first for all levels, its bits become the expected
+// values of the DAG's checks (sched::task_checks: the same (register, gate) pairs as the step plan's lists), ONE
+// bce_dag_run follows in which every workgroup checks and repairs its task's output before it releases the consumers --
+// where Gate::Evaluate does it, src/gate.cpp:153-160 -- and the report is read once.
+void Circuit::clockDataflowVerify() {
+    const auto [lo, hi] = instanceRange();
+    const uint32_t K = hi - lo;
+    if (tasks_.stride > stride_) throw std::logic_error("dataflow schedule needs more scratch slots than the pool stride");
+    if (steps_.steps.empty()) rebuildRelevel();
+    for (size_t l = 0; l < levels_.size(); ++l) plainRound(l);
+    check_report_ = bce_check_report{};
+    if (!vdag_) {   // a DAG of its own: the verify-off runs keep theirs
+        ck(bce_dag_create(cc, (uint32_t)tasks_.tasks.size(), tasks_.tasks.data(), tasks_.prio.data(), &vdag_), "Clock(dataflow DAG)");
+        task_checks_ = sched::task_checks(tasks_, units_, net_);
+        ck(bce_dag_set_checks(cc, vdag_, (uint32_t)task_checks_.tasks.size(), task_checks_.tasks.data(), 1), "Clock(check list)");
+    }
+    if (K) {
+        std::vector<uint8_t> expect;
+        expect.reserve((size_t)K * task_checks_.wires.size());
+        for (unsigned i = lo; i < hi; ++i)
+            for (uint32_t w : task_checks_.wires) expect.push_back(plain_[i][w]);
+        ck(bce_check_reset(cc), "Clock(check reset)");
+        if (!expect.empty()) ck(bce_dag_set_expected(cc, vdag_, K, expect.data()), "Clock(expected bits)");
+        ck(bce_dag_run(cc, vdag_, K, stride_, lo * stride_), "Clock(dataflow run)");
+        ++stats_.sublaunches;
+        reportChecks(nullptr, &task_checks_.gates);
+    }
+    finishReleveled(lo, hi);
+    compareOutputs(lo, hi);
     stats_.levels = 1;
 }
 
@@ -978,7 +1035,9 @@ Outputs Circuit::Clock() {
     const bool releveled = ((relevel_ || dataflow_) && encrypted_flag && !plaintext_flag && batched_) || deviceVerifyActive();
     if (releveled) {
         auto t0 = Clock_t::now();
-        if (deviceVerifyActive()) clockDeviceVerify(); else if (dataflowActive()) clockDataflow(); else clockReleveled();
+        if (deviceVerifyActive()) { if (dataflowActive()) clockDataflowVerify(); else clockDeviceVerify(); }
+        else if (dataflowActive()) clockDataflow();
+        else clockReleveled();
         execution += ms_since(t0);
         done_gates = allGates.size();
     }

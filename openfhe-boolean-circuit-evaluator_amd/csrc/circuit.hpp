@@ -137,9 +137,11 @@ public:
     // opt-in: hand the engine the whole bootstrap DAG (bce_dag_*): ONE persistent launch per Clock() in which a finished
     // bootstrap releases its consumers on the device -- the ready-gate rule of the reference's manager
     // (src/circuit.cpp:575-683) applied per gate instead of per frontier.  Same ciphertexts in every register as the
-    // other schedules.  XOR temporaries get slots of their own (SSA), so it must be chosen before SetInput; it is
-    // ignored (the bootstrap-depth schedule runs) in verify mode, under gate sharding and for parameter classes
-    // without the persistent kernel.
+    // other schedules.  XOR temporaries get slots of their own (SSA), so it must be chosen before SetInput (switching it off and
+    // on again later keeps that layout); it is
+    // ignored (the bootstrap-depth schedule runs) under gate sharding, for parameter classes without the persistent
+    // kernel, and in verify mode unless setDeviceVerify is on too: then the checks run inside the persistent kernel
+    // (bce_dag_set_checks), between a bootstrap and the release of its consumers.
     void setDataflow(bool b);
     bool getDataflow() const { return dataflow_; }
     // opt-in: replay the bootstrap-depth schedule's launches as ONE hipGraph per Clock() (bce_plan_run) instead of one
@@ -154,11 +156,12 @@ public:
     // schedule and no gate sharding; otherwise the host path runs as before.  Differences to the host path: a repaired
     // register holds the trivial ciphertext of the right bit (bce_gpu.h), and NOT gates have no register on this schedule, so
     // a wrong NOT input is caught at its consumer -- fix counts can differ from the gate-level path for that reason.
+    // Together with setDataflow the same checks run on the dataflow schedule instead: one persistent launch per Clock().
     void setDeviceVerify(bool b) { device_verify_ = b; }
     bool getDeviceVerify() const { return device_verify_; }
     bool deviceVerifyActive() const { return device_verify_ && verify_flag && encrypted_flag && cc && batched_ && relevel_ && !gateSharded(); }
     const bce_check_report& checkReport() const { return check_report_; }   // of the last Clock() on the device path
-    bool dataflowActive() const { return dataflow_ && cc && !verify_flag && !gateSharded() && bce_dag_supported(cc) && !tasks_.tasks.empty(); }
+    bool dataflowActive() const { return dataflow_ && cc && (!verify_flag || deviceVerifyActive()) && !gateSharded() && bce_dag_supported(cc) && !tasks_.tasks.empty(); }
     const std::vector<bce_gate_desc>& dataflowTasks() const { return tasks_.tasks; }
     const std::vector<uint8_t>& dataflowPriorities() const { return tasks_.prio; }
     bool getBalance() const { return balance_; }
@@ -270,8 +273,13 @@ private:
     bce_plan* vplan_ = nullptr;                // the same schedule with the check lists of device verify mode attached (its own capture)
     bool vplan_checks_ = false;                // ... once they are attached
     void dropPlan() { for (bce_plan** p : {&plan_, &vplan_}) if (*p) { bce_plan_destroy(cc, *p); *p = nullptr; } vplan_checks_ = false; }
-    void dropDag() { if (dag_) { bce_dag_destroy(cc, dag_); dag_ = nullptr; } }
+    bce_dag* vdag_ = nullptr;                  // the same DAG with the checks of device verify mode attached
+    sched::TaskChecks task_checks_;            // of vdag_
+    void dropDag() { for (bce_dag** g : {&dag_, &vdag_}) if (*g) { bce_dag_destroy(cc, *g); *g = nullptr; } }
     void clockDataflow();
+    void clockDataflowVerify();
+    void reportChecks(const std::vector<std::vector<uint32_t>>* by_tag, const std::vector<uint32_t>* by_index);   // read the report, print and count the mismatches
+    void compareOutputs(unsigned lo, unsigned hi);   // verify mode: OUTPUT gates against the plaintext pass
     void finishReleveled(unsigned lo, unsigned hi);
     void rebuildRelevel();
     std::vector<bce_gate_desc> rebased(std::vector<bce_gate_desc> descs, unsigned lo) const;   // descriptors of instance 0 -> instance lo

@@ -12,6 +12,31 @@ typedef __attribute__((address_space(1))) unsigned long long gu64;
 __device__ __forceinline__ void dag_st(u32* p, u32 v) { __hip_atomic_store((gu32*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ u32 dag_add(u32* p, u32 v) { return __hip_atomic_fetch_add((gu32*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
+// ---- verify mode: the arithmetic of one check, shared by k_lwe_check (kernels.hip) and dag_check below -------------------
+// One wave decrypts one pool row: lane l loads words l, l + 64, ... (word n = b falls to lane n % 64 of the last pass),
+// phase = b - <a, s> mod q as a wrap-around u32 sum (q is a power of two) reduced by shuffles; got = Round(4 phase / q) and
+// err = the centred distance to want q/4 (bo_decrypt / bo_noise of the oracle, bce_decrypt_bits).  Every lane returns the
+// same pair.  BYPASS_L1: the row is read with relaxed agent-scope atomic loads (sc1: served by the L2), see dag_check.
+struct LweRowCheck { u32 got; int err; };
+template <bool BYPASS_L1>
+__device__ __forceinline__ LweRowCheck lwe_row_check(const u32* row, const int8_t* s, u32 n, u32 q, u32 want, u32 lane) {
+    const u32 qm = q - 1;
+    u32 acc = 0;
+    for (u32 k = lane; k <= n; k += 64) {
+        u32 w;
+        if constexpr (BYPASS_L1) w = __hip_atomic_load((const gu32*)(row + k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else w = row[k];
+        acc += k < n ? 0u - w * (u32)(int)s[k] : w;   // b - sum a_k s_k
+    }
+    // __shfl_down / __shfl spelled with the caller's lane number: the library's take it from mbcnt, a loop-invariant value
+    // that the optimiser would compute once and keep in a vector register across the whole persistent loop of dag_worker
+    for (u32 off = 32; off; off >>= 1) acc += (u32)__builtin_amdgcn_ds_bpermute((int)((lane + off < 64 ? lane + off : lane) << 2), (int)acc);
+    const u32 phase = (u32)__builtin_amdgcn_ds_bpermute(0, (int)acc) & qm;
+    const u32 got = (4 * ((phase + q / 8) & qm)) / q;
+    const u32 d = (phase - want * (q / 4)) & qm;
+    return {got, d > q / 2 ? (int)d - (int)q : (int)d};
+}
+
 // ---- wave-uniform scheduler code -------------------------------------------------------------------------------------
 // The scheduler of a workgroup runs on wave 0 with ALL 64 lanes active and every operand wave-uniform: the branch that
 // selects it tests the wave number in a scalar register, so whole waves take one side of it and the optimiser has no
@@ -237,12 +262,66 @@ __device__ __forceinline__ C* as_constant(const S* p) {
     return c;
 }
 
+// Verify mode inside the persistent loop (reference: Gate::Evaluate decrypts, compares and replaces a gate's output before
+// the output wire becomes active, src/gate.cpp:153-160).  Called by wave 0, all 64 lanes, after every storing wave has
+// drained and passed the barrier that follows the bootstrap, and BEFORE the release fence and the consumers' decrements:
+// a consumer reads its inputs microseconds after the decrement, so what it finds must already be the repaired row.  The
+// caller drains the repair stores (s_waitcnt vmcnt(0)) ahead of that fence.
+//   * The row is read past this CU's L1.  Pool rows are n + 1 words apart and only 4-byte aligned, so the first and last
+//     words of `out` share 128-byte lines with the neighbouring slots.  The acquire at claim time emptied the L1, but the
+//     bootstrap then read in0 / in1 (and the CU's other resident workgroup read its own inputs): a line that also holds
+//     words of `out`, with their OLD contents, can be back in the L1.  The tail's stores go through to the L2; whether they
+//     also update such a line is not something to depend on, so the loads are relaxed agent-scope atomics (global_load
+//     ... sc1), which the L2 serves -- the L2 of this XCD, the one the workgroup's own stores reached before the barrier.
+//   * Nothing is carried round the loop: every check sends its own counters to the report block (the same agent-scope
+//     atomics as k_lwe_check, from one lane).  The lane number is made opaque per call, so `lane == 0` is no
+//     loop-invariant lane-divergent condition to unswitch the persistent loop on (header comment above).
+//   * log entry: tag = task, index = check number; instance, slot, err, got, expect as in k_lwe_check.
+template <typename DT, typename PT>
+__device__ __forceinline__ void dag_check(const DT& D, const PT& P, u32 t, u32 k) {
+    const u32 ci = u_ld(D.chk_of_task + t);
+    if (ci == 0) return;                                    // scalar branch: this task has no check
+    u32 lane = threadIdx.x & 63u;
+    asm volatile("" : "+v"(lane));
+    const u32 index = ci - 1u;
+    const u32 want = __builtin_amdgcn_readfirstlane((u32)D.expect[(size_t)k * D.n_checks + index]);
+    const u32 slot = u_ld(&D.tasks[t].out) + D.slot_base + k * D.slot_stride;
+    const u32 n = P.n, q = P.q;
+    u32* const row = P.pool + (size_t)slot * P.pool_stride;
+    const LweRowCheck r = lwe_row_check<true>(row, D.s8, n, q, want, lane);
+    const u32 got = __builtin_amdgcn_readfirstlane(r.got);
+    const int err = (int)__builtin_amdgcn_readfirstlane((u32)r.err);
+    const bool bad = got != want, fix = bad && D.repair != 0;
+    if (lane == 0) {
+        bce_check_report* const rep = D.report;
+        const u32 a = (u32)(err < 0 ? -err : err);
+        __hip_atomic_fetch_add(&rep->checked, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (bad) __hip_atomic_fetch_add(&rep->mismatches, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (fix) __hip_atomic_fetch_add(&rep->repaired, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(&rep->sum_err, (int64_t)err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(&rep->sum_sq_err, (uint64_t)a * a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_max(&rep->max_abs_err, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (bad) {
+            const u32 at = __hip_atomic_fetch_add(&rep->log_count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (at < kCheckLogCap) {
+                bce_check_entry e;
+                e.tag = t; e.index = index; e.instance = k; e.slot = slot; e.err = err;
+                e.got = (uint8_t)got; e.expect = (uint8_t)want; e.pad[0] = e.pad[1] = 0;
+                D.log[at] = e;
+            }
+        }
+    }
+    // repair: the trivial ciphertext (0, ..., 0, want q/4), vector stores (they go through to the L2 like the tail's)
+    if (fix)
+        for (u32 i = lane; i <= n; i += 64) row[i] = i < n ? 0u : want * (q / 4);
+}
+
 // The persistent loop of one workgroup: claim -> acquire -> run_bootstrap(D, task, instance) -> publish, until every class
 // has been claimed to its end.  mbox: kDagMailboxWords words of LDS owned by the loop.  run_bootstrap must leave the
 // refreshed ciphertext in the pool (fused tail) and is called by every thread of the workgroup.
 constexpr u32 kDagMailboxWords = 8;
 template <typename F>
-__device__ __forceinline__ void dag_worker(const DagParams* Dp, u32* smem, F&& run_bootstrap) {
+__device__ __forceinline__ void dag_worker(const DevParams* Pp, const DagParams* Dp, u32* smem, F&& run_bootstrap) {
     // eight words in front of the LDS layout of lat_bootstrap: [0] the item the workgroup runs next, [1] "first workgroup
     // of its CU", [2] the CU's key, [3] when the item was claimed, [4] the cohort (gate generation) its last gated bootstrap started in
     u32* const mbox = smem;
@@ -293,6 +372,15 @@ __device__ __forceinline__ void dag_worker(const DagParams* Dp, u32* smem, F&& r
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (wave == 0) {
+            {   // verify mode: check, then repair, then drain -- all of it before the release below (dag_check).  One build
+                // serves runs with and without checks: a scalar load and a wave-uniform branch when there are none.
+                ConstDagParams& D = *as_constant<ConstDagParams>(Dp);
+                if (D.chk_of_task != nullptr && !(D.policy & 2u)) {   // dry run: no bootstrap, nothing to check
+                    const u32 nt = D.n_tasks, k = item / nt, t = item - k * nt;
+                    dag_check(D, *as_constant<ConstDevParams>(Pp), t, k);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                }
+            }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             ConstDagParams& D = *as_constant<ConstDagParams>(Dp);

@@ -1504,6 +1504,16 @@ struct bce_dag {
     u32* d_slots[kDagQueues] = {nullptr, nullptr, nullptr, nullptr}; size_t slots_cap[kDagQueues] = {0, 0, 0, 0};
     u32* d_ctl = nullptr;
     DagParams* d_params = nullptr;
+    // verify mode (bce_dag_set_checks / bce_dag_set_expected): check number + 1 per task, and the expected bits of the next
+    // run(s) with their pinned staging buffer, grown on demand
+    u32 n_checks = 0;
+    int chk_repair = 0;
+    u32* d_chk_of_task = nullptr;
+    uint8_t *d_expect = nullptr, *h_expect = nullptr;
+    size_t expect_cap = 0;
+    hipEvent_t expect_ev = nullptr;
+    bool expect_busy = false;
+    u32 expect_instances = 0;                      // the instance count the expected bits were set for, 0 = not set
 };
 
 extern "C" {
@@ -1538,7 +1548,59 @@ static void dag_free(bce_dag* g) {
     hipFree(g->d_tasks); hipFree(g->d_cons_off); hipFree(g->d_cons); hipFree(g->d_dep_init); hipFree(g->d_init); hipFree(g->d_qid);
     hipFree(g->d_dep); hipFree(g->d_ctl); hipFree(g->d_params);
     for (u32 q = 0; q < kDagQueues; ++q) hipFree(g->d_slots[q]);
+    hipFree(g->d_chk_of_task); hipFree(g->d_expect);
+    if (g->h_expect) hipHostFree(g->h_expect);
+    if (g->expect_ev) hipEventDestroy(g->expect_ev);
     delete g;
+}
+
+int bce_dag_set_checks(bce_ctx* c, bce_dag* g, uint32_t n_checks, const uint32_t* tasks, int repair) {
+    if (!c || !g) return BCE_ERR_ARG;
+    if (n_checks && !tasks) return c->fail(BCE_ERR_ARG, "bce_dag_set_checks: null task list");
+    if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "bce_keygen / bce_import_keys has not been called");
+    std::vector<u32> of_task(g->n_tasks, 0);
+    for (u32 i = 0; i < n_checks; ++i) {
+        if (tasks[i] >= g->n_tasks) return c->fail(BCE_ERR_ARG, "bce_dag_set_checks: check %u names task %u of %u", i, tasks[i], g->n_tasks);
+        if (of_task[tasks[i]]) return c->fail(BCE_ERR_ARG, "bce_dag_set_checks: task %u is listed twice (checks %u and %u)", tasks[i], of_task[tasks[i]] - 1, i);
+        of_task[tasks[i]] = i + 1;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // a run in flight may still read the old list
+    g->n_checks = 0; g->expect_instances = 0;      // new lists need their own expected bits
+    if (n_checks == 0) return BCE_OK;              // detached: bce_dag_run passes no list to the kernel
+    if (const int rc = ensure_check(c)) return rc;
+    if (!g->d_chk_of_task) HIP_TRY(c, hipMalloc(&g->d_chk_of_task, (size_t)g->n_tasks * sizeof(u32)));
+    HIP_TRY(c, hipMemcpy(g->d_chk_of_task, of_task.data(), (size_t)g->n_tasks * sizeof(u32), hipMemcpyHostToDevice));
+    g->n_checks = n_checks;
+    g->chk_repair = repair ? 1 : 0;
+    return BCE_OK;
+}
+
+int bce_dag_set_expected(bce_ctx* c, bce_dag* g, uint32_t instances, const uint8_t* expect) {
+    if (!c || !g) return BCE_ERR_ARG;
+    if (!expect) return c->fail(BCE_ERR_ARG, "bce_dag_set_expected: null pointer");
+    if (instances == 0) return c->fail(BCE_ERR_ARG, "bce_dag_set_expected: no instances");
+    if (!g->n_checks) return c->fail(BCE_ERR_STATE, "bce_dag_set_expected: the DAG has no checks (bce_dag_set_checks)");
+    const size_t bytes = (size_t)g->n_checks * instances;
+    for (size_t i = 0; i < bytes; ++i)
+        if (expect[i] > 3) return c->fail(BCE_ERR_ARG, "bce_dag_set_expected: expect[%zu] = %u is not a message (0..3)", i, expect[i]);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (g->expect_busy) { HIP_TRY(c, hipEventSynchronize(g->expect_ev)); g->expect_busy = false; }   // the last upload has left the pinned buffer
+    if (bytes > g->expect_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));   // a run in flight may still read the old buffer
+        hipFree(g->d_expect); if (g->h_expect) hipHostFree(g->h_expect);
+        g->d_expect = g->h_expect = nullptr; g->expect_cap = 0; g->expect_instances = 0;
+        HIP_TRY(c, hipMalloc(&g->d_expect, bytes));
+        HIP_TRY(c, hipHostMalloc(&g->h_expect, bytes));
+        g->expect_cap = bytes;
+    }
+    if (!g->expect_ev) HIP_TRY(c, hipEventCreateWithFlags(&g->expect_ev, hipEventDisableTiming));
+    std::memcpy(g->h_expect, expect, bytes);
+    HIP_TRY(c, hipMemcpyAsync(g->d_expect, g->h_expect, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(g->expect_ev, c->stream));
+    g->expect_busy = true;
+    g->expect_instances = instances;
+    return BCE_OK;
 }
 
 int bce_dag_create(bce_ctx* c, uint32_t n_tasks, const bce_gate_desc* tasks, const uint8_t* prio, bce_dag** out) {
@@ -1628,6 +1690,8 @@ int bce_dag_run(bce_ctx* c, bce_dag* g, uint32_t instances, uint32_t slot_stride
     if (!c || !g) return BCE_ERR_ARG;
     if (instances == 0) return BCE_OK;
     if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "bce_keygen / bce_import_keys has not been called");
+    if (g->n_checks && g->expect_instances == 0) return c->fail(BCE_ERR_STATE, "bce_dag_run: the DAG has checks but bce_dag_set_expected has not been called");
+    if (g->n_checks && g->expect_instances != instances) return c->fail(BCE_ERR_STATE, "bce_dag_run: %u instances, but the expected bits were set for %u", instances, g->expect_instances);
     if (instances > 1 && slot_stride <= g->max_slot) return c->fail(BCE_ERR_ARG, "bce_dag_run: slot_stride %u does not cover the DAG's slots (0..%u)", slot_stride, g->max_slot);
     if ((u64)slot_base + g->max_slot + (u64)(instances - 1) * slot_stride >= c->pool_slots) return c->fail(BCE_ERR_POOL, "bce_dag_run: slot %llu outside the pool (%u slots)", (unsigned long long)((u64)slot_base + g->max_slot + (u64)(instances - 1) * slot_stride), c->pool_slots);
     const u64 items = (u64)g->n_tasks * instances;
@@ -1661,6 +1725,11 @@ int bce_dag_run(bce_ctx* c, bce_dag* g, uint32_t instances, uint32_t slot_stride
     D.tasks = g->d_tasks; D.cons_off = g->d_cons_off; D.cons = g->d_cons; D.qid = g->d_qid; D.dep_init = g->d_dep_init;
     D.dep = g->d_dep; D.init_items = g->d_init; D.ctl = g->d_ctl;
     D.n_tasks = g->n_tasks; D.instances = instances; D.slot_stride = slot_stride; D.slot_base = slot_base;
+    if (g->n_checks) {   // verify mode: the worker checks (and repairs) before it releases a task's consumers
+        if (const int rc = ensure_check(c)) return rc;
+        D.chk_of_task = g->d_chk_of_task; D.expect = g->d_expect; D.n_checks = g->n_checks; D.repair = (u32)g->chk_repair;
+        D.s8 = c->d_s8; D.report = c->d_check; D.log = c->d_check_log;
+    }
     D.lazy_ticks = c->dag_lazy_us * 100u;                     // s_memrealtime: 100 MHz
     D.stall_ticks = c->dag_stall_ms * 100000u;
     D.policy = c->dag_placement ? 1u : 0u;

@@ -1669,7 +1669,7 @@ KernelClass kernel_class(const DevParams& P) {
 // running (cu_busy[key]); the control line counts the CUs on which none is (idle_cus).  The first workgroup of an idle CU
 // claims at once; any other one only when the backlog exceeds what the idle CUs will take (seen on two polls in a row),
 // or after it has watched the same queue head for lazy_ticks.
-__global__ void k_dag_rearm(DagParams D) {
+__global__ void k_dag_rearm(DagRearm D) {
     const size_t stride = (size_t)gridDim.x * blockDim.x, i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t items = (size_t)D.n_tasks * D.instances;
     for (size_t i = i0; i < items; i += stride) D.dep[i] = D.dep_init[i % D.n_tasks];
@@ -1692,13 +1692,13 @@ template <class V>
 __global__ __launch_bounds__(V::T, V::WPS) void k_bootstrap_dag(const DevParams* Pp, const DagParams* Dp) {
     extern __shared__ __align__(16) u32 smem[];
     // the worker's mailbox sits in front of the LDS layout of lat_bootstrap
-    dag_worker(Dp, smem, [&](ConstDagParams& D, u32 t, u32 k) {
+    dag_worker(Pp, Dp, smem, [&](ConstDagParams& D, u32 t, u32 k) {
         lat_bootstrap<V, true>(*as_constant<ConstDevParams>(Pp), D.tasks[t], D.slot_base + k * D.slot_stride, 0, smem + kDagMailboxWords,
                                nullptr, nullptr, nullptr);
     });
 }
 
-hipError_t launch_dag_rearm(const DagParams& D, hipStream_t s) {
+hipError_t launch_dag_rearm(const DagRearm& D, hipStream_t s) {
     hipLaunchKernelGGL(k_dag_rearm, dim3(1024), dim3(256), 0, s, D);
     return hipGetLastError();
 }
@@ -1996,7 +1996,6 @@ __global__ __launch_bounds__(64 * kCheckWaves) void k_lwe_check(u32* __restrict_
                                                                u32 items, u32 slot_stride, int repair, u32 tag,
                                                                bce_check_report* __restrict__ rep, bce_check_entry* __restrict__ log) {
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u32 qm = q - 1;
     u32 checked = 0, bad_n = 0, fixed_n = 0, max_abs = 0;
     int64_t sum = 0;
     uint64_t sum_sq = 0;
@@ -2005,17 +2004,9 @@ __global__ __launch_bounds__(64 * kCheckWaves) void k_lwe_check(u32* __restrict_
         const u32 slot = slots[index] + inst * slot_stride;
         const u32 want = expect[(size_t)inst * expect_stride + index];
         u32* row = pool + (size_t)slot * pool_stride;
-        u32 acc = 0;
-        for (u32 k = lane; k <= n; k += 64) {
-            const u32 w = row[k];
-            acc += k < n ? 0u - w * (u32)(int)s[k] : w;   // b - sum a_k s_k
-        }
-        for (int off = 32; off; off >>= 1) acc += __shfl_down(acc, off);
-        const u32 phase = __shfl(acc, 0) & qm;
-        // bo_decrypt / bo_noise of the oracle, bce_decrypt_bits: Round(4 phase / q), and the centred distance to want q/4
-        const u32 got = (4 * ((phase + q / 8) & qm)) / q;
-        const u32 d = (phase - want * (q / 4)) & qm;
-        const int err = d > q / 2 ? (int)d - (int)q : (int)d;
+        const LweRowCheck r = lwe_row_check<false>(row, s, n, q, want, lane);   // dag_sched.hpp: shared with the dataflow kernel
+        const u32 got = r.got;
+        const int err = r.err;
         const bool bad = got != want;
         const u32 a = (u32)(err < 0 ? -err : err);
         ++checked;

@@ -136,7 +136,8 @@ constexpr u32 kDagCohortRing = 64;                         // generations of an 
 constexpr u32 kDagCohort = kDagGate + 16 * 32;             // [16 XCC ids][kDagCohortRing] x {size, arrived}
 constexpr u32 kDagGateWaits = kDagAbort + 8;               // u64: ticks workgroups waited at their XCD's start gate
 constexpr u32 kDagCtlWords = kDagCohort + 16 * kDagCohortRing * 2;
-struct DagParams {
+// DagRearm: what re-arming reads (k_dag_rearm takes it by value); DagParams adds what only the persistent kernel reads.
+struct DagRearm {
     const bce_gate_desc* tasks;   // [n_tasks] topological order, SSA slots
     const u32* cons_off;          // [n_tasks + 1]
     const u32* cons;              // consumers of every task
@@ -157,9 +158,20 @@ struct DagParams {
     u32 gate_ticks;               // longest wait at the XCD start gate (100 MHz ticks)
     u32 gate_backlog;             // queue depth at claim time from which a bootstrap goes through the gate
 };
+struct DagParams : DagRearm {
+    // verify mode (bce_dag_set_checks): the worker checks a task's refreshed ciphertext between its bootstrap and the
+    // release of its consumers (dag_sched.hpp: dag_check).  chk_of_task == nullptr: the run has no checks.
+    const u32* chk_of_task;       // [n_tasks] check number + 1, 0 = the task is not checked
+    const uint8_t* expect;        // [instances][n_checks] expected messages (0..3)
+    u32 n_checks;
+    u32 repair;                   // != 0: a mismatching row is overwritten with the trivial ciphertext of the expected message
+    const int8_t* s8;             // the LWE secret as k_lwe_check reads it
+    bce_check_report* report;     // the context's report block and mismatch log (bce_check_reset / bce_check_get)
+    bce_check_entry* log;
+};
 // rearm = reset counters / queues for one evaluation; then the persistent launch.  wps = 2: one workgroup per CU
 // (256-register build), 4: two per CU.  grid = resident workgroups (never more).
-hipError_t launch_dag_rearm(const DagParams& D, hipStream_t s);
+hipError_t launch_dag_rearm(const DagRearm& D, hipStream_t s);
 // d_P / d_params: the engine's DevParams and the run's DagParams in DEVICE memory (the kernel reads their fields where
 // it needs them instead of holding kernel arguments in registers across its loop)
 hipError_t launch_bootstrap_dag(const DevParams& P, const DevParams* d_P, const DagParams* d_params, int wps, u32 grid,

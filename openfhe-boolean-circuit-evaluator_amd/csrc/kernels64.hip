@@ -1451,7 +1451,7 @@ template <class V>
 __global__ __launch_bounds__(V::T) void k_bootstrap_dag64(const DevParams* Pp, const DagParams* Dp) {
     extern __shared__ __align__(16) double smemd[];
     u32* mbox = reinterpret_cast<u32*>(smemd);
-    dag_worker(Dp, mbox, [&](ConstDagParams& D, u32 t, u32 k) {
+    dag_worker(Pp, Dp, mbox, [&](ConstDagParams& D, u32 t, u32 k) {
         bootstrap64d<V, true>(*as_constant<ConstDevParams>(Pp), D.tasks[t], D.slot_base + k * D.slot_stride, 0, smemd + WdLds::mbox,
                               nullptr, nullptr, nullptr);
     });

@@ -311,13 +311,19 @@ bool check(const StepPlan& P, const Dag& dag, uint32_t rank, uint32_t world, std
     return true;
 }
 
-CheckLists check_lists(const StepPlan& P, const Dag& dag) {
-    CheckLists C;
-    std::vector<int32_t> owner(dag.n_wires, -1);   // wire -> the bootstrapped gate that drives it
+// wire -> the bootstrapped gate that drives it, -1 for every other wire
+static std::vector<int32_t> gate_of_wire(const Dag& dag) {
+    std::vector<int32_t> owner(dag.n_wires, -1);
     for (size_t j = 0; j < dag.gates.size(); ++j) {
         const DagGate& g = dag.gates[j];
         if ((g.op == Op::AND || g.op == Op::OR || g.op == Op::XOR) && g.out >= 0) owner[g.out] = (int32_t)j;
     }
+    return owner;
+}
+
+CheckLists check_lists(const StepPlan& P, const Dag& dag) {
+    CheckLists C;
+    const std::vector<int32_t> owner = gate_of_wire(dag);
     C.wires.resize(P.steps.size());
     C.gates.resize(P.steps.size());
     for (size_t s = 0; s < P.steps.size(); ++s)
@@ -327,6 +333,23 @@ CheckLists check_lists(const StepPlan& P, const Dag& dag) {
             C.wires[s].push_back(d.out);
             C.gates[s].push_back((uint32_t)owner[d.out]);
         }
+    return C;
+}
+
+TaskChecks task_checks(const TaskList& T, const Units& S, const Dag& dag) {
+    TaskChecks C;
+    const std::vector<int32_t> owner = gate_of_wire(dag);
+    size_t listed = 0;
+    for (size_t t = 0; t < T.tasks.size(); ++t) {
+        const bce_gate_desc& d = T.tasks[t];
+        if (d.out >= dag.n_wires) continue;   // an XOR's temporary
+        if (owner[d.out] < 0) throw std::logic_error("task_checks: a task writes a register no gate drives");
+        C.tasks.push_back((uint32_t)t);
+        C.wires.push_back(d.out);
+        C.gates.push_back((uint32_t)owner[d.out]);
+        ++listed;
+    }
+    if (listed != S.units.size()) throw std::logic_error("task_checks: the task list was not lowered from these units");
     return C;
 }
 

@@ -70,6 +70,11 @@ struct CheckLists {
     std::vector<std::vector<uint32_t>> gates;   // [step] -> owning gate of each
 };
 CheckLists check_lists(const StepPlan&, const Dag&);
+// The same checks on the dataflow schedule: one per task whose `out` is a netlist wire, in task order -- the task (index into
+// TaskList::tasks), the register it writes and the owning gate.  As a set of (wire, gate) pairs it equals check_lists of
+// any step plan lowered from the same units; the check runs when the task completes, before its consumers are released.
+struct TaskChecks { std::vector<uint32_t> tasks, wires, gates; };
+TaskChecks task_checks(const TaskList&, const Units&, const Dag&);
 
 // gate sharding of the gate-LEVEL rounds: owner of every gate of a level (0xFF = everyone: OUTPUT), publications after it
 struct LevelShard {

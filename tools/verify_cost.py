@@ -5,13 +5,17 @@
     device        setVerify + setDeviceVerify: checks on the device between the schedule's steps, step by step
     device_graph  the same under setGraph (one hipGraph launch per Clock)
     host          setVerify alone: gate-level rounds, every level's outputs decrypted on the host (today's default)
+    dataflow          verify off on the dataflow schedule: one persistent launch per Clock (setDataflow)
+    device-dataflow   setDataflow + setDeviceVerify + setVerify: the checks inside the persistent kernel, between a
+                      bootstrap and the release of its consumers
 
 for AES-expanded at STD128_OPT GINX K = 32 and adder_64bit at K = 64.  One process, one context, one Circuit per netlist:
 the input ciphertexts are encrypted once and every setting is a Rearm() + Clock() on them, so the settings alternate
 round by round on the same device (a warm-up round first, then --reps timed rounds).  Every Clock() ends in a device
 synchronise; outputs are compared with the known answers after every run.
 
-    python3 tools/verify_cost.py [--reps 2] [--out profiles/verify_device_cost.json] [--aes-k 32] [--adder-k 64]
+    python3 tools/verify_cost.py [--reps 2] [--out profiles/verify_dataflow_cost.json] [--aes-k 32] [--adder-k 64]
+                                 [--settings off,device,...]
 """
 import argparse
 import importlib
@@ -27,31 +31,35 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 bce = importlib.import_module("openfhe-boolean-circuit-evaluator_amd")
 import kat  # noqa: E402
 
-SETTINGS = ("off", "device", "device_graph", "host")
+SETTINGS = ("off", "device", "device_graph", "host", "dataflow", "device-dataflow")
 
 
 def select(c, setting):
-    verify = setting != "off"
+    verify = setting not in ("off", "dataflow")
+    flow = setting.endswith("dataflow")
     c.setVerify(verify)               # on: also sets plaintext + encrypted
     c.setPlaintext(verify)
     c.setEncrypted(True)
+    c.setDataflow(flow)               # chosen before SetInput (measure()): switching it afterwards keeps the pool layout
     c.setDeviceVerify(setting.startswith("device"))
     c.setGraph(setting == "device_graph")
     assert c.deviceVerifyActive() == setting.startswith("device") and c.graphActive() == (setting == "device_graph")
+    assert c.dataflowActive() == flow
 
 
-def measure(cc, name, path, K, cases, reps):
+def measure(cc, name, path, K, cases, reps, settings):
     c = bce.Circuit(cc)
     c.ReadBristol(path)
     c.setInstances(K)
+    c.setDataflow(True)               # the pool is laid out with the dataflow schedule's temporaries too
     c.Reset()
     c.setVerify(True)                 # SetInput keeps the plaintext bits and encrypts
     for k in range(K):
         c.SetInput(cases[k % len(cases)][0], instance=k)
-    wall = {s: [] for s in SETTINGS}
-    stats, report = {}, None
+    wall = {s: [] for s in settings}
+    stats, reports = {}, {}
     for rnd in range(reps + 1):       # round 0 warms up (plan upload, graph capture, first launches)
-        for s in SETTINGS:
+        for s in settings:
             c.Rearm()
             select(c, s)
             t0 = time.perf_counter()
@@ -64,19 +72,32 @@ def measure(cc, name, path, K, cases, reps):
             if rnd:
                 wall[s].append(dt)
             stats[s] = {"levels": st["levels"], "sublaunches": st["sublaunches"], "bootstraps": st["bootstraps"]}
-            if s == "device":
-                report = c.check_report()
+            if s.startswith("device"):
+                reports[s] = c.check_report()
             print("%-12s round %d %-13s %8.3f s  (%d dependent rounds)" % (name, rnd, s, dt, st["levels"]), flush=True)
-    med = {s: statistics.median(wall[s]) for s in SETTINGS}
+    med = {s: statistics.median(wall[s]) for s in settings}
     n, q = cc.n, cc.params["q"]
     res = {"circuit": name, "paramset": "STD128_OPT", "method": "GINX", "instances": K, "reps": reps,
-           "wall_s": wall, "median_wall_s": med, "per_setting": stats,
-           "device_over_off": med["device"] / med["off"], "device_graph_over_off": med["device_graph"] / med["off"],
-           "host_over_off": med["host"] / med["off"], "host_over_device": med["host"] / med["device"],
-           "check_report": report,
-           "checked_bytes_per_clock": report["checked"] * (n + 1) * 4,
-           "checked_bytes_per_step": report["checked"] * (n + 1) * 4 / max(1, stats["device"]["levels"]),
-           "q": q}
+           "wall_s": wall, "median_wall_s": med, "spread_s": {s: max(wall[s]) - min(wall[s]) for s in settings},
+           "per_setting": stats, "check_reports": reports, "q": q}
+
+    def ratio(key, a, b):
+        if a in med and b in med:
+            res[key] = med[a] / med[b]
+
+    ratio("device_over_off", "device", "off")
+    ratio("device_graph_over_off", "device_graph", "off")
+    ratio("host_over_off", "host", "off")
+    ratio("host_over_device", "host", "device")
+    ratio("device_dataflow_over_dataflow", "device-dataflow", "dataflow")
+    ratio("dataflow_over_off", "dataflow", "off")
+    if "device" in reports:
+        res["check_report"] = reports["device"]
+        res["checked_bytes_per_clock"] = reports["device"]["checked"] * (n + 1) * 4
+        res["checked_bytes_per_step"] = reports["device"]["checked"] * (n + 1) * 4 / max(1, stats["device"]["levels"])
+    if "device" in reports and "device-dataflow" in reports:   # integer sums over the same ciphertexts
+        for f in ("checked", "mismatches", "repaired", "sum_err", "sum_sq_err", "max_abs_err"):
+            assert reports["device"][f] == reports["device-dataflow"][f], "%s: the two schedules report different %s" % (name, f)
     c.close()
     return res
 
@@ -86,18 +107,21 @@ def main():
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--aes-k", type=int, default=32)
     ap.add_argument("--adder-k", type=int, default=64)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "verify_device_cost.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "verify_dataflow_cost.json"))
+    ap.add_argument("--settings", default=",".join(SETTINGS), help="comma-separated subset of " + ", ".join(SETTINGS))
     args = ap.parse_args()
+    settings = tuple(args.settings.split(","))
+    assert settings and all(s in SETTINGS for s in settings), settings
     cc = bce.BinFHEContext(bce.STD128_OPT, bce.GINX)
     cc.KeyGen(0x0FE5EED)
     results = []
     if args.adder_k:
         results.append(measure(cc, "adder_64bit", os.path.join(kat.CIRCUITS, "adder_64bit.txt"), args.adder_k,
-                               [kat.adder_case(t, 64) for t in range(8)], args.reps))
+                               [kat.adder_case(t, 64) for t in range(8)], args.reps, settings))
     if args.aes_k:
         vecs = [kat.aes_case(v) for v in kat.AES_VECTORS if v["circuit"] == "AES-expanded"]
         results.append(measure(cc, "AES-expanded", os.path.join(kat.CIRCUITS, "AES-expanded.txt"), args.aes_k,
-                               vecs, args.reps))
+                               vecs, args.reps, settings))
     doc = {"what": "wall time of Circuit.Clock() per verify setting, settings alternating round by round in one process "
                    "on one device (tools/verify_cost.py); medians over `reps` timed rounds after one warm-up round",
            "results": results}
@@ -106,12 +130,14 @@ def main():
         json.dump(doc, f, indent=1)
         f.write("\n")
     for r in results:
-        print("%s K=%d: off %.3f s, device %.3f s (x%.3f), device+graph %.3f s (x%.3f), host %.3f s (x%.3f); host / device = %.2f"
-              % (r["circuit"], r["instances"], r["median_wall_s"]["off"], r["median_wall_s"]["device"], r["device_over_off"],
-                 r["median_wall_s"]["device_graph"], r["device_graph_over_off"], r["median_wall_s"]["host"], r["host_over_off"],
-                 r["host_over_device"]))
-        assert r["median_wall_s"]["device"] < r["median_wall_s"]["host"], "device verify is not faster than host verify on " + r["circuit"]
-        assert r["median_wall_s"]["device_graph"] < r["median_wall_s"]["host"], "device verify (graph) is not faster than host verify on " + r["circuit"]
+        m = r["median_wall_s"]
+        print("%s K=%d: " % (r["circuit"], r["instances"]) + ", ".join("%s %.3f s" % (k, v) for k, v in m.items()))
+        for k in ("device_over_off", "device_graph_over_off", "host_over_off", "device_dataflow_over_dataflow", "dataflow_over_off"):
+            if k in r:
+                print("    %-30s x%.4f" % (k, r[k]))
+        for dev in ("device", "device_graph"):    # same schedule as `off`: the checks must not cost what the host path costs
+            if dev in m and "host" in m:
+                assert m[dev] < m["host"], "%s is not faster than host verify on %s" % (dev, r["circuit"])
 
 
 if __name__ == "__main__":
