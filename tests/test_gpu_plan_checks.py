@@ -11,6 +11,8 @@ which checks fail, with and without repair."""
 import numpy as np
 import pytest
 
+import noise_model as nm
+
 pytestmark = pytest.mark.gpu
 SEED = 0x0FE5EED
 STRIDE, K, BASE = 16, 2, 16        # the plan's instances sit one slot_base above slot 0
@@ -92,6 +94,8 @@ def test_checks_do_not_perturb_a_correct_run_and_join_a_captured_graph(bce, toy)
         run()
         rep, log = c.check_get()
         assert (rep["checked"], rep["mismatches"], rep["repaired"], log) == (6 * K, 0, 0, [])
+        # every checked register is a bootstrap output of TOY: no error beyond 6.5 sigma of the model (12 samples carry no band)
+        nm.check_report(rep, nm.model(c.params, *c.export_sk())["V_out"])
         assert rep["margin"] > 0
         assert np.array_equal(c.lwe_read(REGS), plain_regs), "checks changed a register of a correct run"
     c.plan_set_checks(plan, [[], [], []])                # detached again: runs without expected bits, checks nothing
