@@ -94,6 +94,22 @@ int bce_circuit_get_encrypt_mode(const bce_circuit*);
  * (one bootstrap of 2*(ct1-ct2) instead of NOT,NOT,AND,AND,OR); the reference keeps this disabled
  * because of its higher failure rate (src/gate.cpp:194-203) */
 int bce_circuit_set_xor_fast(bce_circuit*, int on);
+/* opt-in extension: XOR(a, b) = AND(OR(a, b), NAND(a, b)) with the OR and the NAND from ONE blind rotation (a BCE_PAIR
+ * descriptor, bce_gpu.h): two blind rotations per XOR instead of three, in the same two steps; unlike XOR_FAST every gate
+ * input stays the plain sum of two refreshed ciphertexts.  What differs from the reference: the two temporaries of an XOR
+ * hold other ciphertexts; every netlist wire holds the same bit.  Call it before SetInput (BCE_ERR_STATE after); together
+ * with xor_fast: BCE_ERR_ARG.  It is ACTIVE (bce_circuit_xor_shared_active) with batched launches on the bootstrap-depth
+ * schedule, without gate sharding and without a host-side verify pass (verify without device verify); when it is not, the
+ * reference lowering runs exactly as without it.  Graph replay and device verify work with it (the checked registers are
+ * the same netlist wires).  The dataflow kernel has no pairs: requested together with dataflow, the step schedule runs and
+ * bce_circuit_dataflow_active answers 0.  n_bootstraps, the step sizes, the statistics and the plan hash reflect the mode.
+ * Whether it is active is fixed at SetInput as well: set_batched, set_relevel, set_device_verify and set_verify switch the
+ * lowering (and rebuild the schedule) when they change the answer of bce_circuit_xor_shared_active before SetInput; after
+ * SetInput such a call is BCE_ERR_STATE and changes nothing, because the pool is laid out for the schedule of one lowering
+ * (slack filling places the two differently, and the other can need more temporaries per step).  bce_circuit_reset lifts
+ * it.  Without the option these calls are unrestricted, as before. */
+int bce_circuit_set_xor_shared(bce_circuit*, int on);
+int bce_circuit_xor_shared_active(const bce_circuit*);
 /* Schedule by bootstrap depth (NOTs folded into consumers, an XOR's OR launched with the next level's ANDs): the
  * same ciphertext in every bootstrapped register as the reference's gate-level rounds -- asserted register by register on
  * AES-expanded, tests/test_gpu_circuit.py -- in fewer dependent launches (AES-expanded: 416 instead of 496, one block
@@ -116,6 +132,11 @@ int bce_circuit_set_balance(bce_circuit*, int on, uint32_t lone, uint32_t full);
 /* Bootstraps per step of the current bootstrap-depth schedule, for ONE instance: writes min(*n_steps, cap) entries and
  * sets *n_steps to the number of steps. */
 int bce_circuit_relevel_steps(const bce_circuit*, uint32_t* sizes, uint32_t cap, uint32_t* n_steps);
+/* The descriptors of that schedule, all steps back to back (step s has sizes[s] of them), slots of instance 0: what
+ * Clock() hands to bce_plan_create.  Writes min(*n_descs, cap) entries and sets *n_descs to their number.  TEST AND DEBUG
+ * API, not part of the interface a caller of the reference needs: it exists so that a test can replay a schedule descriptor
+ * by descriptor on the oracle (tests/test_gpu_xor_shared.py); slots and temporaries are the runtime's own and may change. */
+int bce_circuit_relevel_descs(const bce_circuit*, bce_gate_desc* descs, uint32_t cap, uint32_t* n_descs);
 /* Gate sharding on that schedule: registers THIS rank publishes after each step (one allgather per step, padded to the
  * widest rank).  Same calling convention as bce_circuit_relevel_steps; all zero without gate sharding. */
 int bce_circuit_relevel_publications(const bce_circuit*, uint32_t* counts, uint32_t cap, uint32_t* n_steps);

@@ -55,13 +55,28 @@ enum { BCE_P_n = 0, BCE_P_N, BCE_P_q, BCE_P_Q, BCE_P_qKS, BCE_P_baseKS, BCE_P_dK
  * bootstrap's LWE prep, which is how XOR = (a AND !b) OR (!a AND b)
  * (src/gate.cpp:198-202) is issued without materialising the NOTs. */
 typedef struct bce_gate_desc {
-    uint32_t op;   /* enum bce_op */
+    uint32_t op;   /* enum bce_op in bits 0..7; bits 8..15: 0, or the second gate + 1 of a pair (BCE_PAIR) */
     uint32_t in0;  /* pool slot */
     uint32_t in1;  /* pool slot (ignored by 1-input ops) */
     uint32_t out;  /* pool slot */
     uint32_t neg0;
     uint32_t neg1;
 } bce_gate_desc;
+
+/* Two gates from ONE blind rotation.  The four plain gates differ only in the window constant q1 of BootstrapGateCore's
+ * test polynomial m, which depends on b and q1 through (b - q1) mod q alone, so m_{q1'} = X^e m_{q1} (mod X^N + 1) with
+ * e = ((q1 - q1') mod q) (2N / q); the monomial commutes with the blind rotation.  A pair descriptor runs the blind rotation
+ * of `op` once and the tail (extract, ModSwitch, KeySwitch, ModSwitch) twice, on acc and on X^e acc:
+ *   slot out     <- op (in0', in1')      (word for word what the plain descriptor writes)
+ *   slot out + 1 <- op2(in0', in1')      (out + 1 + k * slot_stride with instances)
+ * with the same neg0 / neg1 for both.  The second output decrypts like EvalBinGate(op2, ...) but is NOT word-identical to
+ * it (the gadget decomposition's rounding is not symmetric under the rotation); its noise is that of a plain gate.
+ * Legal: op and op2 two DIFFERENT gates of BCE_OR, BCE_AND, BCE_NOR, BCE_NAND; anything else in bits 8.. is BCE_ERR_ARG.
+ * out + 1 obeys every rule out obeys (pool bound: BCE_ERR_POOL; written by this call, read by none of it).
+ * Accepted by bce_eval_gates, bce_eval_gates_strided, bce_plan_create and bce_debug_eval_stages; bce_dag_create refuses
+ * pairs (BCE_ERR_UNSUPPORTED).  The counters of bce_timing count blind rotations: a pair counts 1.
+ * XOR(a, b) = AND(OR(a, b), NAND(a, b)) is then two blind rotations instead of three (bce_circuit_set_xor_shared). */
+#define BCE_PAIR(op, op2) ((uint32_t)(op) | (((uint32_t)(op2) + 1u) << 8))
 
 /* which blind-rotation kernel a launch used (chosen by parameter set and launch size) */
 enum bce_br_kernel {
@@ -80,7 +95,7 @@ typedef struct bce_timing {
     double   blind_rotate_ms;   /* sum over launches of the blind-rotation kernels */
     double   tail_ms;           /* extract + modswitch + keyswitch + modswitch    */
     uint64_t blind_rotate_launches;
-    uint64_t bootstraps;        /* gate-bootstraps executed (NOT/COPY not counted) */
+    uint64_t bootstraps;        /* blind rotations executed (NOT/COPY not counted; a BCE_PAIR descriptor counts 1) */
     /* the same three blind-rotation figures per kernel (index: enum bce_br_kernel) */
     double   br_ms[BCE_BR_KERNELS];
     uint64_t br_launches[BCE_BR_KERNELS];
@@ -189,7 +204,7 @@ int bce_synchronize(bce_ctx*);
  *   bce_plan_run       = every step's launches captured once into a hipGraph and replayed with one hipGraphLaunch:
  *                        no per-step host call, no upload, no event between dependent kernels.  Timed as one unit
  *                        (BCE_BR_GRAPH).  Same ciphertexts in every register as the step-by-step form.
- * Steps hold bootstrapped ops only (BCE_AND .. BCE_XNOR_FAST, BCE_OP_REFRESH); `descs` = the steps' descriptors back to
+ * Steps hold bootstrapped ops only (BCE_AND .. BCE_XNOR_FAST, BCE_OP_REFRESH, BCE_PAIR descriptors); `descs` = the steps' descriptors back to
  * back, step s has step_sizes[s] of them.  instances / slot_stride as in bce_eval_gates_strided; the slots are fixed at
  * creation (slot_base shifts them all, e.g. a rank's first instance). */
 typedef struct bce_plan bce_plan;
@@ -349,7 +364,9 @@ int bce_rccl_comm_info(bce_ctx*, int out[3]);
 /* Runs the frontier like bce_eval_gates and also returns the intermediates
  * (any pointer may be NULL): acc = accumulator after blind rotation,
  * COEFFICIENT domain, u64 [n_desc][2][N]; lweN = after extract + ModSwitch(Q->qKS),
- * u64 [n_desc][N+1]; ks = after KeySwitch, u64 [n_desc][n+1].  Bootstrapped ops only. */
+ * u64 [n_desc][N+1]; ks = after KeySwitch, u64 [n_desc][n+1].  Bootstrapped ops only.
+ * With P pair descriptors (BCE_PAIR) lweN and ks have n_desc + P rows: rows [0, n_desc) are the first outputs, the second
+ * outputs follow from row n_desc on in descriptor order; acc stays one (shared) accumulator per descriptor. */
 int bce_debug_eval_stages(bce_ctx*, uint32_t n_desc, const bce_gate_desc* descs, uint64_t* acc,
                           uint64_t* lweN, uint64_t* ks);
 /* The tail of EvalBinGate alone on caller-supplied accumulators: acc = u64 [count][2][N], COEFFICIENT domain, words < Q

@@ -21,6 +21,14 @@ TOY, MEDIUM, STD128_AP, STD128_APOPT, STD128, STD128_OPT, STD192, STD192_OPT, ST
 AP, GINX = 1, 2
 OR, AND, NOR, NAND, XOR_FAST, XNOR_FAST = range(6)
 OP_NOT, OP_REFRESH, OP_COPY = 16, 17, 18
+
+
+def PAIR(op, op2):
+    """BCE_PAIR: descriptor word for two different gates of OR, AND, NOR, NAND from one blind rotation; the descriptor
+    writes op(in0', in1') to slot `out` and op2(in0', in1') to slot `out + 1`"""
+    return int(op) | ((int(op2) + 1) << 8)
+
+
 FRESH, BOOTSTRAPPED = 0, 1
 OK, ERR_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_NO_KEYS, ERR_POOL, ERR_UNSUPPORTED, ERR_STATE = range(8)
 P_NAMES = ["n", "N", "q", "Q", "qKS", "baseKS", "dKS", "baseG", "dG", "baseR", "dR", "method", "psi"]
@@ -545,11 +553,14 @@ class BinFHEContext:
 
     # --- staged outputs for parity ---
     def debug_eval_stages(self, descs):
+        """(acc, lweN, ks) of one frontier; with pair descriptors (PAIR) lweN and ks carry one more row per pair, in
+        descriptor order, after the len(descs) rows of the first outputs"""
         arr = make_descs(descs)
         nb = len(arr)
+        rows = nb + sum(1 for d in arr if d.op >> 8)
         acc = np.zeros((nb, 2 * self.N), dtype=np.uint64)
-        lweN = np.zeros((nb, self.N + 1), dtype=np.uint64)
-        ks = np.zeros((nb, self.n + 1), dtype=np.uint64)
+        lweN = np.zeros((rows, self.N + 1), dtype=np.uint64)
+        ks = np.zeros((rows, self.n + 1), dtype=np.uint64)
         self._ck(self._L.bce_debug_eval_stages(self.h, nb, arr, _p(acc), _p(lweN), _p(ks)))
         return acc, lweN, ks
 
@@ -594,7 +605,7 @@ CIRCUIT_SYMBOLS = [
     "bce_circuit_create", "bce_circuit_destroy", "bce_circuit_last_error", "bce_circuit_read_file",
     "bce_circuit_read_bristol", "bce_circuit_get_info", "bce_circuit_reset", "bce_circuit_rearm", "bce_circuit_set_plaintext",
     "bce_circuit_set_encrypted", "bce_circuit_set_verify", "bce_circuit_get_flags", "bce_circuit_set_batched",
-    "bce_circuit_set_encrypt_mode", "bce_circuit_get_encrypt_mode", "bce_circuit_plan_hash", "bce_circuit_set_shard_locality", "bce_circuit_set_xor_fast", "bce_circuit_set_relevel", "bce_circuit_get_relevel", "bce_circuit_set_dataflow", "bce_circuit_dataflow_active", "bce_circuit_set_graph", "bce_circuit_graph_active", "bce_circuit_set_device_verify", "bce_circuit_device_verify_active", "bce_circuit_get_check_report", "bce_circuit_dataflow_plan", "bce_circuit_set_balance", "bce_circuit_relevel_steps", "bce_circuit_relevel_publications", "bce_circuit_check_relevel", "bce_circuit_set_instances", "bce_circuit_set_input", "bce_circuit_clock",
+    "bce_circuit_set_encrypt_mode", "bce_circuit_get_encrypt_mode", "bce_circuit_plan_hash", "bce_circuit_set_shard_locality", "bce_circuit_set_xor_fast", "bce_circuit_set_xor_shared", "bce_circuit_xor_shared_active", "bce_circuit_set_relevel", "bce_circuit_get_relevel", "bce_circuit_set_dataflow", "bce_circuit_dataflow_active", "bce_circuit_set_graph", "bce_circuit_graph_active", "bce_circuit_set_device_verify", "bce_circuit_device_verify_active", "bce_circuit_get_check_report", "bce_circuit_dataflow_plan", "bce_circuit_set_balance", "bce_circuit_relevel_steps", "bce_circuit_relevel_descs", "bce_circuit_relevel_publications", "bce_circuit_check_relevel", "bce_circuit_set_instances", "bce_circuit_set_input", "bce_circuit_clock",
     "bce_circuit_get_output", "bce_circuit_get_buses", "bce_circuit_get_counts", "bce_circuit_get_stats", "bce_circuit_dump",
     "bce_circuit_set_exchange", "bce_circuit_enable_rccl", "bce_circuit_exchange_capacity", "bce_assemble_bristol", "bce_pool_gather",
     "bce_pool_scatter",
@@ -619,7 +630,7 @@ def _bind_circuit():
     L.bce_circuit_get_info.argtypes = [vp, C.POINTER(CircuitInfo)]
     for name in ("reset", "rearm", "clock"):
         getattr(L, "bce_circuit_" + name).argtypes = [vp]
-    for name in ("set_plaintext", "set_encrypted", "set_verify", "set_batched", "set_encrypt_mode", "set_xor_fast", "set_relevel", "dump"):
+    for name in ("set_plaintext", "set_encrypted", "set_verify", "set_batched", "set_encrypt_mode", "set_xor_fast", "set_xor_shared", "set_relevel", "dump"):
         getattr(L, "bce_circuit_" + name).argtypes = [vp, i32]
     L.bce_circuit_get_flags.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.bce_circuit_set_instances.argtypes = [vp, u32]
@@ -636,8 +647,10 @@ def _bind_circuit():
     L.bce_circuit_plan_hash.argtypes = [vp]
     L.bce_circuit_plan_hash.restype = u64
     L.bce_circuit_dataflow_active.argtypes = [vp]
+    L.bce_circuit_xor_shared_active.argtypes = [vp]
     L.bce_circuit_dataflow_plan.argtypes = [vp, vp, vp, u32, C.POINTER(u32)]
     L.bce_circuit_relevel_steps.argtypes = [vp, C.POINTER(u32), u32, C.POINTER(u32)]
+    L.bce_circuit_relevel_descs.argtypes = [vp, vp, u32, C.POINTER(u32)]
     L.bce_circuit_relevel_publications.argtypes = [vp, C.POINTER(u32), u32, C.POINTER(u32)]
     L.bce_circuit_check_relevel.argtypes = [vp]
     L.bce_circuit_set_input.argtypes = [vp, u32, vp, u32, vp]
@@ -787,6 +800,16 @@ class Circuit:
         """opt-in, not reference semantics: XOR as one XOR_FAST bootstrap"""
         self._ck(self._L.bce_circuit_set_xor_fast(self.h, int(b)))
 
+    def setXorShared(self, b):
+        """opt-in: XOR as AND(OR, NAND) with the OR and the NAND from one blind rotation (a PAIR descriptor): two blind
+        rotations per XOR instead of three, same depth, same bits on every netlist wire; before SetInput, not with setXorFast"""
+        self._ck(self._L.bce_circuit_set_xor_shared(self.h, int(b)))
+
+    def xorSharedActive(self):
+        """True if the next Clock() on the bootstrap-depth schedule lowers its XORs that way (batched launches, no gate
+        sharding, no host-side verify pass)"""
+        return bool(self._L.bce_circuit_xor_shared_active(self.h))
+
     def setRelevel(self, b):
         """bootstrap-depth schedule (fewer dependent launches, same ciphertexts): the default; False = the reference's
         gate-level Clock rounds (src/circuit.cpp:532-573)"""
@@ -848,6 +871,20 @@ class Circuit:
         buf = (C.c_uint32 * max(1, n.value))()
         self._ck(self._L.bce_circuit_relevel_steps(self.h, buf, n.value, C.byref(n)))
         return [int(buf[i]) for i in range(n.value)]
+
+    def relevel_plan(self):
+        """test and debug API: the bootstrap-depth schedule's descriptors, one list of (op, in0, in1, out, neg0, neg1) per
+        step, slots of instance 0, for replaying a schedule descriptor by descriptor on the oracle"""
+        n = C.c_uint32(0)
+        self._ck(self._L.bce_circuit_relevel_descs(self.h, None, 0, C.byref(n)))
+        buf = (GateDesc * max(1, n.value))()
+        self._ck(self._L.bce_circuit_relevel_descs(self.h, buf, n.value, C.byref(n)))
+        flat = [(d.op, d.in0, d.in1, d.out, d.neg0, d.neg1) for d in buf[:n.value]]
+        steps, at = [], 0
+        for size in self.relevel_steps():
+            steps.append(flat[at:at + size])
+            at += size
+        return steps
 
     def relevel_publications(self):
         """registers this rank publishes after each step of the bootstrap-depth schedule (gate sharding)"""

@@ -384,7 +384,7 @@ void Circuit::finalizeNetlist() {
         net_.level_off.push_back((uint32_t)net_.gates.size());
     }
     for (const auto& g : allGates) if (g.op == GateEnum::OUTPUT) net_.outputs.push_back(g.in[0]);
-    units_ = sched::build_units(net_, xor_fast_); tasks_ = {};
+    buildUnits();
     rebuildRelevel();  // also sizes the scratch slots the re-levelled schedule needs
     buildShardPlan();
     Reset();
@@ -395,6 +395,7 @@ void Circuit::Reset() {
     plaintext_flag = encrypted_flag = verify_flag = false;  // gep's copies are left alone, like the reference
     done = false;
     inputs_set_ = false;
+    syncXorMode();   // verify_flag is one of the things xorSharedActive() reads
     ++epoch_;
     plain_.assign(instances_, std::vector<uint8_t>(wire_names_.size(), 0));
     circuitOut.assign(instances_, std::vector<uint8_t>(n_output_bits.empty() ? 0 : n_output_bits[0], 0));
@@ -409,7 +410,8 @@ void Circuit::Rearm() {
 }
 
 void Circuit::setVerify(bool b) {
-    verify_flag = gep.verify_flag = b;
+    setModeFlag(verify_flag, b, "setVerify");   // one of the things xorSharedActive() reads
+    gep.verify_flag = b;
     if (b) { setPlaintext(true); setEncrypted(true); }
 }
 
@@ -510,6 +512,7 @@ void Circuit::setExchange(uint32_t rank, uint32_t world, int shard_mode, bce_all
     if (world > 1 && shard_mode == 0 && instances_ % world) throw std::invalid_argument("setExchange: instance sharding needs instances divisible by world");
     if (world > 250) throw std::invalid_argument("setExchange: world too large");
     rank_ = rank; world_ = world; shard_mode_ = shard_mode; xfn_ = fn; xuser_ = user;
+    if (units_mode_ != xorMode()) buildUnits();   // gate sharding keeps the reference lowering
     host_send_ = host_send; host_recv_ = host_recv; dev_send_ = dev_send; dev_recv_ = dev_recv; xcap_ = capacity;
     buildShardPlan();
     rebuildRelevel();   // the number of instances this rank evaluates may have changed
@@ -518,7 +521,7 @@ void Circuit::setExchange(uint32_t rank, uint32_t world, int shard_mode, bce_all
 uint64_t Circuit::planHash() const {
     uint64_t h = 0xcbf29ce484222325ull;   // FNV-1a over 64-bit words
     auto mix = [&](uint64_t v) { h = (h ^ v) * 0x100000001b3ull; };
-    mix(world_); mix((uint64_t)shard_mode_); mix(stride_); mix(instances_); mix(relevel_ ? 1 : 0); mix(xor_fast_ ? 1 : 0);
+    mix(world_); mix((uint64_t)shard_mode_); mix(stride_); mix(instances_); mix(relevel_ ? 1 : 0); mix((uint64_t)xorMode());
     for (const auto& lv : shard_.owner) { mix(lv.size()); for (uint8_t o : lv) mix(o); }
     for (const auto& lv : shard_.publish) for (const auto& r : lv) { mix(r.size()); for (int w : r) mix((uint64_t)w); }
     for (const auto& st : steps_.publish) for (const auto& r : st) { mix(r.size()); for (int w : r) mix((uint64_t)w); }
@@ -617,7 +620,8 @@ void Circuit::rebuildRelevel() {
     const auto [lo, hi] = instanceRange();
     const uint64_t K = std::max(1u, hi - lo);
     const uint32_t world = gateSharded() ? world_ : 1;   // gate sharding: every step's units are split over the ranks
-    if (!dataflow_ || tasks_.tasks.empty()) tasks_ = dataflow_ ? sched::lower_tasks(units_, net_.n_wires) : sched::TaskList{};   // a function of the units
+    const bool want_tasks = dataflow_ && units_mode_ != sched::XorMode::Shared;   // the dataflow kernel has no pairs
+    if (!want_tasks || tasks_.tasks.empty()) tasks_ = want_tasks ? sched::lower_tasks(units_, net_.n_wires) : sched::TaskList{};   // a function of the units
     auto plan = [&](bool by_slack) {   // returns the slot stride the schedules need
         if (by_slack && !units_.units.empty()) {
             const auto [lone, full] = launchCapacity();
@@ -651,10 +655,37 @@ std::vector<uint32_t> Circuit::relevelPublications() const {
 }
 
 void Circuit::setXorFast(bool b) {
+    if (b && xor_shared_) throw std::invalid_argument("setXorFast: not together with setXorShared");
     xor_fast_ = gep.xor_fast = b;
-    units_ = sched::build_units(net_, xor_fast_); tasks_ = {};
+    buildUnits();
     buildShardPlan();
     rebuildRelevel();
+}
+
+void Circuit::setXorShared(bool b) {
+    if (b && xor_fast_) throw std::invalid_argument("setXorShared: not together with setXorFast");
+    if (inputs_set_ && b != xor_shared_) throw std::logic_error("setXorShared: choose the XOR lowering before SetInput");
+    xor_shared_ = b;
+    syncXorMode();
+}
+
+// The two lowerings use the same temporaries (two adjacent slots per XOR): under the same placement the slot stride does
+// not depend on the mode.  Placement by slack does depend on it (a shared XOR weighs 1 + 1, a reference one 2 + 1), so the
+// stride of one lowering's schedule need not hold the other's: the mode is settled when the pool is laid out.
+void Circuit::syncXorMode() {
+    if (units_mode_ == xorMode()) return;
+    buildUnits();
+    rebuildRelevel();
+}
+
+void Circuit::setModeFlag(bool& flag, bool b, const char* who) {
+    const bool was = flag;
+    flag = b;
+    if (inputs_set_ && units_mode_ != xorMode()) {
+        flag = was;
+        throw std::logic_error(std::string(who) + ": it would switch the XOR lowering chosen with setXorShared; call it before SetInput");
+    }
+    syncXorMode();
 }
 
 // the schedule's descriptors on the device (bce_plan), for the instances [lo, lo + K)
@@ -787,7 +818,7 @@ void Circuit::setDataflow(bool b) {
         // the pool layout is fixed.  The schedule can be switched off and on again while that layout has room for its
         // temporaries (it was chosen when the inputs were set; tools/verify_cost.py alternates the schedules on one set of
         // input ciphertexts): only the choice changes, the schedules and their resident plans and DAGs stay as they are
-        if (b && tasks_.tasks.empty()) {
+        if (b && tasks_.tasks.empty() && units_mode_ != sched::XorMode::Shared) {
             sched::TaskList t = sched::lower_tasks(units_, net_.n_wires);
             if (t.stride > stride_) throw std::logic_error("setDataflow: choose the dataflow schedule before SetInput (it lays the pool out with its own temporaries)");
             tasks_ = std::move(t);
@@ -1106,9 +1137,10 @@ bce_circuit_info Circuit::info() const {
     for (const auto& L : levels_) {
         uint32_t a = 0, b = 0;
         for (int gi : L.gates) {
-            const uint32_t w = sched::gate_weight(sched_op(allGates[gi].op), xor_fast_);   // 3 = XOR: two ANDs in stage A, their OR in stage B
-            a += w == 3 ? 2 : w;
-            b += w == 3;
+            // an XOR: two ANDs in stage A, their OR in stage B (3), or a pair in stage A and an AND in stage B (2, shared)
+            const uint32_t w = sched::gate_weight(sched_op(allGates[gi].op), xorMode());
+            a += w >= 2 ? w - 1 : w;
+            b += w >= 2;
         }
         if (a) ++I.n_sublaunches;
         if (b) ++I.n_sublaunches;

@@ -117,7 +117,7 @@ public:
     // ---- extensions --------------------------------------------------------------
     void setInstances(unsigned k);            // K lock-step input sets (before SetInput)
     unsigned getInstances() const { return instances_; }
-    void setBatched(bool b) { batched_ = b; }
+    void setBatched(bool b) { setModeFlag(batched_, b, "setBatched"); }
     // cc.Encrypt(sk, bit) of SetInput (src/circuit.cpp:506) and of the verify-mode repairs (src/gate.cpp:118,139,143,158,179,211):
     // BCE_BOOTSTRAPPED by default, as OpenFHE v1.0.x's Encrypt defaults to BOOTSTRAPPED (one Bootstrap per fresh ciphertext);
     // BCE_FRESH is the opt-in that skips it
@@ -126,10 +126,26 @@ public:
     // opt-in, NOT the reference's semantics: evaluate XOR natively with OpenFHE's XOR_FAST gate
     // (src/gate.cpp:194-196 disables it "for now" because of its higher failure rate)
     void setXorFast(bool b);
+    // opt-in: XOR as AND(OR(a, b), NAND(a, b)) with the OR and the NAND from ONE blind rotation (a BCE_PAIR descriptor,
+    // bce_gpu.h): two blind rotations per XOR instead of three, in the same two steps, and every gate input is still the sum
+    // of two refreshed ciphertexts.  The XOR's two temporaries hold other ciphertexts than the reference lowering's; every
+    // netlist wire holds the same BIT.  Before SetInput; not together with setXorFast.  Active with batched launches on the
+    // bootstrap-depth schedule, without gate sharding and without a host-side verify pass (setVerify without
+    // setDeviceVerify); otherwise the reference lowering runs exactly as without it.  The dataflow kernel has no pairs:
+    // with setDataflow on top the step schedule runs (dataflowActive() is false).
+    // The lowering is fixed at SetInput, and so is whether it is active: setBatched, setRelevel, setDeviceVerify and
+    // setVerify rebuild the units and the schedule when they change xorSharedActive() before SetInput, and are refused
+    // (std::logic_error, BCE_ERR_STATE; the flag keeps its value) when they would change it after.  The pool is laid out
+    // for the schedule of one lowering: slack filling spreads the 2-rotation XORs over other steps than the 3-rotation
+    // ones, so the other lowering can need more temporaries per step than the stride has (adder_64bit, K = 64: 899
+    // slots laid out, 923 needed).  With the option off these calls behave as they always did.  Reset() lifts it.
+    void setXorShared(bool b);
+    bool getXorShared() const { return xor_shared_; }
+    bool xorSharedActive() const { return xor_shared_ && batched_ && relevel_ && !gateSharded() && !(verify_flag && !device_verify_); }
     // opt-in: schedule by BOOTSTRAP depth instead of gate level -- NOT gates are folded into their
     // consumers' prep (neg flags) and an XOR's OR shares a launch with the next level's ANDs.  Same
     // ciphertexts as the level schedule (EvalNOT is deterministic), fewer dependent launches.
-    void setRelevel(bool b) { relevel_ = b; }
+    void setRelevel(bool b) { setModeFlag(relevel_, b, "setRelevel"); }
     bool getRelevel() const { return relevel_; }
     // the bootstrap-depth schedule fills its steps by slack up to the launch staircase of the engine (default on; see
     // sched::place_by_slack).  lone / full = 0: ask the engine (bce_launch_capacity), else use these capacities (tests).
@@ -157,15 +173,16 @@ public:
     // register holds the trivial ciphertext of the right bit (bce_gpu.h), and NOT gates have no register on this schedule, so
     // a wrong NOT input is caught at its consumer -- fix counts can differ from the gate-level path for that reason.
     // Together with setDataflow the same checks run on the dataflow schedule instead: one persistent launch per Clock().
-    void setDeviceVerify(bool b) { device_verify_ = b; }
+    void setDeviceVerify(bool b) { setModeFlag(device_verify_, b, "setDeviceVerify"); }
     bool getDeviceVerify() const { return device_verify_; }
     bool deviceVerifyActive() const { return device_verify_ && verify_flag && encrypted_flag && cc && batched_ && relevel_ && !gateSharded(); }
     const bce_check_report& checkReport() const { return check_report_; }   // of the last Clock() on the device path
-    bool dataflowActive() const { return dataflow_ && cc && (!verify_flag || deviceVerifyActive()) && !gateSharded() && bce_dag_supported(cc) && !tasks_.tasks.empty(); }
+    bool dataflowActive() const { return dataflow_ && !xorSharedActive() && cc && (!verify_flag || deviceVerifyActive()) && !gateSharded() && bce_dag_supported(cc) && !tasks_.tasks.empty(); }
     const std::vector<bce_gate_desc>& dataflowTasks() const { return tasks_.tasks; }
     const std::vector<uint8_t>& dataflowPriorities() const { return tasks_.prio; }
     bool getBalance() const { return balance_; }
     std::vector<uint32_t> relevelStepSizes() const;          // bootstraps per step, one instance
+    const std::vector<std::vector<bce_gate_desc>>& relevelStepDescs() const { return steps_.steps; }   // this rank's descriptors, instance 0
     std::vector<uint32_t> relevelPublications() const;       // registers this rank publishes per step (gate sharding)
     bool checkRelevelPlan(std::string* why = nullptr) const { return sched::check(steps_, net_, rank_, gateSharded() ? world_ : 1, why); }
     bool getXorFast() const { return xor_fast_; }
@@ -212,7 +229,7 @@ private:
     bce_ctx* cc = nullptr;
     bool owns_engine_ = false;
     bool plaintext_flag = false, encrypted_flag = false, verify_flag = false;
-    bool done = false, inputs_set_ = false, quiet_ = false, batched_ = true, xor_fast_ = false;
+    bool done = false, inputs_set_ = false, quiet_ = false, batched_ = true, xor_fast_ = false, xor_shared_ = false;
     int encrypt_mode_ = BCE_BOOTSTRAPPED;
     GateEvalParams gep;
 
@@ -258,7 +275,12 @@ private:
     bool relevel_ = true;   // the bootstrap-depth schedule is the default since round 4 (identical registers, 416 instead of 496
                             // dependent launches on AES-expanded); setRelevel(false) = the reference's gate-level rounds, src/circuit.cpp:532-573
     sched::Dag net_;          // the levelised netlist as the schedule module reads it
-    sched::Units units_;      // rebuilt when the netlist or xor_fast_ changes
+    sched::Units units_;      // rebuilt when the netlist or the XOR mode changes
+    sched::XorMode units_mode_ = sched::XorMode::Reference;   // the mode units_ were built for
+    sched::XorMode xorMode() const { return xor_fast_ ? sched::XorMode::Fast : xorSharedActive() ? sched::XorMode::Shared : sched::XorMode::Reference; }
+    void buildUnits() { units_mode_ = xorMode(); units_ = sched::build_units(net_, units_mode_); tasks_ = {}; }
+    void syncXorMode();       // after a change of anything xorSharedActive() reads: units and schedules for the mode that now holds
+    void setModeFlag(bool& flag, bool b, const char* who);   // sets one of those flags; refused after SetInput where it would switch the lowering
     sched::StepPlan steps_;   // bootstrap-depth schedule: redone when K, capacities, world, locality or balance change
     sched::TaskList tasks_;   // dataflow schedule: held only while it is chosen
     uint32_t base_stride_ = 0;

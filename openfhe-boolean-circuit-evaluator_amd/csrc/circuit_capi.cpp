@@ -81,6 +81,8 @@ int bce_circuit_set_encrypt_mode(bce_circuit* h, int mode) {
     });
 }
 int bce_circuit_set_xor_fast(bce_circuit* h, int on) { return guarded(h, [&] { h->c.setXorFast(on != 0); }); }
+int bce_circuit_set_xor_shared(bce_circuit* h, int on) { return guarded(h, [&] { h->c.setXorShared(on != 0); }); }
+int bce_circuit_xor_shared_active(const bce_circuit* h) { return h && h->c.xorSharedActive() ? 1 : 0; }
 int bce_circuit_set_relevel(bce_circuit* h, int on) { return guarded(h, [&] { h->c.setRelevel(on != 0); }); }
 int bce_circuit_get_relevel(bce_circuit* h) { return h && h->c.getRelevel() ? 1 : 0; }
 int bce_circuit_set_instances(bce_circuit* h, uint32_t k) { return guarded(h, [&] { h->c.setInstances(k); }); }
@@ -114,6 +116,14 @@ int bce_circuit_relevel_steps(const bce_circuit* h, uint32_t* sizes, uint32_t ca
     const std::vector<uint32_t> v = h->c.relevelStepSizes();
     for (size_t i = 0; i < v.size() && i < cap; ++i) sizes[i] = v[i];
     *n_steps = (uint32_t)v.size();
+    return BCE_OK;
+}
+int bce_circuit_relevel_descs(const bce_circuit* h, bce_gate_desc* descs, uint32_t cap, uint32_t* n_descs) {
+    if (!h || !n_descs || (cap && !descs)) return BCE_ERR_ARG;
+    uint32_t n = 0;
+    for (const auto& st : h->c.relevelStepDescs())
+        for (const bce_gate_desc& d : st) { if (n < cap) descs[n] = d; ++n; }
+    *n_descs = n;
     return BCE_OK;
 }
 int bce_circuit_relevel_publications(const bce_circuit* h, uint32_t* counts, uint32_t cap, uint32_t* n_steps) {

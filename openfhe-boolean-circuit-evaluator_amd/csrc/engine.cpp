@@ -679,11 +679,20 @@ int sync_stream(bce_ctx* c) {
     return check_dag_runs(c);
 }
 
+// The descriptor word `op`: bits 0..7 the gate, bits 8..15 the second gate + 1 of a pair (BCE_PAIR, two different gates of
+// OR, AND, NOR, NAND on one blind rotation).  0: plain descriptor, 1: legal pair, -1: anything else in the high bits.
+int pair_kind(u32 op) {
+    if (op <= 0xFFu) return 0;
+    const u32 lo = op & 0xFFu, hi = op >> 8;
+    return (lo <= BCE_NAND && hi >= 1 && hi - 1 <= BCE_NAND && hi - 1 != lo) ? 1 : -1;
+}
+
 // One frontier of bootstrapped gates whose descriptors already sit on the device: blind rotation (+ the tail kernels
 // when the blind-rotation kernel does not carry it).  timed: HIP events around each kernel group + the counters of
 // bce_timing; untimed (stream capture of bce_plan_run): launches only, *fused_out says whether the tail was fused.
+// pairs: at least one descriptor is a pair (its second tail pass runs in the fused epilogue or as a second tail launch).
 int launch_bootstraps(bce_ctx* c, const bce_gate_desc* dd, u32 n, u32 instances, u32 slot_stride, void* d_acc,
-                      u32* d_lweN, u32* d_ks, bool timed, bool* fused_out, u64* d_partial = nullptr) {
+                      u32* d_lweN, u32* d_ks, bool timed, bool* fused_out, bool pairs, u64* d_partial = nullptr) {
     const size_t nb = (size_t)n * instances;
     int kid = 0;
     bool tail_fused = false;
@@ -725,7 +734,7 @@ int launch_bootstraps(bce_ctx* c, const bce_gate_desc* dd, u32 n, u32 instances,
                 c->tail_cap = cap;
             }
         }
-        const hipError_t e = launch_tail(c->P, dd, n, instances, slot_stride, d_acc, d_partial ? d_partial : c->d_tail_partial, d_lweN, d_ks, c->stream, le1);
+        const hipError_t e = launch_tail(c->P, dd, n, instances, slot_stride, d_acc, d_partial ? d_partial : c->d_tail_partial, d_lweN, d_ks, c->stream, le1, pairs);
         if (e != hipSuccess) {
             if (events) c->free_events.push_back(e1);
             HIP_TRY(c, e);
@@ -751,13 +760,16 @@ int eval_impl(bce_ctx* c, u32 n_desc, const bce_gate_desc* descs, u32 instances,
     std::vector<bce_gate_desc> boot, unary;
     boot.reserve(n_desc);
     const u64 max_slot = (u64)(instances - 1) * slot_stride;
+    u32 n_pairs = 0;
     for (u32 i = 0; i < n_desc; ++i) {
         const bce_gate_desc& g = descs[i];
-        const bool is_boot = g.op <= BCE_XNOR_FAST || g.op == BCE_OP_REFRESH;
+        const int pair = pair_kind(g.op);
+        const bool is_boot = pair > 0 || g.op <= BCE_XNOR_FAST || g.op == BCE_OP_REFRESH;
         const bool is_unary = g.op == BCE_OP_NOT || g.op == BCE_OP_COPY;
         if (!is_boot && !is_unary) return c->fail(BCE_ERR_ARG, "descriptor %u: unknown op %u", i, g.op);
-        u64 hi = std::max<u64>(g.in0, g.out);
-        if (g.op <= BCE_XNOR_FAST) hi = std::max<u64>(hi, g.in1);
+        n_pairs += pair > 0;
+        u64 hi = std::max<u64>(g.in0, (u64)g.out + (pair > 0));   // a pair writes out and out + 1
+        if (pair > 0 || g.op <= BCE_XNOR_FAST) hi = std::max<u64>(hi, g.in1);
         if (hi + max_slot >= c->pool_slots) return c->fail(BCE_ERR_POOL, "descriptor %u: slot %llu outside the pool (%u slots)", i, (unsigned long long)(hi + max_slot), c->pool_slots);
         (is_boot ? boot : unary).push_back(g);
     }
@@ -770,9 +782,11 @@ int eval_impl(bce_ctx* c, u32 n_desc, const bce_gate_desc* descs, u32 instances,
         rc = stage_descs(c, boot.data(), boot.size(), &dd, &slot);
         if (rc) return rc;
         u32 *d_lweN = nullptr, *d_ks = nullptr;
-        if (dbg_lweN) HIP_TRY(c, hipMalloc(&d_lweN, nb * (c->N + 1) * sizeof(u32)));
-        if (dbg_ks) HIP_TRY(c, hipMalloc(&d_ks, nb * (c->n + 1) * sizeof(u32)));
-        rc = launch_bootstraps(c, dd, (u32)boot.size(), instances, slot_stride, c->d_acc, d_lweN, d_ks, true, nullptr);
+        // staged outputs of a launch with pairs: the kernels write the second outputs to a second block of nb rows
+        const size_t dbg_rows = n_pairs ? 2 * nb : nb;
+        if (dbg_lweN) HIP_TRY(c, hipMalloc(&d_lweN, dbg_rows * (c->N + 1) * sizeof(u32)));
+        if (dbg_ks) HIP_TRY(c, hipMalloc(&d_ks, dbg_rows * (c->n + 1) * sizeof(u32)));
+        rc = launch_bootstraps(c, dd, (u32)boot.size(), instances, slot_stride, c->d_acc, d_lweN, d_ks, true, nullptr, n_pairs != 0);
         if (rc) return rc;
         hipEventRecord(c->ring_ev[slot], c->stream);
         c->ring_busy[slot] = true;
@@ -781,8 +795,21 @@ int eval_impl(bce_ctx* c, u32 n_desc, const bce_gate_desc* descs, u32 instances,
             if (dbg_acc && (rc = words_from_device(c, dbg_acc, c->d_acc, nb * 2 * c->N, c->is64))) return rc;
             if (dbg_lweN && (rc = words_from_device(c, dbg_lweN, d_lweN, nb * (c->N + 1), false))) return rc;
             if (dbg_ks && (rc = words_from_device(c, dbg_ks, d_ks, nb * (c->n + 1), false))) return rc;
+            // ... which the caller gets packed, in descriptor order, from row nb on (bce_debug_eval_stages: one instance)
+            if (n_pairs) {
+                auto pack = [&](u64* dst, const u32* dev, size_t w) {   // the second block in one copy, then packed on the host
+                    std::vector<u64> second(nb * w);
+                    const int e = words_from_device(c, second.data(), dev + nb * w, nb * w, false);
+                    for (size_t i = 0, row = nb; !e && i < nb; ++i)
+                        if (pair_kind(boot[i].op) > 0) std::copy_n(second.data() + i * w, w, dst + row++ * w);
+                    return e;
+                };
+                if (dbg_lweN) rc = pack(dbg_lweN, d_lweN, c->N + 1);
+                if (dbg_ks && !rc) rc = pack(dbg_ks, d_ks, c->n + 1);
+            }
             if (d_lweN) hipFree(d_lweN);
             if (d_ks) hipFree(d_ks);
+            if (rc) return rc;
         }
         if (c->pending.size() > 4096) {
             HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1190,6 +1217,7 @@ int bce_synchronize(bce_ctx* c) {
 
 struct bce_plan {
     std::vector<u32> off, cnt;                 // step s = descriptors [off[s], off[s] + cnt[s])
+    std::vector<uint8_t> pairs;                // step s holds at least one pair descriptor (BCE_PAIR)
     u32 instances = 0, slot_stride = 0, slot_base = 0;
     u32 max_step = 0;                          // descriptors of the largest step
     u64 boots_per_run = 0;
@@ -1288,11 +1316,18 @@ int bce_plan_create(bce_ctx* c, uint32_t n_steps, const uint32_t* step_sizes, co
     }
     std::vector<bce_gate_desc> d(descs, descs + total);
     const u64 span = (u64)slot_base + (u64)(instances - 1) * slot_stride;
+    p->pairs.assign(n_steps, 0);
+    u32 step = 0;
     for (u64 i = 0; i < total; ++i) {
         bce_gate_desc& g = d[i];
-        const bool two = g.op <= BCE_XNOR_FAST;
+        const int pair = pair_kind(g.op);
+        const bool two = pair > 0 || g.op <= BCE_XNOR_FAST;
         if (!two && g.op != BCE_OP_REFRESH) return c->fail(BCE_ERR_ARG, "bce_plan_create: descriptor %llu is not a bootstrapped gate (op %u)", (unsigned long long)i, g.op);
-        u64 hi = std::max<u64>(g.in0, g.out);
+        if (pair > 0) {
+            while (step + 1 < n_steps && i >= (u64)p->off[step + 1]) ++step;
+            p->pairs[step] = 1;
+        }
+        u64 hi = std::max<u64>(g.in0, (u64)g.out + (pair > 0));   // a pair writes out and out + 1
         if (two) hi = std::max<u64>(hi, g.in1);
         if (hi + span >= c->pool_slots) return c->fail(BCE_ERR_POOL, "bce_plan_create: descriptor %llu: slot %llu outside the pool (%u slots)", (unsigned long long)i, (unsigned long long)(hi + span), c->pool_slots);
         g.in0 += slot_base; g.in1 += slot_base; g.out += slot_base;
@@ -1312,7 +1347,7 @@ int bce_plan_run_step(bce_ctx* c, bce_plan* p, uint32_t step) {
     HIP_TRY(c, hipSetDevice(c->device));
     const int rc = ensure_acc(c, (size_t)p->cnt[step] * p->instances);
     if (rc) return rc;
-    const int rc2 = launch_bootstraps(c, p->d_descs + p->off[step], p->cnt[step], p->instances, p->slot_stride, c->d_acc, nullptr, nullptr, true, nullptr);
+    const int rc2 = launch_bootstraps(c, p->d_descs + p->off[step], p->cnt[step], p->instances, p->slot_stride, c->d_acc, nullptr, nullptr, true, nullptr, p->pairs[step] != 0);
     if (rc2) return rc2;
     if (const int rc3 = plan_check_step(c, p, step)) return rc3;
     if (c->pending.size() > 4096) {
@@ -1344,7 +1379,7 @@ int bce_plan_run(bce_ctx* c, bce_plan* p) {
         u64 fused = 0;
         for (size_t s = 0; s < p->cnt.size() && rc == BCE_OK; ++s) {
             bool f = false;
-            rc = launch_bootstraps(c, p->d_descs + p->off[s], p->cnt[s], p->instances, p->slot_stride, p->d_acc, nullptr, nullptr, false, &f, p->d_partial);
+            rc = launch_bootstraps(c, p->d_descs + p->off[s], p->cnt[s], p->instances, p->slot_stride, p->d_acc, nullptr, nullptr, false, &f, p->pairs[s] != 0, p->d_partial);
             fused += f ? 1 : 0;
             if (rc == BCE_OK) rc = plan_check_step(c, p, s);
         }
@@ -1613,6 +1648,7 @@ int bce_dag_create(bce_ctx* c, uint32_t n_tasks, const bce_gate_desc* tasks, con
     u32 max_slot = 0;
     for (u32 i = 0; i < n_tasks; ++i) {
         const bce_gate_desc& g = tasks[i];
+        if (pair_kind(g.op) > 0) return c->fail(BCE_ERR_UNSUPPORTED, "bce_dag_create: task %u is a pair descriptor (BCE_PAIR): the dataflow kernel runs one tail per bootstrap; use bce_eval_gates or a bce_plan", i);
         const bool two = g.op <= BCE_XNOR_FAST;
         if (!two && g.op != BCE_OP_REFRESH) return c->fail(BCE_ERR_ARG, "bce_dag_create: task %u is not a bootstrapped gate (op %u)", i, g.op);
         if (prio && prio[i] >= kDagQueues) return c->fail(BCE_ERR_ARG, "bce_dag_create: task %u has priority class %u (0..%u)", i, prio[i], kDagQueues - 1);
@@ -1852,7 +1888,7 @@ int bce_debug_eval_stages(bce_ctx* c, uint32_t n_desc, const bce_gate_desc* desc
                           uint64_t* ks) {
     if (!c) return BCE_ERR_ARG;
     for (u32 i = 0; i < n_desc; ++i)
-        if (!(descs[i].op <= BCE_XNOR_FAST || descs[i].op == BCE_OP_REFRESH)) return c->fail(BCE_ERR_ARG, "staged outputs need bootstrapped ops only");
+        if (!(pair_kind(descs[i].op) > 0 || descs[i].op <= BCE_XNOR_FAST || descs[i].op == BCE_OP_REFRESH)) return c->fail(BCE_ERR_ARG, "staged outputs need bootstrapped ops only");
     return eval_impl(c, n_desc, descs, 1, 0, acc, lweN, ks);
 }
 

@@ -13,6 +13,40 @@ __device__ __forceinline__ u32 round_qQ(u64 v, u32 q, u64 Qfrom) {
     return (u32)(r >= q ? r - q : r);
 }
 
+// gate constant q1 of BootstrapGateCore (OR 5q/8, AND 7q/8, NOR q/8, NAND 3q/8)
+__device__ __forceinline__ u32 gate_const(u32 op, u32 q) {
+    const u32 e = q >> 3;
+    switch (op) {
+        case BCE_OR: case BCE_XOR_FAST: return 5 * e;
+        case BCE_NOR: case BCE_XNOR_FAST: return e;
+        case BCE_NAND: return 3 * e;
+        default: return 7 * e;  // AND, REFRESH
+    }
+}
+
+// ---- two gates from one blind rotation (BCE_PAIR, include/bce_gpu.h) ---------------------------------------------
+// BootstrapGateCore's test polynomial depends on the gate only through (b - q1) mod q, so the polynomial of gate op2 is
+// X^e times that of gate op (mod X^N + 1), e = ((q1 - q1') mod q) * (2N / q), and the monomial commutes with the blind
+// rotation: the second output of a pair is the tail applied to X^e * acc.  The rotation is an index and a sign on the
+// tail's own reads of the accumulator.
+// e in [0, 2N) for the second output of descriptor word `op`; 0 for its first output and for a plain descriptor.
+template <typename PT>
+__device__ __forceinline__ u32 pair_rotation(const PT& P, u32 op) {
+    const u32 hi = (op >> 8) & 0xFFu;
+    if (hi == 0) return 0;
+    return ((gate_const(op & 0xFFu, P.q) - gate_const(hi - 1, P.q)) & (P.q - 1)) * P.factor;
+}
+// coefficient i of X^e * p (p: N words below Q): s p[i - e'] for i >= e', -s p[N + i - e'] below, e' = e mod N, s = -1 iff e >= N;
+// `flip` negates once more (the transpose of the sample extraction)
+template <typename CW>
+__device__ __forceinline__ u64 rotated_coef(const CW* p, u32 i, u32 e, u32 N, u64 Q, bool flip) {
+    const u32 es = e & (N - 1);
+    const bool wrap = i < es;
+    const u64 src = p[wrap ? N + i - es : i - es];
+    const bool neg = (wrap != (e >= N)) != flip;
+    return neg ? (src ? Q - src : 0) : src;
+}
+
 // ---- tail of EvalBinGate fused into the blind-rotation kernel (saturated launches) ------------------------------
 // After the last inverse transform the workgroup that ran the blind rotation also extracts the LWE sample,
 // switches it to qKS, gathers its N*dKS key-switching rows and writes the refreshed ciphertext: the same arithmetic
@@ -21,10 +55,11 @@ __device__ __forceinline__ u32 round_qQ(u64 v, u32 q, u64 Qfrom) {
 // separate kernel between two dependent blind-rotation launches.
 //   coef : [2][N] coefficient-form accumulator in LDS        rowidx : [N * dKS] row numbers in LDS
 //   red  : [SL][Gv * VW] u64 partial sums in LDS (SL row slices, one per RW = ceil(Gv / 64) waves)
+//   rot  : the tail runs on X^rot * acc (pair_rotation; 0 = the accumulator itself)
 // T threads (a multiple of 64); every thread of the workgroup must call it.
 template <typename KT, u32 T, typename CW, typename PT>
 __device__ __forceinline__ void fused_tail(const PT& P, const CW* coef, u32* rowidx, u64* red, u32* out, u32 boot,
-                                           u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks) {
+                                           u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks, u32 rot = 0) {
     constexpr u32 VW = 16 / sizeof(KT), W = T / 64;
     const u32 N = P.N, n = P.n, qKS = P.qKS, B = P.baseKS, D = P.dKS;
     const u64 Q = sizeof(CW) == 8 ? (u64)P.Q64 : (u64)P.Q;            // coefficient words: u32 (Q < 2^28) or u64
@@ -33,8 +68,7 @@ __device__ __forceinline__ void fused_tail(const PT& P, const CW* coef, u32* row
     const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // transpose (X -> X^-1) of acc[0]: a'_0 = a_0, a'_{N-i} = -a_i; ModSwitch(Q -> qKS); digits -> row numbers
     for (u32 i = tid; i < N; i += T) {
-        const u64 src = (i == 0) ? coef[0] : coef[N - i];
-        const u64 v = (i == 0) ? src : (src ? Q - src : 0);
+        const u64 v = rotated_coef(coef, i == 0 ? 0 : N - i, rot, N, Q, i != 0);
         u32 at = round_qQ(v, qKS, Q);
         if (dbg_lweN) dbg_lweN[(size_t)boot * (N + 1) + i] = at;
         for (u32 j = 0; j < D; ++j) {
@@ -101,7 +135,7 @@ __device__ __forceinline__ void fused_tail(const PT& P, const CW* coef, u32* row
         const u32 sm = (u32)(sum % qKS);
         u32 base = 0;
         if (k == n) {
-            u64 b = (u64)coef[N] + Q8p1;
+            u64 b = rotated_coef(coef + N, 0, rot, N, Q, false) + Q8p1;
             b = b >= Q ? b - Q : b;
             base = round_qQ(b, qKS, Q);
             if (dbg_lweN) dbg_lweN[(size_t)boot * (N + 1) + N] = base;

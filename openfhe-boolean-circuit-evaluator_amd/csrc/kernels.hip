@@ -719,17 +719,6 @@ __device__ __forceinline__ uint4 bsk_row(__amdgpu_buffer_rsrc_t rsrc, u32 voff, 
 }
 
 
-// gate constant q1 of BootstrapGateCore (OR 5q/8, AND 7q/8, NOR q/8, NAND 3q/8)
-__device__ __forceinline__ u32 gate_const(u32 op, u32 q) {
-    u32 e = q >> 3;
-    switch (op) {
-        case BCE_OR: case BCE_XOR_FAST: return 5 * e;
-        case BCE_NOR: case BCE_XNOR_FAST: return e;
-        case BCE_NAND: return 3 * e;
-        default: return 7 * e;  // AND, REFRESH
-    }
-}
-
 // Tail of one GINX MAC item: sp / sn are the 64-bit row sums against key+ / key- at the 4 consecutive
 // evaluation positions p0..p0+3; multiplies them by the monomials psi^(+-(2k+1)a') - 1 and accumulates
 // into the 4 accumulator words read at accp, written to accw (also returned in a[], values < 2Q when LAZY).
@@ -831,10 +820,11 @@ __device__ __forceinline__ void bootstrap_prologue(const PT& P, const bce_gate_d
     constexpr int N = C::N, NP = C::NP;
     const u32 Q = P.Q, q = P.q, qm = q - 1, n = P.n;
     for (u32 i = tid; i < (u32)N; i += T) twf[i] = P.tw_f[i];
+    const u32 op = g.op & 0xFFu;   // bits 8..15: the second gate of a pair (BCE_PAIR), the tail's business
     {   // EvalBinGate LWE prep with folded EvalNOT: (-a, q/4 - b)
         const u32* in0 = P.pool + (size_t)(g.in0 + soff) * P.pool_stride;
         const u32* in1 = P.pool + (size_t)(g.in1 + soff) * P.pool_stride;
-        const bool two = g.op <= BCE_XNOR_FAST;
+        const bool two = op <= BCE_XNOR_FAST;
         for (u32 i = tid; i <= n; i += T) {
             u32 v0 = in0[i];
             if (g.neg0) v0 = ((i == n ? (q >> 2) : 0u) - v0) & qm;
@@ -842,7 +832,7 @@ __device__ __forceinline__ void bootstrap_prologue(const PT& P, const bce_gate_d
             if (two) {
                 u32 v1 = in1[i];
                 if (g.neg1) v1 = ((i == n ? (q >> 2) : 0u) - v1) & qm;
-                v = (g.op == BCE_XOR_FAST || g.op == BCE_XNOR_FAST) ? (2u * (v0 - v1)) & qm : (v0 + v1) & qm;
+                v = (op == BCE_XOR_FAST || op == BCE_XNOR_FAST) ? (2u * (v0 - v1)) & qm : (v0 + v1) & qm;
             } else if (i == n) {
                 v = (v0 + (q >> 2)) & qm;  // Bootstrap(): ct + q/4
             }
@@ -852,7 +842,7 @@ __device__ __forceinline__ void bootstrap_prologue(const PT& P, const bce_gate_d
     __syncthreads();
     {   // BootstrapGateCore: acc = (0, m(X)), m sparse with +-(Q/8+1)
         const u32 b = av[n];
-        const u32 q1 = gate_const(g.op, q), q2 = (q1 + (q >> 1)) & qm;
+        const u32 q1 = gate_const(op, q), q2 = (q1 + (q >> 1)) & qm;
         const u32 pos = P.Q8p1, neg = Q - P.Q8p1;
         for (u32 j = tid; j < (u32)N; j += T) {
             u32 v = 0;
@@ -1531,6 +1521,16 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
         u32* outp = P.pool + (size_t)(g.out + soff) * P.pool_stride;
         if (P.ksk_u16) fused_tail<uint16_t, T>(P, acc, rowidx, red, outp, boot, dbg_lweN, dbg_ks);
         else fused_tail<u32, T>(P, acc, rowidx, red, outp, boot, dbg_lweN, dbg_ks);
+        // a pair descriptor (BCE_PAIR) runs the tail a second time, on X^e * acc, into slot out + 1 (debug rows: a second block
+        // of gridDim.x rows); the branch is workgroup-uniform, the barrier frees rowidx / red.  The dataflow kernel has no pairs.
+        if constexpr (!PERSIST) {
+            if (g.op >> 8) {
+                __syncthreads();
+                const u32 e = pair_rotation(P, g.op), row = boot + gridDim.x;
+                if (P.ksk_u16) fused_tail<uint16_t, T>(P, acc, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, e);
+                else fused_tail<u32, T>(P, acc, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, e);
+            }
+        }
     }
 }
 
@@ -1777,9 +1777,13 @@ hipError_t launch_blind_rotate(const DevParams& P, const bce_gate_desc* d, u32 n
 //   k_tail_finish: grid = bootstraps.  Sums the S partials, reduces mod qKS, subtracts from (0, b) and applies
 //     ModSwitch(qKS -> q) into the pool.
 // KT = key-switch key element type (u16 when qKS <= 2^16), AW = accumulator word of the blind rotation.
-template <typename KT, typename AW>
+// PAIR: the second pass of a launch that holds pair descriptors (BCE_PAIR): the same tail on X^e * acc (pair_rotation,
+// fused_tail.hpp) into slot out + 1; workgroups of plain descriptors leave at once.  Debug rows of the second pass: a
+// second block of `bootstraps` rows.
+template <typename KT, typename AW, bool PAIR>
 __global__ __launch_bounds__(256) void k_tail_gather(DevParams P, u32 S, const AW* __restrict__ acc_in,
-                                                     u64* __restrict__ partial, u32* __restrict__ dbg_lweN) {
+                                                     u64* __restrict__ partial, u32* __restrict__ dbg_lweN,
+                                                     const bce_gate_desc* __restrict__ descs, u32 n_desc) {
     extern __shared__ __align__(16) u32 smem[];
     constexpr u32 VW = 16 / sizeof(KT);  // elements per 16-byte load
     const u32 N = P.N, n = P.n, qKS = P.qKS, B = P.baseKS, D = P.dKS;
@@ -1787,6 +1791,13 @@ __global__ __launch_bounds__(256) void k_tail_gather(DevParams P, u32 S, const A
     const u32 tid = threadIdx.x, lane = tid & 63;
     const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const u32 boot = blockIdx.x / S, s = blockIdx.x - boot * S;
+    u32 rot = 0, dbg_row = boot;
+    if constexpr (PAIR) {
+        const u32 op = descs[boot % n_desc].op;
+        if (!(op >> 8)) return;
+        rot = pair_rotation(P, op);
+        dbg_row = boot + gridDim.x / S;
+    }
     const u32 ni = N / S, i0 = s * ni, LR = ni * D;  // coefficients / rows of this workgroup
     u32* rowidx = smem;                                   // [LR] row number (i*B + digit)*D + j
     u64* red = reinterpret_cast<u64*>(smem + ((LR + 3) & ~3u));  // [slices][Gv*VW] or [256] (scalar pass)
@@ -1795,10 +1806,9 @@ __global__ __launch_bounds__(256) void k_tail_gather(DevParams P, u32 S, const A
     // Transpose (X -> X^-1) of acc[0]: a'_0 = a_0, a'_{N-i} = -a_i ; then ModSwitch(Q -> qKS)
     for (u32 ii = tid; ii < ni; ii += 256) {
         const u32 i = i0 + ii;
-        const u64 src = (i == 0) ? a0[0] : a0[N - i];
-        const u64 v = (i == 0) ? src : (src ? Q - src : 0);
+        const u64 v = rotated_coef(a0, i == 0 ? 0 : N - i, rot, N, Q, i != 0);
         u32 at = round_qQ(v, qKS, Q);
-        if (dbg_lweN) dbg_lweN[(size_t)boot * (N + 1) + i] = at;
+        if (dbg_lweN) dbg_lweN[(size_t)dbg_row * (N + 1) + i] = at;
         for (u32 j = 0; j < D; ++j) {
             rowidx[ii * D + j] = (i * B + at % B) * D + j;
             at /= B;
@@ -1880,7 +1890,7 @@ __global__ __launch_bounds__(256) void k_tail_gather(DevParams P, u32 S, const A
     }
 }
 
-template <typename AW>
+template <typename AW, bool PAIR>
 __global__ __launch_bounds__(256) void k_tail_finish(DevParams P, const bce_gate_desc* __restrict__ descs, u32 n_desc, u32 slot_stride,
                                                      u32 S, const AW* __restrict__ acc_in, const u64* __restrict__ partial,
                                                      u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks) {
@@ -1889,7 +1899,13 @@ __global__ __launch_bounds__(256) void k_tail_finish(DevParams P, const bce_gate
     const u64 Q8p1 = sizeof(AW) == 8 ? P.Q8p1_64 : (u64)P.Q8p1;
     const u32 boot = blockIdx.x;
     const bce_gate_desc g = descs[boot % n_desc];
-    u32* out = P.pool + (size_t)(g.out + (boot / n_desc) * slot_stride) * P.pool_stride;
+    u32 rot = 0, dbg_row = boot;
+    if constexpr (PAIR) {
+        if (!(g.op >> 8)) return;
+        rot = pair_rotation(P, g.op);
+        dbg_row = boot + gridDim.x;
+    }
+    u32* out = P.pool + (size_t)(g.out + (PAIR ? 1u : 0u) + (boot / n_desc) * slot_stride) * P.pool_stride;
     const u64* part = partial + (size_t)boot * S * (n + 1);
     // KeySwitch: a' = -sum_rows A[row], b' = b - sum_rows B[row]   (mod qKS), b = acc[1][0] + Q/8 + 1 mod-switched
     for (u32 k = threadIdx.x; k <= n; k += 256) {
@@ -1898,13 +1914,13 @@ __global__ __launch_bounds__(256) void k_tail_finish(DevParams P, const bce_gate
         const u32 sm = (u32)(sum % qKS);
         u32 base = 0;
         if (k == n) {
-            u64 b = (u64)acc_in[(size_t)boot * 2 * N + N] + Q8p1;
+            u64 b = rotated_coef(acc_in + (size_t)boot * 2 * N + N, 0, rot, N, Q, false) + Q8p1;
             b = b >= Q ? b - Q : b;
             base = round_qQ(b, qKS, Q);
-            if (dbg_lweN) dbg_lweN[(size_t)boot * (N + 1) + N] = base;
+            if (dbg_lweN) dbg_lweN[(size_t)dbg_row * (N + 1) + N] = base;
         }
         const u32 v = base >= sm ? base - sm : base + qKS - sm;
-        if (dbg_ks) dbg_ks[(size_t)boot * (n + 1) + k] = v;
+        if (dbg_ks) dbg_ks[(size_t)dbg_row * (n + 1) + k] = v;
         out[k] = round_qQ(v, P.q, qKS);  // ModSwitch(qKS -> q)
     }
 }
@@ -1918,29 +1934,32 @@ u32 tail_split(const DevParams& P, u32 boots) {
 size_t tail_partial_words(const DevParams& P, u32 boots) { return (size_t)boots * tail_split(P, boots) * (P.n + 1); }
 
 hipError_t launch_tail(const DevParams& P, const bce_gate_desc* d, u32 n_desc, u32 instances, u32 slot_stride,
-                       const void* acc_in, u64* partial, u32* dbg_lweN, u32* dbg_ks, hipStream_t s, LaunchEvents ev) {
+                       const void* acc_in, u64* partial, u32* dbg_lweN, u32* dbg_ks, hipStream_t s, LaunchEvents ev, bool pairs) {
     const u32 boots = n_desc * instances, S = tail_split(P, boots);
     const dim3 grid(boots * S), block(256);
     const u32 VW = P.ksk_u16 ? 8 : 4, G = (P.n + VW) / VW, Gv = G < 256 ? G : 256, RW = (Gv + 63) / 64, SL = 4 / RW;
     const size_t LR = (size_t)P.N / S * P.dKS;
     const size_t red_words = std::max<size_t>((size_t)SL * Gv * VW, 256);
     const size_t lds = ((LR + 3) & ~(size_t)3) * sizeof(u32) + red_words * sizeof(u64);
-    const LaunchEvents first{ev.start, nullptr}, last{nullptr, ev.stop};
-    // the gather carries the start timestamp, the finish the stop (plain launches when none was asked for)
+    // the first gather carries the start timestamp, the last finish the stop (plain launches when none was asked for)
+    const LaunchEvents none{}, first{ev.start, nullptr}, last{nullptr, ev.stop};
     auto go = [&](auto kern, dim3 g, size_t l, LaunchEvents e, auto... args) { return launch_kernel(kern, g, block, l, s, e, args...); };
-    hipError_t rc;
-    if (P.is64) {
-        const u64* a = static_cast<const u64*>(acc_in);
-        if (P.ksk_u16) rc = go(k_tail_gather<uint16_t, u64>, grid, lds, first, P, S, a, partial, dbg_lweN);
-        else rc = go(k_tail_gather<u32, u64>, grid, lds, first, P, S, a, partial, dbg_lweN);
+    // one pass: gather + finish; the second pass of a launch with pairs reuses `partial` (stream order)
+    auto pass = [&](auto aw, auto pair, LaunchEvents e0, LaunchEvents e1) {
+        using AW = decltype(aw);
+        constexpr bool PAIR = decltype(pair)::value;
+        const AW* a = static_cast<const AW*>(acc_in);
+        const hipError_t rc = P.ksk_u16 ? go(k_tail_gather<uint16_t, AW, PAIR>, grid, lds, e0, P, S, a, partial, dbg_lweN, d, n_desc)
+                                        : go(k_tail_gather<u32, AW, PAIR>, grid, lds, e0, P, S, a, partial, dbg_lweN, d, n_desc);
         if (rc != hipSuccess) return rc;
-        return go(k_tail_finish<u64>, dim3(boots), 0, last, P, d, n_desc, slot_stride, S, a, partial, dbg_lweN, dbg_ks);
-    }
-    const u32* a = static_cast<const u32*>(acc_in);
-    if (P.ksk_u16) rc = go(k_tail_gather<uint16_t, u32>, grid, lds, first, P, S, a, partial, dbg_lweN);
-    else rc = go(k_tail_gather<u32, u32>, grid, lds, first, P, S, a, partial, dbg_lweN);
-    if (rc != hipSuccess) return rc;
-    return go(k_tail_finish<u32>, dim3(boots), 0, last, P, d, n_desc, slot_stride, S, a, partial, dbg_lweN, dbg_ks);
+        return go(k_tail_finish<AW, PAIR>, dim3(boots), 0, e1, P, d, n_desc, slot_stride, S, a, partial, dbg_lweN, dbg_ks);
+    };
+    auto both = [&](auto aw) {
+        const hipError_t rc = pass(aw, std::false_type{}, first, pairs ? none : last);
+        if (rc != hipSuccess || !pairs) return rc;
+        return pass(aw, std::true_type{}, none, last);
+    };
+    return P.is64 ? both(u64{}) : both(u32{});
 }
 
 // ---------------------------------------------------------------------------------------

@@ -220,10 +220,13 @@ hipError_t launch_blind_rotate(const DevParams& P, const bce_gate_desc* d_descs,
 // extract + ModSwitch(Q->qKS) + KeySwitch + ModSwitch(qKS->q) -> pool[out]
 // dbg_lweN: u32 [n_boot][N+1] or null; dbg_ks: u32 [n_boot][n+1] or null
 // partial: device scratch of tail_partial_words(P, n_desc * instances) u64 words (partial key-switch sums)
+// pairs: the descriptors hold at least one BCE_PAIR: both kernels run a second time for the second outputs (slot out + 1;
+// the debug buffers then have 2 n_boot rows, the second outputs in the second half).  A blind-rotation kernel that fuses
+// the tail runs the second pass itself.
 size_t tail_partial_words(const DevParams& P, u32 boots);
 hipError_t launch_tail(const DevParams& P, const bce_gate_desc* d_descs, u32 n_desc, u32 instances, u32 slot_stride,
                        const void* acc_in /* u32 or u64 words by P.is64 */, u64* partial, u32* dbg_lweN, u32* dbg_ks,
-                       hipStream_t s, LaunchEvents ev = {});   // ev.start on the first kernel, ev.stop on the last
+                       hipStream_t s, LaunchEvents ev = {}, bool pairs = false);   // ev.start on the first kernel, ev.stop on the last
 
 // key words u64 <-> IEEE double in place (layout of the double-precision formulation, kernels64.hip)
 hipError_t launch_words_u64_f64(u64* words, size_t count, int to_double, hipStream_t s);

@@ -222,16 +222,6 @@ __device__ __forceinline__ u64 psi_pow(const ulonglong2* tw, u32 e, u64 Q) {
     return (e & N) ? Q - v : v;
 }
 
-__device__ __forceinline__ u32 gate_const(u32 op, u32 q) {
-    const u32 e = q >> 3;
-    switch (op) {
-        case BCE_OR: case BCE_XOR_FAST: return 5 * e;
-        case BCE_NOR: case BCE_XNOR_FAST: return e;
-        case BCE_NAND: return 3 * e;
-        default: return 7 * e;
-    }
-}
-
 // LDS of one workgroup of k_blind_rotate64, in 64-bit words: used by the kernel and by kernel_class64.
 // narrow: the R digit rows are 32-bit words (Q < 2^31: a digit + Q and every normalised transform value fit), the inverse
 // transforms get a scratch of their own -- what lets N = 2048 with FOUR gadget digits (STD256, STD256_OPT: 29-bit Q, base 2^8)
@@ -274,10 +264,11 @@ __global__ __launch_bounds__(128 * DG) void k_blind_rotate64(DevParams P, const 
     const u32 q = P.q, qm = q - 1, n = P.n;
     const bce_gate_desc g = descs[blockIdx.x % n_desc];
     const u32 soff = (blockIdx.x / n_desc) * slot_stride;
+    const u32 op = g.op & 0xFFu;   // bits 8..15: the second gate of a pair (BCE_PAIR), the tail's business
     {
         const u32* in0 = P.pool + (size_t)(g.in0 + soff) * P.pool_stride;
         const u32* in1 = P.pool + (size_t)(g.in1 + soff) * P.pool_stride;
-        const bool two = g.op <= BCE_XNOR_FAST;
+        const bool two = op <= BCE_XNOR_FAST;
         for (u32 i = tid; i <= n; i += T) {
             u32 v0 = in0[i];
             if (g.neg0) v0 = ((i == n ? (q >> 2) : 0u) - v0) & qm;
@@ -285,7 +276,7 @@ __global__ __launch_bounds__(128 * DG) void k_blind_rotate64(DevParams P, const 
             if (two) {
                 u32 v1 = in1[i];
                 if (g.neg1) v1 = ((i == n ? (q >> 2) : 0u) - v1) & qm;
-                v = (g.op == BCE_XOR_FAST || g.op == BCE_XNOR_FAST) ? (2u * (v0 - v1)) & qm : (v0 + v1) & qm;
+                v = (op == BCE_XOR_FAST || op == BCE_XNOR_FAST) ? (2u * (v0 - v1)) & qm : (v0 + v1) & qm;
             } else if (i == n) {
                 v = (v0 + (q >> 2)) & qm;
             }
@@ -295,7 +286,7 @@ __global__ __launch_bounds__(128 * DG) void k_blind_rotate64(DevParams P, const 
     __syncthreads();
     {
         const u32 b = av[n];
-        const u32 q1 = gate_const(g.op, q), q2 = (q1 + (q >> 1)) & qm;
+        const u32 q1 = gate_const(op, q), q2 = (q1 + (q >> 1)) & qm;
         const u64 pos = P.Q8p1_64, neg = Q - P.Q8p1_64;
         for (u32 j = tid; j < (u32)N; j += T) {
             u64 v = 0;
@@ -535,7 +526,6 @@ using w64::wave_sync;
 using w64::block_sync_lds;
 constexpr int INV_BARRIERS = 1;   // workgroup barriers inside split_inverse11 (its other exchanges stay inside one wave)
 using w64::for_each_index;
-using w64::gate_const;
 
 // Twiddle table access: entries [0, lds_n) are mirrored in LDS (the 8-wave N = 2048 kernel has room for the first
 // 1024 = every stage except the one on bit 0), the rest is read from global memory.  The block a stage uses
@@ -1130,10 +1120,11 @@ __device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g,
     const Tw twa{tw, twl, twl1, invQ};
 
     const u32 q = P.q, qm = q - 1, n = P.n;
+    const u32 op = g.op & 0xFFu;   // bits 8..15: the second gate of a pair (BCE_PAIR), the tail's business
     {
         const u32* in0 = P.pool + (size_t)(g.in0 + soff) * P.pool_stride;
         const u32* in1 = P.pool + (size_t)(g.in1 + soff) * P.pool_stride;
-        const bool two = g.op <= BCE_XNOR_FAST;
+        const bool two = op <= BCE_XNOR_FAST;
         for (u32 i = tid; i <= n; i += T) {
             u32 v0 = in0[i];
             if (g.neg0) v0 = ((i == n ? (q >> 2) : 0u) - v0) & qm;
@@ -1141,7 +1132,7 @@ __device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g,
             if (two) {
                 u32 v1 = in1[i];
                 if (g.neg1) v1 = ((i == n ? (q >> 2) : 0u) - v1) & qm;
-                v = (g.op == BCE_XOR_FAST || g.op == BCE_XNOR_FAST) ? (2u * (v0 - v1)) & qm : (v0 + v1) & qm;
+                v = (op == BCE_XOR_FAST || op == BCE_XNOR_FAST) ? (2u * (v0 - v1)) & qm : (v0 + v1) & qm;
             } else if (i == n) {
                 v = (v0 + (q >> 2)) & qm;
             }
@@ -1151,7 +1142,7 @@ __device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g,
     __syncthreads();
     {
         const u32 b = av[n];
-        const u32 q1 = gate_const(g.op, q), q2 = (q1 + (q >> 1)) & qm;
+        const u32 q1 = gate_const(op, q), q2 = (q1 + (q >> 1)) & qm;
         const double pos = (double)P.Q8p1_64, neg = -pos;
         for (u32 j = tid; j < (u32)N; j += T) {
             double v = 0.0;
@@ -1433,6 +1424,15 @@ __device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g,
         const u64* coef = reinterpret_cast<const u64*>(acc);
         if (P.ksk_u16) fused_tail<uint16_t, T>(P, coef, rowidx, red, outp, boot, dbg_lweN, dbg_ks);
         else fused_tail<u32, T>(P, coef, rowidx, red, outp, boot, dbg_lweN, dbg_ks);
+        // a pair descriptor (BCE_PAIR): second tail pass on X^e * acc into slot out + 1, as in lat_bootstrap (kernels.hip)
+        if constexpr (!PERSIST) {
+            if (g.op >> 8) {
+                __syncthreads();
+                const u32 e = pair_rotation(P, g.op), row = boot + gridDim.x;
+                if (P.ksk_u16) fused_tail<uint16_t, T>(P, coef, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, e);
+                else fused_tail<u32, T>(P, coef, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, e);
+            }
+        }
     }
 }
 

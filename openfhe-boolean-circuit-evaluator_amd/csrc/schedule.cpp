@@ -7,8 +7,8 @@
 
 namespace bce::sched {
 
-uint32_t gate_weight(Op op, bool xor_fast) {
-    return op == Op::XOR ? (xor_fast ? 1 : 3) : (op == Op::AND || op == Op::OR) ? 1 : 0;
+uint32_t gate_weight(Op op, XorMode mode) {
+    return op == Op::XOR ? (mode == XorMode::Fast ? 1 : mode == XorMode::Shared ? 2 : 3) : (op == Op::AND || op == Op::OR) ? 1 : 0;
 }
 
 void xor_lower(const bce_gate_desc& u, uint32_t t1, uint32_t t2, bce_gate_desc out[3]) {
@@ -17,8 +17,13 @@ void xor_lower(const bce_gate_desc& u, uint32_t t1, uint32_t t2, bce_gate_desc o
     out[2] = {BCE_OR, t1, t2, u.out, 0, 0};
 }
 
+void xor_lower_shared(const bce_gate_desc& u, uint32_t t, bce_gate_desc out[2]) {
+    out[0] = {BCE_PAIR(BCE_OR, BCE_NAND), u.in0, u.in1, t, u.neg0, u.neg1};
+    out[1] = {BCE_AND, t, t + 1, u.out, 0, 0};
+}
+
 // units in topological order (NOT chains resolved into negation flags), their successors (CSR) and ALAP start steps
-Units build_units(const Dag& dag, bool xor_fast) {
+Units build_units(const Dag& dag, XorMode mode) {
     Units S;
     const size_t W = dag.n_wires;
     S.base.resize(W);
@@ -40,12 +45,13 @@ Units build_units(const Dag& dag, bool xor_fast) {
             Unit u{d, d, 1, 0, {0, b0, b1, (uint32_t)g.out, n0, n1}, prod[b0], prod[b1]};
             if (g.op != Op::XOR) {
                 u.d.op = (uint32_t)(g.op == Op::AND ? BCE_AND : BCE_OR);
-            } else if (xor_fast) {
+            } else if (mode == XorMode::Fast) {
                 // XOR_FAST of negated inputs: NOT a XOR NOT b = a XOR b; one negation flips the result
                 u.d.op = (uint32_t)((n0 ^ n1) ? BCE_XNOR_FAST : BCE_XOR_FAST);
                 u.d.neg0 = u.d.neg1 = 0;
             } else {
                 u.lat = 2;
+                u.shared = mode == XorMode::Shared;
             }
             depth[g.out] = d + u.lat - 1;
             prod[g.out] = (int32_t)units.size();
@@ -89,7 +95,7 @@ void place_by_slack(Units& S, uint64_t K, uint32_t lone, uint32_t full) {
         waiting[i] = (u.p0 >= 0) + (u.p1 >= 0 && u.p1 != u.p0);
         if (!waiting[i]) ready.push({alap[i], (uint32_t)i});
     }
-    std::vector<uint32_t> ors_due(D + 2, 0);   // ORs of the XORs started one step earlier
+    std::vector<uint32_t> ors_due(D + 2, 0);   // ORs (shared mode: ANDs) of the XORs started one step earlier
     std::vector<uint32_t> chosen;
     for (uint32_t s = 1; s <= D; ++s) {
         for (uint32_t i : later[s]) ready.push({alap[i], i});
@@ -237,11 +243,13 @@ StepPlan lower_steps(const Units& S, const Dag& dag, uint32_t rank, uint32_t wor
     for (const auto& u : S.units) {
         if (sharded && u.owner != rank) continue;
         if (u.lat == 1) { P.steps[u.start - 1].push_back(u.d); continue; }
-        const uint32_t idx = xor_at[u.start]++;
+        const uint32_t idx = xor_at[u.start]++, t = W + (u.start & 1) * 2 * max_x + 2 * idx;
         bce_gate_desc x[3];
-        xor_lower(u.d, W + (u.start & 1) * 2 * max_x + 2 * idx, W + (u.start & 1) * 2 * max_x + 2 * idx + 1, x);
-        P.steps[u.start - 1].insert(P.steps[u.start - 1].end(), x, x + 2);
-        P.steps[u.start].push_back(x[2]);   // the OR one step later
+        if (u.shared) xor_lower_shared(u.d, t, x);
+        else xor_lower(u.d, t, t + 1, x);
+        const int first = u.shared ? 1 : 2;   // descriptors of the start step; the last one runs one step later
+        P.steps[u.start - 1].insert(P.steps[u.start - 1].end(), x, x + first);
+        P.steps[u.start].push_back(x[first]);
     }
     // NOT wires consumed by OUTPUT gates need a real ciphertext (decrypt must see EvalNOT's output); double negation: a copy
     std::vector<uint8_t> done_not(W, 0);
@@ -264,6 +272,7 @@ TaskList lower_tasks(const Units& S, uint32_t n_wires) {
         const uint32_t slack = S.alap[i] - u.asap;
         const uint8_t pc = slack == 0 ? 0 : slack <= 1 ? 1 : slack <= 2 ? 2 : 3;
         if (u.lat == 1) { T.tasks.push_back(u.d); T.prio.push_back(pc); continue; }
+        if (u.shared) throw std::logic_error("lower_tasks: the dataflow schedule has no shared XORs");
         bce_gate_desc x[3];
         xor_lower(u.d, n_wires + 2 * nx, n_wires + 2 * nx + 1, x);
         ++nx;
@@ -291,10 +300,14 @@ bool check(const StepPlan& P, const Dag& dag, uint32_t rank, uint32_t world, std
                 }
             }
         for (const auto& d : P.steps[s]) {
-            if (d.out >= P.stride) return fail("output slot outside the stride");
-            if (d.out < W && written[d.out] >= 0) return fail("register written twice");
-            if (written[d.out] == (int32_t)s) return fail("slot written twice in one step");
-            written[d.out] = (int32_t)s;
+            const uint32_t outs = (d.op >> 8) ? 2 : 1;   // a pair writes out and out + 1, both temporaries
+            if (outs == 2 && d.out < W) return fail("a pair writes a netlist register");
+            for (uint32_t o = d.out; o < d.out + outs; ++o) {
+                if (o >= P.stride) return fail("output slot outside the stride");
+                if (o < W && written[o] >= 0) return fail("register written twice");
+                if (written[o] == (int32_t)s) return fail("slot written twice in one step");
+                written[o] = (int32_t)s;
+            }
         }
         // gate sharding: what the other ranks publish after this step arrives before the next one
         if (s < P.publish.size())

@@ -20,27 +20,39 @@ struct Dag {
     std::vector<int> outputs;          // the wires the OUTPUT gates read, in FILE order
 };
 
-uint32_t gate_weight(Op op, bool xor_fast);   // bootstraps per gate (src/gate.cpp:133,172,200-202)
-// the ONE place that spells the XOR: (a AND !b) -> t1, (!a AND b) -> t2 with u's own negations folded in, then t1 OR t2 -> u.out
+// How an XOR gate is evaluated.  Reference: the reference's three bootstraps (src/gate.cpp:198-202).  Fast: one XOR_FAST
+// bootstrap of 2 (ct1 - ct2) (eight times the input variance).  Shared: AND(OR(a, b), NAND(a, b)) with the OR and the NAND
+// from ONE blind rotation (a BCE_PAIR descriptor): two blind rotations, the same depth and the same inputs' noise as Reference.
+enum class XorMode : uint8_t { Reference, Fast, Shared };
+inline XorMode xor_mode(bool xor_fast) { return xor_fast ? XorMode::Fast : XorMode::Reference; }
+uint32_t gate_weight(Op op, XorMode mode);   // blind rotations per gate (src/gate.cpp:133,172,200-202)
+inline uint32_t gate_weight(Op op, bool xor_fast) { return gate_weight(op, xor_mode(xor_fast)); }
+// the two places that spell an XOR, with u's own negations folded in:
+//   (a AND !b) -> t1, (!a AND b) -> t2, then t1 OR t2 -> u.out
 void xor_lower(const bce_gate_desc& u, uint32_t t1, uint32_t t2, bce_gate_desc out[3]);
+//   the pair (a OR b) -> t, (a NAND b) -> t + 1 from one blind rotation, then t AND (t + 1) -> u.out
+void xor_lower_shared(const bce_gate_desc& u, uint32_t t, bce_gate_desc out[2]);
 
-// Units of the schedule: a single bootstrap (AND / OR / XOR_FAST; its output is ready one step later) or an XOR built as
-// the reference builds it (lat 2: two ANDs in step `start`, their OR in step start + 1; d holds in0, in1, out, neg0, neg1).
+// Units of the schedule: a single bootstrap (AND / OR / XOR_FAST; its output is ready one step later) or an XOR of lat 2:
+// built as the reference builds it (two ANDs in step `start`, their OR in step start + 1) or, `shared`, as a pair in step
+// `start` and an AND in step start + 1; d holds in0, in1, out, neg0, neg1.
 struct Unit {
     uint32_t asap, start;
     uint8_t lat, owner;
     bce_gate_desc d;
     int32_t p0, p1;   // producing units of the inputs, -1 = primary input / constant
-    uint32_t weight() const { return lat == 2 ? 2 : 1; }   // bootstraps in the unit's start step
+    uint8_t shared = 0;
+    uint32_t weight() const { return lat == 2 && !shared ? 2 : 1; }   // blind rotations in the unit's start step
 };
-struct Units {   // a function of (netlist, xor_fast) except Unit::start and Unit::owner, which placement and assign_owners set
+struct Units {   // a function of (netlist, XOR mode) except Unit::start and Unit::owner, which placement and assign_owners set
     std::vector<Unit> units;             // topological order
     std::vector<int> base;               // wire -> wire at the bottom of its NOT chain
     std::vector<uint8_t> neg;            // wire -> parity of that chain
     uint32_t depth = 0;                  // bootstrap depth D = steps of the schedule
     std::vector<uint32_t> soff, succ, alap;   // successors (CSR) and ALAP start steps
 };
-Units build_units(const Dag&, bool xor_fast);
+Units build_units(const Dag&, XorMode mode);
+inline Units build_units(const Dag& dag, bool xor_fast) { return build_units(dag, xor_mode(xor_fast)); }
 inline void place_asap(Units& S) { for (auto& u : S.units) u.start = u.asap; }
 // the same D steps filled by SLACK: a step of K x count bootstraps is topped up to the next stair of the launch staircase
 // (`lone` bootstraps cost one latency, then one round per `full`) with the ready units of least slack
@@ -57,13 +69,15 @@ struct StepPlan {
 };
 StepPlan lower_steps(const Units&, const Dag&, uint32_t rank, uint32_t world, uint64_t K);   // world 1 = not sharded
 struct TaskList { std::vector<bce_gate_desc> tasks; std::vector<uint8_t> prio; uint32_t stride = 0; };
-TaskList lower_tasks(const Units&, uint32_t n_wires);   // SSA: every XOR owns its temporaries; prio = slack class
-// every step reads only what earlier steps wrote (or received), every XOR temporary is read one step after it is written
+TaskList lower_tasks(const Units&, uint32_t n_wires);   // SSA: every XOR owns its temporaries; prio = slack class (no shared XORs:
+                                                         // the dataflow kernel runs one tail per bootstrap)
+// every step reads only what earlier steps wrote (or received), every XOR temporary is read one step after it is written; a
+// pair descriptor writes two adjacent temporaries
 bool check(const StepPlan&, const Dag&, uint32_t rank, uint32_t world, std::string* why = nullptr);
 
 // Verify mode on the step schedule (the reference decrypts and compares every GATE output, src/gate.cpp:153-160): per step,
-// the descriptors whose `out` is a netlist wire -- AND, OR, the final OR of a lowered XOR, XOR_FAST / XNOR_FAST -- as the
-// register they write and the gate (index into Dag::gates) that owns it.  An XOR's two temporaries are not listed.  NOT
+// the descriptors whose `out` is a netlist wire -- AND, OR, the final OR (AND, in shared mode) of a lowered XOR, XOR_FAST /
+// XNOR_FAST -- as the register they write and the gate (index into Dag::gates) that owns it.  An XOR's two temporaries are not listed.  NOT
 // gates have no register on this schedule: a wrong NOT input shows at its consumer.
 struct CheckLists {
     std::vector<std::vector<uint32_t>> wires;   // [step] -> registers written in that step, in descriptor order
