@@ -16,12 +16,12 @@
 #include <memory>
 #include <mutex>
 #include <unordered_set>
-#include <type_traits>
 #include <string>
 #include <vector>
 
 #include "../../include/bce_circuit.h"
 #include "../../include/bce_gpu.h"
+#include "devmem.hpp"
 #include "fwd_mfma.hpp"
 #include "host_math.hpp"
 #include "kernels.hpp"
@@ -92,20 +92,18 @@ struct bce_ctx {
     int method = 0, device = 0;
     std::string err;
 
+    // every device / pinned buffer below owns its memory (devmem.hpp); bce_ctx_destroy keeps what has an order
     hipStream_t stream = nullptr;
-    DevParams P{};
+    DevParams P{};   // its pointers mirror the owning members below, set where those are allocated
     // device tables / keys
-    uint2* d_twf = nullptr;
-    u32* d_fwd_mfma = nullptr;
-    u32* d_psi = nullptr;
-    u32* d_psi_r2 = nullptr;
-    u32* d_xcd_gate = nullptr;
-    void* d_bsk = nullptr;       // u32 words (Q < 2^28) or u64 words (is64)
-    ulonglong2* d_tw64 = nullptr;
-    double2* d_tw64d = nullptr;   // (w, w / Q) for the double-precision formulation
+    DevBuf<uint2> d_twf;
+    DevBuf<u32> d_fwd_mfma, d_psi, d_psi_r2, d_xcd_gate;
+    DevBuf<char> d_bsk;          // u32 words (Q < 2^28) or u64 words (is64)
+    DevBuf<ulonglong2> d_tw64;
+    DevBuf<double2> d_tw64d;      // (w, w / Q) for the double-precision formulation
     bool is64 = false;
     size_t wbytes = 4;
-    void* d_ksk = nullptr;
+    DevBuf<char> d_ksk;
     u64 bsk_polys = 0;
     bool have_keys = false;
     // host secrets
@@ -119,44 +117,36 @@ struct bce_ctx {
     uint64_t enc_counter = 0;
     void* rccl_comm = nullptr;   // ncclComm_t of the in-library all-gather (rccl_xchg.cpp), if enabled
     // pool
-    u32* d_pool = nullptr;
+    DevBuf<u32> d_pool;
     u32 pool_slots = 0;
     // work buffers
-    void* d_acc = nullptr;
-    size_t acc_cap = 0;  // bootstraps
-    u64* d_tail_partial = nullptr;  // partial key-switch sums (kernels.hip, k_tail_gather)
+    DevBuf<char> d_acc;             // accumulators of the largest launch so far
+    DevBuf<u64> d_tail_partial;     // partial key-switch sums (kernels.hip, k_tail_gather)
     bool events_on = true;                 // per-launch HIP events (bce_timing_set_events): off = counters only, no event packets between dependent kernels
-    u32 *d_io = nullptr, *h_io = nullptr;  // staging of bce_lwe_read for scattered slots (device gather + one pinned copy)
-    size_t io_cap = 0;
-    size_t tail_cap = 0;            // u64 words
+    DevBuf<u32> d_io;               // staging of bce_lwe_read for scattered slots (device gather + one pinned copy)
+    DevBuf<u32, true> h_io;
     static constexpr int kRing = 4;
-    bce_gate_desc* d_descs[kRing] = {nullptr, nullptr, nullptr, nullptr};
-    bce_gate_desc* h_descs[kRing] = {nullptr, nullptr, nullptr, nullptr};
-    size_t desc_cap[kRing] = {0, 0, 0, 0};
-    hipEvent_t ring_ev[kRing] = {nullptr, nullptr, nullptr, nullptr};
-    bool ring_busy[kRing] = {false, false, false, false};
+    StagedUpload ring[kRing];       // descriptor lists of the launches in flight (stage_descs)
     int ring_pos = 0;
     // verify mode on the device (bce_check_*): the LWE secret as int8[n padded to 64] (uploaded wherever `s` is set), the
     // report block followed by the mismatch log, and the staging pair of bce_check_slots (slot list + expected bits)
-    int8_t* d_s8 = nullptr;
-    bce_check_report* d_check = nullptr;
-    bce_check_entry* d_check_log = nullptr;
-    char *d_chk_stage = nullptr, *h_chk_stage = nullptr;
-    size_t chk_cap = 0;
-    hipEvent_t chk_ev = nullptr;
-    bool chk_busy = false;
+    DevBuf<int8_t> d_s8;            // allocated once per context, never reallocated: captured plans point to it
+    DevBuf<char> d_check_mem;
+    bce_check_report* d_check() const { return reinterpret_cast<bce_check_report*>(d_check_mem.get()); }
+    bce_check_entry* d_check_log() const { return reinterpret_cast<bce_check_entry*>(d_check_mem.get() + sizeof(bce_check_report)); }
+    StagedUpload chk_stage;
     // timing
     std::vector<EventPair> pending, free_events;
     bce_timing timing{};
     // dependency-driven runs (bce_dag_*): device copy of P, knobs, and the status words of runs not yet checked
-    DevParams* d_P = nullptr;
+    DevBuf<DevParams> d_P;
     int dag_wg_per_cu = 0, dag_placement = 1;
     uint32_t dag_lazy_us = 20, dag_stall_ms = 4000;
     struct DagStatus { uint32_t abort, done, lazy_waits, pad; uint64_t busy_ticks, wait_ticks, gate_ticks; };
     static constexpr int kDagRuns = 32;
-    DagStatus* h_dag_status = nullptr;        // pinned, kDagRuns entries
+    DevBuf<DagStatus, true> h_dag_status;     // pinned, kDagRuns entries
     struct DagStage { DevParams P; DagParams D; };
-    DagStage* h_dag_stage = nullptr;          // pinned, kDagRuns entries: sources of the stream-ordered parameter uploads
+    DevBuf<DagStage, true> h_dag_stage;       // pinned, kDagRuns entries: sources of the stream-ordered parameter uploads
     uint64_t dag_expected[kDagRuns] = {0};
     int dag_wps_used[kDagRuns] = {0};
     int dag_pending = 0;
@@ -369,37 +359,42 @@ int derive_ctx(bce_ctx* c, u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 
     return BCE_OK;
 }
 
-// Second half: stream, events, and the tables of derive_ctx on the device
+// device copy of a host vector in a buffer that is still empty (one element at least)
+template <class T>
+hipError_t upload_vector(DevBuf<T>& dst, const std::vector<T>& v) {
+    const hipError_t e = dst.alloc(std::max<size_t>(1, v.size()));
+    return e != hipSuccess ? e : hipMemcpy(dst.get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+// Second half: stream, and the tables of derive_ctx on the device
 int upload_ctx(bce_ctx* c, const HostTables& T) {
     DevParams& P = c->P;
     if (hipSetDevice(c->device) != hipSuccess) { g_create_error = "hipSetDevice failed"; return BCE_ERR_HIP; }
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { g_create_error = "hipStreamCreate failed"; return BCE_ERR_HIP; }
-    // device copy of a host table; what names the table in the message of a failed allocation
-    const auto up = [](auto** dst, const auto& v, const char* what) -> bool {
-        const size_t bytes = v.size() * sizeof(v[0]);
-        if (hipMalloc(reinterpret_cast<void**>(dst), bytes) != hipSuccess) { g_create_error = std::string("hipMalloc(") + what + ") failed"; return false; }
-        hipMemcpy(*dst, v.data(), bytes, hipMemcpyHostToDevice);
-        return true;
+    // `what` names the table in the message of a failure
+    const auto up = [](auto& dst, const auto& v, const char* what) -> bool {
+        if (upload_vector(dst, v) == hipSuccess) return true;
+        g_create_error = std::string("hipMalloc(") + what + ") failed";
+        return false;
     };
-    if (!up(&c->d_twf, T.twf, "twiddles") || !up(&c->d_psi, T.psi, "psi table") || !up(&c->d_psi_r2, T.psi_r2, "psi table")) return BCE_ERR_HIP;
-    for (int i = 0; i < bce_ctx::kRing; ++i) hipEventCreateWithFlags(&c->ring_ev[i], hipEventDisableTiming);
-    P.tw_f = c->d_twf;
-    P.psi_tab = c->d_psi;
-    P.psi_tab_r2 = c->d_psi_r2;
+    if (!up(c->d_twf, T.twf, "twiddles") || !up(c->d_psi, T.psi, "psi table") || !up(c->d_psi_r2, T.psi_r2, "psi table")) return BCE_ERR_HIP;
+    P.tw_f = c->d_twf.get();
+    P.psi_tab = c->d_psi.get();
+    P.psi_tab_r2 = c->d_psi_r2.get();
     P.xcd_gate = nullptr;
     if (T.xcd_gate) {
-        if (hipMalloc(&c->d_xcd_gate, 16 * 32 * sizeof(u32)) != hipSuccess) { g_create_error = "hipMalloc(xcd gate) failed"; return BCE_ERR_HIP; }
-        P.xcd_gate = c->d_xcd_gate;
+        if (c->d_xcd_gate.alloc(16 * 32) != hipSuccess) { g_create_error = "hipMalloc(xcd gate) failed"; return BCE_ERR_HIP; }
+        P.xcd_gate = c->d_xcd_gate.get();
     }
     if (c->is64) {
-        if (!up(&c->d_tw64, T.tw64, "twiddles64") || !up(&c->d_tw64d, T.tw64d, "twiddles64d")) return BCE_ERR_HIP;
-        P.tw64 = c->d_tw64;
-        P.tw64d = c->d_tw64d;
+        if (!up(c->d_tw64, T.tw64, "twiddles64") || !up(c->d_tw64d, T.tw64d, "twiddles64d")) return BCE_ERR_HIP;
+        P.tw64 = c->d_tw64.get();
+        P.tw64d = c->d_tw64d.get();
     }
     P.fwd_mfma_tab = nullptr;
     if (P.fwd_mfma) {
-        if (!up(&c->d_fwd_mfma, T.fwd.table, "forward matrix table")) return BCE_ERR_HIP;
-        P.fwd_mfma_tab = c->d_fwd_mfma;
+        if (!up(c->d_fwd_mfma, T.fwd.table, "forward matrix table")) return BCE_ERR_HIP;
+        P.fwd_mfma_tab = c->d_fwd_mfma.get();
     }
     c->enc_seed_ok = os_entropy(c->enc_seed);
     return BCE_OK;
@@ -440,9 +435,9 @@ u64 rgsw_rows_total(const bce_ctx* c);
 // evaluation-form key words -> what the kernels read: rows l >= 1 of every RGSW ciphertext minus B^l times row 0
 // when the lowest gadget digit is folded (P.fold); IEEE doubles for the double-precision 64-bit kernels (exact, Q < 2^39)
 int bsk_words_to_kernel_layout(bce_ctx* c) {
-    if (c->P.fold) HIP_TRY(c, launch_fold_gadget(c->P, c->d_bsk, rgsw_rows_total(c) / (2ull * c->dG), +1, c->stream));
+    if (c->P.fold) HIP_TRY(c, launch_fold_gadget(c->P, c->d_bsk.get(), rgsw_rows_total(c) / (2ull * c->dG), +1, c->stream));
     if (!c->P.fp64) { HIP_TRY(c, hipStreamSynchronize(c->stream)); return BCE_OK; }
-    HIP_TRY(c, launch_words_u64_f64(static_cast<u64*>(c->d_bsk), (size_t)c->bsk_polys * c->N, 1, c->stream));
+    HIP_TRY(c, launch_words_u64_f64(reinterpret_cast<u64*>(c->d_bsk.get()), (size_t)c->bsk_polys * c->N, 1, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return BCE_OK;
 }
@@ -453,17 +448,17 @@ u64 rgsw_rows_total(const bce_ctx* c) {
 }
 
 int alloc_keys(bce_ctx* c) {
-    if (!c->d_bsk) {
+    if (!c->d_bsk.get()) {
         c->bsk_polys = rgsw_rows_total(c) * 2;
-        HIP_TRY(c, hipMalloc(&c->d_bsk, c->wbytes * c->bsk_polys * c->N));
+        HIP_TRY(c, c->d_bsk.alloc(c->wbytes * c->bsk_polys * c->N));
     }
-    if (!c->d_ksk) {
+    if (!c->d_ksk.get()) {
         size_t rows = (size_t)c->N * c->baseKS * c->dKS;
-        HIP_TRY(c, hipMalloc(&c->d_ksk, rows * c->P.ksk_stride * (c->P.ksk_u16 ? 2 : 4)));
+        HIP_TRY(c, c->d_ksk.alloc(rows * c->P.ksk_stride * (c->P.ksk_u16 ? 2 : 4)));
     }
-    c->P.bsk = static_cast<const u32*>(c->d_bsk);
-    c->P.bsk64 = static_cast<const u64*>(c->d_bsk);
-    c->P.ksk = c->d_ksk;
+    c->P.bsk = reinterpret_cast<const u32*>(c->d_bsk.get());
+    c->P.bsk64 = reinterpret_cast<const u64*>(c->d_bsk.get());
+    c->P.ksk = c->d_ksk.get();
     return BCE_OK;
 }
 
@@ -474,11 +469,11 @@ int upload_ksk(bce_ctx* c, const u32* ksk) {
         std::vector<uint16_t> buf(rows * S, 0);
         for (size_t r = 0; r < rows; ++r)
             for (size_t k = 0; k < W; ++k) buf[r * S + k] = (uint16_t)ksk[r * W + k];
-        HIP_TRY(c, hipMemcpy(c->d_ksk, buf.data(), buf.size() * 2, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(c->d_ksk.get(), buf.data(), buf.size() * 2, hipMemcpyHostToDevice));
     } else {
         std::vector<u32> buf(rows * S, 0);
         for (size_t r = 0; r < rows; ++r) std::memcpy(&buf[r * S], &ksk[r * W], W * 4);
-        HIP_TRY(c, hipMemcpy(c->d_ksk, buf.data(), buf.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(c->d_ksk.get(), buf.data(), buf.size() * 4, hipMemcpyHostToDevice));
     }
     return BCE_OK;
 }
@@ -489,57 +484,43 @@ int upload_secret(bce_ctx* c) {
     const size_t padded = ((size_t)c->n + 63) / 64 * 64;
     std::vector<int8_t> s8(padded, 0);
     for (u32 k = 0; k < c->n; ++k) s8[k] = (int8_t)c->s[k];
-    if (!c->d_s8) HIP_TRY(c, hipMalloc(&c->d_s8, padded));
+    if (!c->d_s8.get()) HIP_TRY(c, c->d_s8.alloc(padded));   // once: the pointer must not move (see above)
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(c->d_s8, s8.data(), padded, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_s8.get(), s8.data(), padded, hipMemcpyHostToDevice));
     return BCE_OK;
 }
 
 // report block + mismatch log of the device-side checks: one allocation per context, zeroed
 int ensure_check(bce_ctx* c) {
-    if (c->d_check) return BCE_OK;
+    if (c->d_check_mem.get()) return BCE_OK;
     const size_t bytes = sizeof(bce_check_report) + (size_t)kCheckLogCap * sizeof(bce_check_entry);
-    void* p = nullptr;
-    HIP_TRY(c, hipMalloc(&p, bytes));
-    if (hipMemset(p, 0, bytes) != hipSuccess) { hipFree(p); return c->fail(BCE_ERR_HIP, "hipMemset(check report) failed"); }
-    c->d_check = static_cast<bce_check_report*>(p);
-    c->d_check_log = reinterpret_cast<bce_check_entry*>(static_cast<char*>(p) + sizeof(bce_check_report));
+    DevBuf<char> mem;
+    HIP_TRY(c, mem.alloc(bytes));
+    if (hipMemset(mem.get(), 0, bytes) != hipSuccess) return c->fail(BCE_ERR_HIP, "hipMemset(check report) failed");
+    c->d_check_mem = std::move(mem);
     return BCE_OK;
 }
 
+// accumulators for `boots` bootstraps: at least doubled when they grow, after the work in flight
 int ensure_acc(bce_ctx* c, size_t boots) {
-    if (boots <= c->acc_cap) return BCE_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->d_acc) hipFree(c->d_acc);
-    c->d_acc = nullptr;
-    size_t cap = std::max(boots, c->acc_cap * 2);
-    HIP_TRY(c, hipMalloc(&c->d_acc, cap * 2 * c->N * c->wbytes));
-    c->acc_cap = cap;
+    const size_t need = boots * 2 * c->N * c->wbytes;
+    HIP_TRY(c, c->d_acc.grow(need, std::max(need, 2 * c->d_acc.capacity()), c->stream));
     return BCE_OK;
 }
 
-// stage a descriptor list into the next ring slot; returns device pointer
-int stage_descs(bce_ctx* c, const bce_gate_desc* d, size_t n, bce_gate_desc** dev, int* slot) {
-    int k = c->ring_pos;
-    c->ring_pos = (k + 1) % bce_ctx::kRing;
-    if (c->ring_busy[k]) {
-        HIP_TRY(c, hipEventSynchronize(c->ring_ev[k]));
-        c->ring_busy[k] = false;
-    }
-    if (n > c->desc_cap[k]) {
-        if (c->d_descs[k]) hipFree(c->d_descs[k]);
-        if (c->h_descs[k]) hipHostFree(c->h_descs[k]);
-        size_t cap = std::max(n, (size_t)1024);
-        HIP_TRY(c, hipMalloc(&c->d_descs[k], cap * sizeof(bce_gate_desc)));
-        HIP_TRY(c, hipHostMalloc(&c->h_descs[k], cap * sizeof(bce_gate_desc)));
-        c->desc_cap[k] = cap;
-    }
-    std::memcpy(c->h_descs[k], d, n * sizeof(bce_gate_desc));
-    HIP_TRY(c, hipMemcpyAsync(c->d_descs[k], c->h_descs[k], n * sizeof(bce_gate_desc), hipMemcpyHostToDevice, c->stream));
-    *dev = c->d_descs[k];
-    *slot = k;
+// Stage a descriptor list into the next ring slot (1,024 descriptors at least).  The caller launches the kernel that reads
+// descs_of(slot) and then marks the slot: its event must follow that kernel, not just the copy.
+int stage_descs(bce_ctx* c, const bce_gate_desc* d, size_t n, StagedUpload** slot) {
+    StagedUpload& r = c->ring[c->ring_pos];
+    c->ring_pos = (c->ring_pos + 1) % bce_ctx::kRing;
+    const size_t bytes = n * sizeof(bce_gate_desc);
+    HIP_TRY(c, r.reserve(bytes, std::max(n, (size_t)1024) * sizeof(bce_gate_desc), nullptr));
+    std::memcpy(r.host(), d, bytes);
+    HIP_TRY(c, r.copy(bytes, c->stream));
+    *slot = &r;
     return BCE_OK;
 }
+const bce_gate_desc* descs_of(const StagedUpload* slot) { return static_cast<const bce_gate_desc*>(slot->device()); }
 
 EventPair get_events(bce_ctx* c, int kind) {
     EventPair p;
@@ -565,7 +546,13 @@ void drain_timing(bce_ctx* c) {
     }
     c->pending.clear();
 }
-
+// after a launch: keeps the list of event pairs short
+int drain_if_long(bce_ctx* c) {
+    if (c->pending.size() <= 4096) return BCE_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    drain_timing(c);
+    return BCE_OK;
+}
 
 // uint64_t words of the ABI <-> words in device memory: u64 as they are (wide), u32 through a staging vector.  The
 // accumulators, key words and polynomials of a context are wide when c->is64; LWE words are always 32-bit.
@@ -601,26 +588,23 @@ int dev_ntt(bce_ctx* c, void* polys, u64 count, int inverse) {
 
 // device copies of what the key samplers read (keygen.hip): secrets, Gaussian CDF table, parameters
 struct KeygenDev {
-    int32_t *s = nullptr, *z = nullptr;
-    u64* cdf = nullptr;
-    void *ta = nullptr, *zq = nullptr;
-    ~KeygenDev() { hipFree(s); hipFree(z); hipFree(cdf); hipFree(ta); hipFree(zq); }
+    DevBuf<int32_t> s, z;
+    DevBuf<u64> cdf;
+    DevBuf<char> ta, zq;
 };
 
 int keygen_params(bce_ctx* c, const GaussSampler& gauss, KeygenDev& D, KeygenParams& kp) {
-    HIP_TRY(c, hipMalloc(&D.s, c->n * sizeof(int32_t)));
-    HIP_TRY(c, hipMalloc(&D.z, c->N * sizeof(int32_t)));
-    HIP_TRY(c, hipMalloc(&D.cdf, 81 * sizeof(u64)));
-    HIP_TRY(c, hipMemcpy(D.s, c->s.data(), c->n * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(D.z, c->z.data(), c->N * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(D.cdf, gauss.table(), 81 * sizeof(u64), hipMemcpyHostToDevice));
+    HIP_TRY(c, upload_vector(D.s, c->s));
+    HIP_TRY(c, upload_vector(D.z, c->z));
+    HIP_TRY(c, D.cdf.alloc(81));
+    HIP_TRY(c, hipMemcpy(D.cdf.get(), gauss.table(), 81 * sizeof(u64), hipMemcpyHostToDevice));
     std::memcpy(kp.seed, c->seed, 32);
     kp.n = c->n; kp.N = c->N; kp.Q = c->Q; kp.q = c->q; kp.qKS = c->qKS;
     kp.qbits = bit_length(c->Q - 1); kp.ksbits = bit_length(c->qKS - 1);
     kp.R = 2 * c->dG; kp.ap = c->method == BCE_AP ? 1 : 0; kp.baseR = c->baseR; kp.dR = c->dR;
     kp.baseKS = c->baseKS; kp.dKS = c->dKS; kp.ksk_stride = c->P.ksk_stride;
     { u64 v = 1; for (u32 i = 0; i < 4; ++i) { kp.gpow[i] = v; v = mul_mod(v, c->baseG, c->Q); } }
-    kp.s = D.s; kp.z = D.z; kp.cdf = D.cdf;
+    kp.s = D.s.get(); kp.z = D.z.get(); kp.cdf = D.cdf.get();
     return BCE_OK;
 }
 
@@ -636,24 +620,24 @@ int keygen_bsk(bce_ctx* c, const KeygenParams& kp, KeygenDev& D) {
     const size_t wb = c->wbytes;
     const u64 rows = rgsw_rows_total(c);
     const u64 chunk = std::max<u64>(R, std::min<u64>(rows, ((u64)1 << 30) / ((u64)N * wb)) / R * R);
-    HIP_TRY(c, hipMalloc(&D.ta, chunk * N * wb));
-    HIP_TRY(c, hipMalloc(&D.zq, N * wb));
+    HIP_TRY(c, D.ta.alloc(chunk * N * wb));
+    HIP_TRY(c, D.zq.alloc(N * wb));
     {
         std::vector<u64> zq(N);
         for (u32 k = 0; k < N; ++k) zq[k] = lift_signed(c->z[k], Q);
-        if (const int rc = words_to_device(c, D.zq, zq.data(), N, c->is64)) return rc;
+        if (const int rc = words_to_device(c, D.zq.get(), zq.data(), N, c->is64)) return rc;
     }
-    int rc = dev_ntt(c, D.zq, 1, 0);
+    int rc = dev_ntt(c, D.zq.get(), 1, 0);
     if (rc) return rc;
-    char* dev = static_cast<char*>(c->d_bsk);
+    char* dev = c->d_bsk.get();
     for (u64 r0 = 0; r0 < rows; r0 += chunk) {
         const u64 cnt = std::min(chunk, rows - r0);
         char* dst = dev + r0 * 2 * N * wb;
-        HIP_TRY(c, launch_gen_bsk_rows(kp, r0, (u32)cnt, dst, D.ta, c->is64 ? 1 : 0, c->stream));
+        HIP_TRY(c, launch_gen_bsk_rows(kp, r0, (u32)cnt, dst, D.ta.get(), c->is64 ? 1 : 0, c->stream));
         if ((rc = dev_ntt(c, dst, cnt * 2, 0))) return rc;
-        if ((rc = dev_ntt(c, D.ta, cnt, 0))) return rc;
+        if ((rc = dev_ntt(c, D.ta.get(), cnt, 0))) return rc;
         // b-column (odd polys) += NTT(a) * NTT(z)
-        HIP_TRY(c, launch_pointwise_mac(c->P, dst + N * wb, D.ta, D.zq, (u32)cnt, 2, c->stream));
+        HIP_TRY(c, launch_pointwise_mac(c->P, dst + N * wb, D.ta.get(), D.zq.get(), (u32)cnt, 2, c->stream));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return BCE_OK;
@@ -663,7 +647,7 @@ int keygen_bsk(bce_ctx* c, const KeygenParams& kp, KeygenDev& D) {
 int check_dag_runs(bce_ctx* c) {
     int rc = BCE_OK;
     for (int i = 0; i < c->dag_pending; ++i) {
-        const bce_ctx::DagStatus& st = c->h_dag_status[i];
+        const bce_ctx::DagStatus& st = c->h_dag_status.get()[i];
         c->dag_last[0] = st.done; c->dag_last[1] = st.lazy_waits; c->dag_last[2] = st.abort; c->dag_last[3] = (u64)c->dag_wps_used[i] / 2;
         c->dag_last[4] = st.busy_ticks; c->dag_last[5] = st.wait_ticks; c->dag_last[6] = st.gate_ticks;
         if (st.abort != 0 || st.done != c->dag_expected[i])
@@ -724,17 +708,10 @@ int launch_bootstraps(bce_ctx* c, const bce_gate_desc* dd, u32 n, u32 instances,
             le1 = LaunchEvents{e1.a, e1.b};
         }
         if (!d_partial) {
-            const size_t need = tail_partial_words(c->P, (u32)nb);
-            if (need > c->tail_cap) {
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                if (c->d_tail_partial) hipFree(c->d_tail_partial);
-                c->d_tail_partial = nullptr;
-                const size_t cap = std::max(need, c->tail_cap * 2);
-                HIP_TRY(c, hipMalloc(&c->d_tail_partial, cap * sizeof(u64)));
-                c->tail_cap = cap;
-            }
+            const size_t need = tail_partial_words(c->P, (u32)nb);   // grows like the accumulators (ensure_acc)
+            HIP_TRY(c, c->d_tail_partial.grow(need, std::max(need, 2 * c->d_tail_partial.capacity()), c->stream));
         }
-        const hipError_t e = launch_tail(c->P, dd, n, instances, slot_stride, d_acc, d_partial ? d_partial : c->d_tail_partial, d_lweN, d_ks, c->stream, le1, pairs);
+        const hipError_t e = launch_tail(c->P, dd, n, instances, slot_stride, d_acc, d_partial ? d_partial : c->d_tail_partial.get(), d_lweN, d_ks, c->stream, le1, pairs);
         if (e != hipSuccess) {
             if (events) c->free_events.push_back(e1);
             HIP_TRY(c, e);
@@ -777,24 +754,22 @@ int eval_impl(bce_ctx* c, u32 n_desc, const bce_gate_desc* descs, u32 instances,
         const size_t nb = boot.size() * (size_t)instances;
         int rc = ensure_acc(c, nb);
         if (rc) return rc;
-        bce_gate_desc* dd = nullptr;
-        int slot = 0;
-        rc = stage_descs(c, boot.data(), boot.size(), &dd, &slot);
+        StagedUpload* slot = nullptr;
+        rc = stage_descs(c, boot.data(), boot.size(), &slot);
         if (rc) return rc;
-        u32 *d_lweN = nullptr, *d_ks = nullptr;
+        DevBuf<u32> d_lweN, d_ks;
         // staged outputs of a launch with pairs: the kernels write the second outputs to a second block of nb rows
         const size_t dbg_rows = n_pairs ? 2 * nb : nb;
-        if (dbg_lweN) HIP_TRY(c, hipMalloc(&d_lweN, dbg_rows * (c->N + 1) * sizeof(u32)));
-        if (dbg_ks) HIP_TRY(c, hipMalloc(&d_ks, dbg_rows * (c->n + 1) * sizeof(u32)));
-        rc = launch_bootstraps(c, dd, (u32)boot.size(), instances, slot_stride, c->d_acc, d_lweN, d_ks, true, nullptr, n_pairs != 0);
+        if (dbg_lweN) HIP_TRY(c, d_lweN.alloc(dbg_rows * (c->N + 1)));
+        if (dbg_ks) HIP_TRY(c, d_ks.alloc(dbg_rows * (c->n + 1)));
+        rc = launch_bootstraps(c, descs_of(slot), (u32)boot.size(), instances, slot_stride, c->d_acc.get(), d_lweN.get(), d_ks.get(), true, nullptr, n_pairs != 0);
         if (rc) return rc;
-        hipEventRecord(c->ring_ev[slot], c->stream);
-        c->ring_busy[slot] = true;
+        slot->mark(c->stream);
         if (dbg_acc || dbg_lweN || dbg_ks) {
             HIP_TRY(c, hipStreamSynchronize(c->stream));
-            if (dbg_acc && (rc = words_from_device(c, dbg_acc, c->d_acc, nb * 2 * c->N, c->is64))) return rc;
-            if (dbg_lweN && (rc = words_from_device(c, dbg_lweN, d_lweN, nb * (c->N + 1), false))) return rc;
-            if (dbg_ks && (rc = words_from_device(c, dbg_ks, d_ks, nb * (c->n + 1), false))) return rc;
+            if (dbg_acc && (rc = words_from_device(c, dbg_acc, c->d_acc.get(), nb * 2 * c->N, c->is64))) return rc;
+            if (dbg_lweN && (rc = words_from_device(c, dbg_lweN, d_lweN.get(), nb * (c->N + 1), false))) return rc;
+            if (dbg_ks && (rc = words_from_device(c, dbg_ks, d_ks.get(), nb * (c->n + 1), false))) return rc;
             // ... which the caller gets packed, in descriptor order, from row nb on (bce_debug_eval_stages: one instance)
             if (n_pairs) {
                 auto pack = [&](u64* dst, const u32* dev, size_t w) {   // the second block in one copy, then packed on the host
@@ -804,26 +779,19 @@ int eval_impl(bce_ctx* c, u32 n_desc, const bce_gate_desc* descs, u32 instances,
                         if (pair_kind(boot[i].op) > 0) std::copy_n(second.data() + i * w, w, dst + row++ * w);
                     return e;
                 };
-                if (dbg_lweN) rc = pack(dbg_lweN, d_lweN, c->N + 1);
-                if (dbg_ks && !rc) rc = pack(dbg_ks, d_ks, c->n + 1);
+                if (dbg_lweN) rc = pack(dbg_lweN, d_lweN.get(), c->N + 1);
+                if (dbg_ks && !rc) rc = pack(dbg_ks, d_ks.get(), c->n + 1);
             }
-            if (d_lweN) hipFree(d_lweN);
-            if (d_ks) hipFree(d_ks);
             if (rc) return rc;
         }
-        if (c->pending.size() > 4096) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            drain_timing(c);
-        }
+        if (const int rc2 = drain_if_long(c)) return rc2;
     }
     if (!unary.empty()) {
-        bce_gate_desc* dd = nullptr;
-        int slot = 0;
-        int rc = stage_descs(c, unary.data(), unary.size(), &dd, &slot);
+        StagedUpload* slot = nullptr;
+        int rc = stage_descs(c, unary.data(), unary.size(), &slot);
         if (rc) return rc;
-        HIP_TRY(c, launch_lwe_unary(c->P, dd, (u32)unary.size(), instances, slot_stride, c->stream));
-        hipEventRecord(c->ring_ev[slot], c->stream);
-        c->ring_busy[slot] = true;
+        HIP_TRY(c, launch_lwe_unary(c->P, descs_of(slot), (u32)unary.size(), instances, slot_stride, c->stream));
+        slot->mark(c->stream);
     }
     return BCE_OK;
 }
@@ -842,36 +810,6 @@ int bce_ctx_create(int paramset, int method, int device, bce_ctx** out) {
 int bce_ctx_create_custom(uint32_t n, uint32_t N, uint64_t q, uint64_t Q, uint64_t qKS, uint32_t baseKS, uint32_t baseG,
                           uint32_t baseR, int method, int device, bce_ctx** out) {
     return build_ctx(n, N, q, Q, qKS, baseKS, baseG, baseR, method, device, out);
-}
-
-static void plan_free(bce_plan* p);
-static void dag_free(bce_dag* g);
-
-void bce_ctx_destroy(bce_ctx* c) {
-    if (!c) return;
-    hipSetDevice(c->device);
-    if (c->stream) hipStreamSynchronize(c->stream);
-    if (c->rccl_comm) bce_rccl_shutdown(c);
-    drain_timing(c);
-    {   // schedules nobody destroyed: theirs callers' handles die with the context
-        std::unordered_set<bce_plan*> plans;
-        std::unordered_set<bce_dag*> dags;
-        { std::lock_guard<std::mutex> lk(g_live_mu); plans.swap(c->plans); dags.swap(c->dags); g_live.erase(c); }
-        for (bce_plan* p : plans) plan_free(p);
-        for (bce_dag* g : dags) dag_free(g);
-    }
-    for (auto& p : c->free_events) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
-    for (int i = 0; i < bce_ctx::kRing; ++i) {
-        if (c->d_descs[i]) hipFree(c->d_descs[i]);
-        if (c->h_descs[i]) hipHostFree(c->h_descs[i]);
-        if (c->ring_ev[i]) hipEventDestroy(c->ring_ev[i]);
-    }
-    hipFree(c->d_io); if (c->h_io) hipHostFree(c->h_io);
-    hipFree(c->d_s8); hipFree(c->d_check); hipFree(c->d_chk_stage); if (c->h_chk_stage) hipHostFree(c->h_chk_stage); if (c->chk_ev) hipEventDestroy(c->chk_ev);
-    hipFree(c->d_P); if (c->h_dag_status) hipHostFree(c->h_dag_status); if (c->h_dag_stage) hipHostFree(c->h_dag_stage);
-    hipFree(c->d_twf); hipFree(c->d_fwd_mfma); hipFree(c->d_psi); hipFree(c->d_psi_r2); hipFree(c->d_xcd_gate); hipFree(c->d_tw64); hipFree(c->d_tw64d); hipFree(c->d_bsk); hipFree(c->d_ksk); hipFree(c->d_pool); hipFree(c->d_acc); hipFree(c->d_tail_partial);
-    if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
 }
 
 hipStream_t bce_internal_stream(bce_ctx* c) { return c->stream; }
@@ -924,8 +862,8 @@ int bce_keygen(bce_ctx* c, const uint8_t seed_in[32]) {
     // the padded row layout the tail kernel gathers from
     {
         const u64 rows = (u64)N * c->baseKS * c->dKS;
-        HIP_TRY(c, hipMemsetAsync(c->d_ksk, 0, rows * c->P.ksk_stride * (c->P.ksk_u16 ? 2 : 4), c->stream));
-        HIP_TRY(c, launch_gen_ksk_rows(kp, rows, c->d_ksk, c->P.ksk_u16 ? 1 : 0, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_ksk.get(), 0, rows * c->P.ksk_stride * (c->P.ksk_u16 ? 2 : 4), c->stream));
+        HIP_TRY(c, launch_gen_ksk_rows(kp, rows, c->d_ksk.get(), c->P.ksk_u16 ? 1 : 0, c->stream));
     }
     rc = keygen_bsk(c, kp, D);
     if (!rc) rc = bsk_words_to_kernel_layout(c);
@@ -966,9 +904,9 @@ static int import_keys_impl(bce_ctx* c, const int32_t* s, const int32_t* z, cons
             const u64 cnt = std::min(chunk, bsk_words - o);
             for (u64 i = 0; i < cnt; ++i)
                 if (bsk[o + i] >= c->Q) return c->fail(BCE_ERR_ARG, "bsk word %llu not reduced mod Q", (unsigned long long)(o + i));
-            if ((rc = words_to_device(c, static_cast<char*>(c->d_bsk) + o * c->wbytes, bsk + o, cnt, c->is64))) return rc;
+            if ((rc = words_to_device(c, c->d_bsk.get() + o * c->wbytes, bsk + o, cnt, c->is64))) return rc;
         }
-        if (!evaluation_form && (rc = dev_ntt(c, c->d_bsk, bsk_words / c->N, 0))) return rc;
+        if (!evaluation_form && (rc = dev_ntt(c, c->d_bsk.get(), bsk_words / c->N, 0))) return rc;
         if ((rc = bsk_words_to_kernel_layout(c))) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
@@ -995,12 +933,12 @@ static int export_bsk_impl(bce_ctx* c, uint64_t* bsk, bool evaluation_form) {
     const u64 words = bce_bsk_words(c);
     const u64 per_rgsw = 4ull * c->dG;  // polynomials of one RGSW ciphertext: chunks hold whole ciphertexts (un-folding works per ciphertext)
     const u64 chunk_polys = std::max<u64>(1, ((u64)256 << 20) / ((u64)c->N * c->wbytes) / per_rgsw) * per_rgsw;
-    void* d_tmp = nullptr;
-    HIP_TRY(c, hipMalloc(&d_tmp, chunk_polys * c->N * c->wbytes));
-    struct Free { void* p; ~Free() { hipFree(p); } } free_tmp{d_tmp};  // released on every return path
+    DevBuf<char> tmp;
+    HIP_TRY(c, tmp.alloc(chunk_polys * c->N * c->wbytes));
+    void* const d_tmp = tmp.get();
     for (u64 p0 = 0; p0 < words / c->N; p0 += chunk_polys) {
         const u64 cnt = std::min(chunk_polys, words / c->N - p0), w = cnt * c->N;
-        const char* src = static_cast<const char*>(c->d_bsk) + p0 * c->N * c->wbytes;
+        const char* src = c->d_bsk.get() + p0 * c->N * c->wbytes;
         HIP_TRY(c, hipMemcpyAsync(d_tmp, src, w * c->wbytes, hipMemcpyDeviceToDevice, c->stream));
         if (c->P.fp64) HIP_TRY(c, launch_words_u64_f64(static_cast<u64*>(d_tmp), w, 0, c->stream));  // doubles -> u64 words
         if (c->P.fold) HIP_TRY(c, launch_fold_gadget(c->P, d_tmp, cnt / (4ull * c->dG), -1, c->stream));   // rows l >= 1 += B^l row 0
@@ -1020,12 +958,12 @@ int bce_export_ksk(bce_ctx* c, uint32_t* ksk) {
     const size_t rows = (size_t)c->N * c->baseKS * c->dKS, W = c->n + 1, S = c->P.ksk_stride;
     if (c->P.ksk_u16) {
         std::vector<uint16_t> buf(rows * S);
-        HIP_TRY(c, hipMemcpy(buf.data(), c->d_ksk, buf.size() * 2, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(buf.data(), c->d_ksk.get(), buf.size() * 2, hipMemcpyDeviceToHost));
         for (size_t r = 0; r < rows; ++r)
             for (size_t k = 0; k < W; ++k) ksk[r * W + k] = buf[r * S + k];
     } else {
         std::vector<u32> buf(rows * S);
-        HIP_TRY(c, hipMemcpy(buf.data(), c->d_ksk, buf.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(buf.data(), c->d_ksk.get(), buf.size() * 4, hipMemcpyDeviceToHost));
         for (size_t r = 0; r < rows; ++r) std::memcpy(&ksk[r * W], &buf[r * S], W * 4);
     }
     return BCE_OK;
@@ -1036,16 +974,14 @@ int bce_pool_reserve(bce_ctx* c, uint32_t slots) {
     if (slots <= c->pool_slots) return BCE_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    u32* np = nullptr;
-    HIP_TRY(c, hipMalloc(&np, (size_t)slots * c->P.pool_stride * 4));
-    HIP_TRY(c, hipMemset(np, 0, (size_t)slots * c->P.pool_stride * 4));
-    if (c->d_pool) {
-        HIP_TRY(c, hipMemcpy(np, c->d_pool, (size_t)c->pool_slots * c->P.pool_stride * 4, hipMemcpyDeviceToDevice));
-        hipFree(c->d_pool);
-    }
-    c->d_pool = np;
+    DevBuf<u32> np;
+    HIP_TRY(c, np.alloc((size_t)slots * c->P.pool_stride));
+    HIP_TRY(c, hipMemset(np.get(), 0, (size_t)slots * c->P.pool_stride * 4));
+    if (c->d_pool.get()) HIP_TRY(c, hipMemcpy(np.get(), c->d_pool.get(), (size_t)c->pool_slots * c->P.pool_stride * 4, hipMemcpyDeviceToDevice));
+    // published only now, zeroed and holding the old contents: a failure above left the old pool in place
+    c->d_pool = std::move(np);
     c->pool_slots = slots;
-    c->P.pool = np;
+    c->P.pool = c->d_pool.get();
     return BCE_OK;
 }
 
@@ -1069,7 +1005,7 @@ int bce_lwe_write(bce_ctx* c, const uint32_t* slots, uint32_t count, const uint6
             if (v >= c->q) return c->fail(BCE_ERR_ARG, "ciphertext word not reduced mod q");
             buf[k] = (u32)v;
         }
-        HIP_TRY(c, hipMemcpy(c->d_pool + (size_t)slots[i] * c->P.pool_stride, buf.data(), buf.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(c->d_pool.get() + (size_t)slots[i] * c->P.pool_stride, buf.data(), buf.size() * 4, hipMemcpyHostToDevice));
         i += run;
     }
     return BCE_OK;
@@ -1091,25 +1027,19 @@ int bce_lwe_read(bce_ctx* c, const uint32_t* slots, uint32_t count, uint64_t* ct
     std::vector<u32> buf;
     if ((u64)(hi - lo + 1) <= 4ull * count + 64) {
         buf.resize((size_t)(hi - lo + 1) * W);
-        HIP_TRY(c, hipMemcpy(buf.data(), c->d_pool + (size_t)lo * W, buf.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(buf.data(), c->d_pool.get() + (size_t)lo * W, buf.size() * 4, hipMemcpyDeviceToHost));
         for (u32 i = 0; i < count; ++i)
             for (size_t k = 0; k < W; ++k) cts[i * W + k] = buf[(size_t)(slots[i] - lo) * W + k];
     } else {
         // scattered slots (the outputs of K instances sit one pool stride apart): gather on the device, one copy
         const size_t words = (size_t)count * W;
-        if (words > c->io_cap) {
-            if (c->d_io) hipFree(c->d_io);
-            if (c->h_io) hipHostFree(c->h_io);
-            c->d_io = nullptr; c->h_io = nullptr; c->io_cap = 0;
-            const size_t cap = std::max(words, (size_t)64 * W);
-            HIP_TRY(c, hipMalloc(&c->d_io, cap * sizeof(u32)));
-            HIP_TRY(c, hipHostMalloc(&c->h_io, cap * sizeof(u32)));
-            c->io_cap = cap;
-        }
-        { const int rc = pool_pack(c, slots, count, c->d_io, 0); if (rc) return rc; }
-        HIP_TRY(c, hipMemcpyAsync(c->h_io, c->d_io, words * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+        const size_t cap = std::max(words, (size_t)64 * W);   // (the stream was synchronised above)
+        HIP_TRY(c, c->d_io.grow(words, cap, nullptr));
+        HIP_TRY(c, c->h_io.grow(words, cap, nullptr));
+        { const int rc = pool_pack(c, slots, count, c->d_io.get(), 0); if (rc) return rc; }
+        HIP_TRY(c, hipMemcpyAsync(c->h_io.get(), c->d_io.get(), words * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (size_t k = 0; k < words; ++k) cts[k] = c->h_io[k];
+        for (size_t k = 0; k < words; ++k) cts[k] = c->h_io.get()[k];
     }
     return BCE_OK;
 }
@@ -1221,11 +1151,12 @@ struct bce_plan {
     u32 instances = 0, slot_stride = 0, slot_base = 0;
     u32 max_step = 0;                          // descriptors of the largest step
     u64 boots_per_run = 0;
-    bce_gate_desc* d_descs = nullptr;          // all steps, resident
+    DevBuf<bce_gate_desc> d_descs;             // all steps, resident
     // captured form (bce_plan_run): its own accumulator / partial-sum scratch, so that nothing the graph points to is ever
-    // re-allocated by other calls on the context
-    void* d_acc = nullptr;
-    u64* d_partial = nullptr;
+    // re-allocated by other calls on the context.  d_descs, d_acc, d_partial, d_chk_slots and `expect` never move while
+    // `exec` exists: each is allocated once, the check lists only after bce_plan_set_checks dropped the capture.
+    DevBuf<char> d_acc;
+    DevBuf<u64> d_partial;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     u64 fused_launches = 0;
@@ -1233,15 +1164,21 @@ struct bce_plan {
     const void* cap_ptrs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     u32 cap_flags[3] = {0, 0, 0};
     // device-side checks (bce_plan_set_checks): step s checks the slots [chk_off[s], chk_off[s] + chk_cnt[s]) of d_chk_slots
-    // against the same range of every instance's row of d_expect ([instances][chk_total], one fixed buffer: the captured
-    // graph points into it; bce_plan_set_expected refills it through the pinned h_expect)
+    // against the same range of every instance's row of `expect` ([instances][chk_total], one fixed buffer: the captured
+    // graph points into it; bce_plan_set_expected refills it through its pinned half)
     std::vector<u32> chk_off, chk_cnt;
     u32 chk_total = 0;
     int chk_repair = 0;
-    bool expected_set = false, expect_busy = false;
-    u32* d_chk_slots = nullptr;
-    uint8_t *d_expect = nullptr, *h_expect = nullptr;
-    hipEvent_t expect_ev = nullptr;
+    bool expected_set = false;
+    DevBuf<u32> d_chk_slots;
+    StagedUpload expect;
+    const uint8_t* d_expect() const { return static_cast<const uint8_t*>(expect.device()); }
+
+    void drop_capture() {
+        if (exec) { hipGraphExecDestroy(exec); exec = nullptr; }
+        if (graph) { hipGraphDestroy(graph); graph = nullptr; }
+    }
+    ~bce_plan() { drop_capture(); }   // the graph goes before the buffers it points to
 };
 
 namespace {
@@ -1250,23 +1187,29 @@ bool plan_capture_is_current(const bce_ctx* c, const bce_plan* p) {
     const u32 flags[3] = {c->P.variant, c->P.fuse_tail, c->P.fold};
     return std::memcmp(now, p->cap_ptrs, sizeof now) == 0 && std::memcmp(flags, p->cap_flags, sizeof flags) == 0;
 }
-void plan_drop_capture(bce_plan* p) {
-    if (p->exec) { hipGraphExecDestroy(p->exec); p->exec = nullptr; }
-    if (p->graph) { hipGraphDestroy(p->graph); p->graph = nullptr; }
-}
 void plan_free_checks(bce_plan* p) {
-    hipFree(p->d_chk_slots); hipFree(p->d_expect);
-    if (p->h_expect) hipHostFree(p->h_expect);
-    if (p->expect_ev) hipEventDestroy(p->expect_ev);
-    p->d_chk_slots = nullptr; p->d_expect = nullptr; p->h_expect = nullptr; p->expect_ev = nullptr;
+    p->d_chk_slots.reset();
+    p->expect.reset();
     p->chk_off.clear(); p->chk_cnt.clear();
-    p->chk_total = 0; p->expected_set = p->expect_busy = false;
+    p->chk_total = 0; p->expected_set = false;
 }
 // the checks of plan step s, after its kernels (no allocation, no synchronisation: also runs under stream capture)
 int plan_check_step(bce_ctx* c, const bce_plan* p, size_t s) {
     if (!p->chk_total || !p->chk_cnt[s]) return BCE_OK;
-    HIP_TRY(c, launch_lwe_check(c->P, c->d_s8, p->d_chk_slots + p->chk_off[s], p->d_expect + p->chk_off[s], p->chk_cnt[s], p->chk_total,
-                                p->instances, p->slot_stride, p->chk_repair, (u32)s, c->d_check, c->d_check_log, c->stream));
+    HIP_TRY(c, launch_lwe_check(c->P, c->d_s8.get(), p->d_chk_slots.get() + p->chk_off[s], p->d_expect() + p->chk_off[s], p->chk_cnt[s], p->chk_total,
+                                p->instances, p->slot_stride, p->chk_repair, (u32)s, c->d_check(), c->d_check_log(), c->stream));
+    return BCE_OK;
+}
+// the expected bits of a check list are messages; `who` names the call in the message
+int expected_are_messages(bce_ctx* c, const char* who, const uint8_t* expect, size_t count) {
+    for (size_t i = 0; i < count; ++i)
+        if (expect[i] > 3) return c->fail(BCE_ERR_ARG, "%s: expect[%zu] = %u is not a message (0..3)", who, i, expect[i]);
+    return BCE_OK;
+}
+// every checked slot, at every instance (span = the distance of the last instance's copy), lies in the pool
+int checked_slots_in_pool(bce_ctx* c, const char* who, const uint32_t* slots, u64 count, u64 span) {
+    for (u64 i = 0; i < count; ++i)
+        if (slots[i] + span >= c->pool_slots) return c->fail(BCE_ERR_POOL, "%s: check %llu: slot %llu outside the pool (%u slots)", who, (unsigned long long)i, (unsigned long long)(slots[i] + span), c->pool_slots);
     return BCE_OK;
 }
 int plan_checks_ready(bce_ctx* c, const bce_plan* p, const char* who) {
@@ -1277,13 +1220,6 @@ int plan_checks_ready(bce_ctx* c, const bce_plan* p, const char* who) {
 
 extern "C" {
 
-static void plan_free(bce_plan* p) {
-    plan_drop_capture(p);
-    plan_free_checks(p);
-    hipFree(p->d_descs); hipFree(p->d_acc); hipFree(p->d_partial);
-    delete p;
-}
-
 void bce_plan_destroy(bce_ctx* c, bce_plan* p) {
     if (!p || !c) return;
     {   // a context that no longer exists took its plans along (bce_ctx_destroy): nothing left to free, nothing to touch
@@ -1292,7 +1228,7 @@ void bce_plan_destroy(bce_ctx* c, bce_plan* p) {
     }
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
-    plan_free(p);
+    delete p;
 }
 
 int bce_plan_create(bce_ctx* c, uint32_t n_steps, const uint32_t* step_sizes, const bce_gate_desc* descs, uint32_t instances,
@@ -1333,8 +1269,7 @@ int bce_plan_create(bce_ctx* c, uint32_t n_steps, const uint32_t* step_sizes, co
         g.in0 += slot_base; g.in1 += slot_base; g.out += slot_base;
     }
     p->boots_per_run = total * instances;
-    HIP_TRY(c, hipMalloc(&p->d_descs, total * sizeof(bce_gate_desc)));
-    HIP_TRY(c, hipMemcpy(p->d_descs, d.data(), total * sizeof(bce_gate_desc), hipMemcpyHostToDevice));
+    HIP_TRY(c, upload_vector(p->d_descs, d));
     *out = p.release();
     return BCE_OK;
 }
@@ -1347,14 +1282,10 @@ int bce_plan_run_step(bce_ctx* c, bce_plan* p, uint32_t step) {
     HIP_TRY(c, hipSetDevice(c->device));
     const int rc = ensure_acc(c, (size_t)p->cnt[step] * p->instances);
     if (rc) return rc;
-    const int rc2 = launch_bootstraps(c, p->d_descs + p->off[step], p->cnt[step], p->instances, p->slot_stride, c->d_acc, nullptr, nullptr, true, nullptr, p->pairs[step] != 0);
+    const int rc2 = launch_bootstraps(c, p->d_descs.get() + p->off[step], p->cnt[step], p->instances, p->slot_stride, c->d_acc.get(), nullptr, nullptr, true, nullptr, p->pairs[step] != 0);
     if (rc2) return rc2;
     if (const int rc3 = plan_check_step(c, p, step)) return rc3;
-    if (c->pending.size() > 4096) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        drain_timing(c);
-    }
-    return BCE_OK;
+    return drain_if_long(c);
 }
 
 int bce_plan_run(bce_ctx* c, bce_plan* p) {
@@ -1365,13 +1296,13 @@ int bce_plan_run(bce_ctx* c, bce_plan* p) {
     if (p->exec && !plan_capture_is_current(c, p)) {
         // the pool grew (bce_pool_reserve) or keys were re-imported since the capture: the graph's kernel arguments are stale
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        plan_drop_capture(p);
+        p->drop_capture();
     }
     if (!p->exec) {
         // scratch of the captured launches, sized for the largest step
         const size_t nb = (size_t)p->max_step * p->instances;
-        if (!p->d_acc) HIP_TRY(c, hipMalloc(&p->d_acc, nb * 2 * c->N * c->wbytes));
-        if (!p->d_partial) HIP_TRY(c, hipMalloc(&p->d_partial, std::max<size_t>(1, tail_partial_words(c->P, (u32)nb)) * sizeof(u64)));
+        if (!p->d_acc.get()) HIP_TRY(c, p->d_acc.alloc(nb * 2 * c->N * c->wbytes));
+        if (!p->d_partial.get()) HIP_TRY(c, p->d_partial.alloc(std::max<size_t>(1, tail_partial_words(c->P, (u32)nb))));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         // relaxed mode: the launchers set kernel attributes (dynamic LDS size) while the stream is capturing
         HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
@@ -1379,7 +1310,7 @@ int bce_plan_run(bce_ctx* c, bce_plan* p) {
         u64 fused = 0;
         for (size_t s = 0; s < p->cnt.size() && rc == BCE_OK; ++s) {
             bool f = false;
-            rc = launch_bootstraps(c, p->d_descs + p->off[s], p->cnt[s], p->instances, p->slot_stride, p->d_acc, nullptr, nullptr, false, &f, p->pairs[s] != 0, p->d_partial);
+            rc = launch_bootstraps(c, p->d_descs.get() + p->off[s], p->cnt[s], p->instances, p->slot_stride, p->d_acc.get(), nullptr, nullptr, false, &f, p->pairs[s] != 0, p->d_partial.get());
             fused += f ? 1 : 0;
             if (rc == BCE_OK) rc = plan_check_step(c, p, s);
         }
@@ -1404,11 +1335,7 @@ int bce_plan_run(bce_ctx* c, bce_plan* p) {
     c->timing.blind_rotate_launches += p->cnt.size();
     c->timing.bootstraps += p->boots_per_run;
     c->timing.fused_tail_launches += p->fused_launches;
-    if (c->pending.size() > 4096) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        drain_timing(c);
-    }
-    return BCE_OK;
+    return drain_if_long(c);
 }
 
 // ---- verify mode on the device (include/bce_gpu.h, "verify mode on the device") -----------------------------------
@@ -1420,32 +1347,19 @@ int bce_check_slots(bce_ctx* c, uint32_t count, const uint32_t* slots, const uin
     if (count == 0 || instances == 0) return BCE_OK;
     const u64 items = (u64)count * instances;
     if (items > (1ull << 31)) return c->fail(BCE_ERR_ARG, "bce_check_slots: too many checks");
-    const u64 span = (u64)(instances - 1) * slot_stride;
-    for (u32 i = 0; i < count; ++i)
-        if (slots[i] + span >= c->pool_slots) return c->fail(BCE_ERR_POOL, "bce_check_slots: check %u: slot %llu outside the pool (%u slots)", i, (unsigned long long)(slots[i] + span), c->pool_slots);
-    for (u64 i = 0; i < items; ++i)
-        if (expect[i] > 3) return c->fail(BCE_ERR_ARG, "bce_check_slots: expect[%llu] = %u is not a message (0..3)", (unsigned long long)i, expect[i]);
+    if (const int rc = checked_slots_in_pool(c, "bce_check_slots", slots, count, (u64)(instances - 1) * slot_stride)) return rc;
+    if (const int rc = expected_are_messages(c, "bce_check_slots", expect, items)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = ensure_check(c)) return rc;
     const size_t slot_bytes = (size_t)count * sizeof(u32), bytes = slot_bytes + items;
-    if (c->chk_busy) { HIP_TRY(c, hipEventSynchronize(c->chk_ev)); c->chk_busy = false; }   // the last upload has left the pinned buffer
-    if (bytes > c->chk_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        hipFree(c->d_chk_stage); if (c->h_chk_stage) hipHostFree(c->h_chk_stage);
-        c->d_chk_stage = c->h_chk_stage = nullptr; c->chk_cap = 0;
-        const size_t cap = std::max(bytes, (size_t)1 << 16);
-        HIP_TRY(c, hipMalloc(&c->d_chk_stage, cap));
-        HIP_TRY(c, hipHostMalloc(&c->h_chk_stage, cap));
-        c->chk_cap = cap;
-    }
-    if (!c->chk_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->chk_ev, hipEventDisableTiming));
-    std::memcpy(c->h_chk_stage, slots, slot_bytes);
-    std::memcpy(c->h_chk_stage + slot_bytes, expect, items);
-    HIP_TRY(c, hipMemcpyAsync(c->d_chk_stage, c->h_chk_stage, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipEventRecord(c->chk_ev, c->stream));
-    c->chk_busy = true;
-    HIP_TRY(c, launch_lwe_check(c->P, c->d_s8, reinterpret_cast<const u32*>(c->d_chk_stage), reinterpret_cast<const uint8_t*>(c->d_chk_stage + slot_bytes),
-                                count, count, instances, slot_stride, repair, tag, c->d_check, c->d_check_log, c->stream));
+    StagedUpload& st = c->chk_stage;   // slot list, then expected bits: 64 KiB at least, grown after the work in flight
+    HIP_TRY(c, st.reserve(bytes, std::max(bytes, (size_t)1 << 16), c->stream));
+    std::memcpy(st.host(), slots, slot_bytes);
+    std::memcpy(static_cast<char*>(st.host()) + slot_bytes, expect, items);
+    HIP_TRY(c, st.send(bytes, c->stream));
+    const char* dev = static_cast<const char*>(st.device());
+    HIP_TRY(c, launch_lwe_check(c->P, c->d_s8.get(), reinterpret_cast<const u32*>(dev), reinterpret_cast<const uint8_t*>(dev + slot_bytes),
+                                count, count, instances, slot_stride, repair, tag, c->d_check(), c->d_check_log(), c->stream));
     return BCE_OK;
 }
 
@@ -1458,24 +1372,19 @@ int bce_plan_set_checks(bce_ctx* c, bce_plan* p, const uint32_t* check_sizes, co
     if (total && !slots) return c->fail(BCE_ERR_ARG, "bce_plan_set_checks: null slot list");
     if (total * p->instances > (1ull << 31)) return c->fail(BCE_ERR_ARG, "bce_plan_set_checks: too many checks");
     const u64 span = (u64)p->slot_base + (u64)(p->instances - 1) * p->slot_stride;   // the span rule of bce_plan_create
+    if (const int rc = checked_slots_in_pool(c, "bce_plan_set_checks", slots, total, span)) return rc;
     std::vector<u32> shifted(total);
-    for (u64 i = 0; i < total; ++i) {
-        if (slots[i] + span >= c->pool_slots) return c->fail(BCE_ERR_POOL, "bce_plan_set_checks: check %llu: slot %llu outside the pool (%u slots)", (unsigned long long)i, (unsigned long long)(slots[i] + span), c->pool_slots);
-        shifted[i] = slots[i] + p->slot_base;
-    }
+    for (u64 i = 0; i < total; ++i) shifted[i] = slots[i] + p->slot_base;
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    plan_drop_capture(p);   // its launches would miss (or still hold) the old lists: captured again at the next bce_plan_run
+    p->drop_capture();   // its launches would miss (or still hold) the old lists: captured again at the next bce_plan_run
     plan_free_checks(p);
     if (total == 0) return BCE_OK;
     if (const int rc = ensure_check(c)) return rc;
     for (size_t s = 0, at = 0; s < n_steps; ++s) { p->chk_off.push_back((u32)at); p->chk_cnt.push_back(check_sizes[s]); at += check_sizes[s]; }
     const size_t ebytes = (size_t)total * p->instances;
-    HIP_TRY(c, hipMalloc(&p->d_chk_slots, total * sizeof(u32)));
-    HIP_TRY(c, hipMemcpy(p->d_chk_slots, shifted.data(), total * sizeof(u32), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMalloc(&p->d_expect, ebytes));
-    HIP_TRY(c, hipHostMalloc(&p->h_expect, ebytes));
-    HIP_TRY(c, hipEventCreateWithFlags(&p->expect_ev, hipEventDisableTiming));
+    HIP_TRY(c, upload_vector(p->d_chk_slots, shifted));
+    HIP_TRY(c, p->expect.reserve(ebytes, ebytes, nullptr));   // once, here: the next capture points into it
     p->chk_total = (u32)total;
     p->chk_repair = repair;
     return BCE_OK;
@@ -1486,14 +1395,11 @@ int bce_plan_set_expected(bce_ctx* c, bce_plan* p, const uint8_t* expect) {
     if (!expect) return c->fail(BCE_ERR_ARG, "bce_plan_set_expected: null pointer");
     if (!p->chk_total) return c->fail(BCE_ERR_STATE, "bce_plan_set_expected: the plan has no checks (bce_plan_set_checks)");
     const size_t bytes = (size_t)p->chk_total * p->instances;
-    for (size_t i = 0; i < bytes; ++i)
-        if (expect[i] > 3) return c->fail(BCE_ERR_ARG, "bce_plan_set_expected: expect[%zu] = %u is not a message (0..3)", i, expect[i]);
+    if (const int rc = expected_are_messages(c, "bce_plan_set_expected", expect, bytes)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (p->expect_busy) { HIP_TRY(c, hipEventSynchronize(p->expect_ev)); p->expect_busy = false; }
-    std::memcpy(p->h_expect, expect, bytes);
-    HIP_TRY(c, hipMemcpyAsync(p->d_expect, p->h_expect, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipEventRecord(p->expect_ev, c->stream));
-    p->expect_busy = true;
+    HIP_TRY(c, p->expect.reserve(bytes, bytes, nullptr));   // its size since bce_plan_set_checks: only waits for the last upload
+    std::memcpy(p->expect.host(), expect, bytes);
+    HIP_TRY(c, p->expect.send(bytes, c->stream));
     p->expected_set = true;
     return BCE_OK;
 }
@@ -1502,7 +1408,7 @@ int bce_check_reset(bce_ctx* c) {
     if (!c) return BCE_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = ensure_check(c)) return rc;
-    HIP_TRY(c, hipMemsetAsync(c->d_check, 0, sizeof(bce_check_report), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_check(), 0, sizeof(bce_check_report), c->stream));
     return BCE_OK;
 }
 
@@ -1512,10 +1418,10 @@ int bce_check_get(bce_ctx* c, bce_check_report* out, bce_check_entry* log, uint3
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = ensure_check(c)) return rc;
     if (const int rc = sync_stream(c)) return rc;
-    HIP_TRY(c, hipMemcpy(out, c->d_check, sizeof *out, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out, c->d_check(), sizeof *out, hipMemcpyDeviceToHost));
     out->log_count = std::min<u32>(out->log_count, kCheckLogCap);   // the device counter goes on counting past the log's end
     const u32 n = std::min(out->log_count, log_cap);
-    if (n) HIP_TRY(c, hipMemcpy(log, c->d_check_log, (size_t)n * sizeof *log, hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(c, hipMemcpy(log, c->d_check_log(), (size_t)n * sizeof *log, hipMemcpyDeviceToHost));
     return BCE_OK;
 }
 
@@ -1531,23 +1437,20 @@ struct bce_dag {
     std::vector<u32> init_items;                   // initially ready tasks by class
     u32 init_off[kDagQueues + 1] = {0, 0, 0, 0, 0};
     // immutable device arrays
-    bce_gate_desc* d_tasks = nullptr;
-    u32 *d_cons_off = nullptr, *d_cons = nullptr, *d_dep_init = nullptr, *d_init = nullptr;
-    uint8_t* d_qid = nullptr;
-    // per-run state, grown on demand
-    u32* d_dep = nullptr; size_t dep_cap = 0;
-    u32* d_slots[kDagQueues] = {nullptr, nullptr, nullptr, nullptr}; size_t slots_cap[kDagQueues] = {0, 0, 0, 0};
-    u32* d_ctl = nullptr;
-    DagParams* d_params = nullptr;
+    DevBuf<bce_gate_desc> d_tasks;
+    DevBuf<u32> d_cons_off, d_cons, d_dep_init, d_init;
+    DevBuf<uint8_t> d_qid;
+    // per-run state, grown on demand to the exact size, after the work in flight
+    DevBuf<u32> d_dep;
+    DevBuf<u32> d_slots[kDagQueues];
+    DevBuf<u32> d_ctl;
+    DevBuf<DagParams> d_params;
     // verify mode (bce_dag_set_checks / bce_dag_set_expected): check number + 1 per task, and the expected bits of the next
     // run(s) with their pinned staging buffer, grown on demand
     u32 n_checks = 0;
     int chk_repair = 0;
-    u32* d_chk_of_task = nullptr;
-    uint8_t *d_expect = nullptr, *h_expect = nullptr;
-    size_t expect_cap = 0;
-    hipEvent_t expect_ev = nullptr;
-    bool expect_busy = false;
+    DevBuf<u32> d_chk_of_task;
+    StagedUpload expect;
     u32 expect_instances = 0;                      // the instance count the expected bits were set for, 0 = not set
 };
 
@@ -1576,17 +1479,29 @@ void bce_dag_destroy(bce_ctx* c, bce_dag* g) {
     }
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
-    dag_free(g);
+    delete g;
 }
 
-static void dag_free(bce_dag* g) {
-    hipFree(g->d_tasks); hipFree(g->d_cons_off); hipFree(g->d_cons); hipFree(g->d_dep_init); hipFree(g->d_init); hipFree(g->d_qid);
-    hipFree(g->d_dep); hipFree(g->d_ctl); hipFree(g->d_params);
-    for (u32 q = 0; q < kDagQueues; ++q) hipFree(g->d_slots[q]);
-    hipFree(g->d_chk_of_task); hipFree(g->d_expect);
-    if (g->h_expect) hipHostFree(g->h_expect);
-    if (g->expect_ev) hipEventDestroy(g->expect_ev);
-    delete g;
+// (Here, where bce_plan and bce_dag are complete.)  The order is kept in this body rather than in the order of bce_ctx's
+// members: the stream is synchronised first, every buffer of the context and of its schedules is released by its owner
+// (devmem.hpp), the stream is destroyed last.
+void bce_ctx_destroy(bce_ctx* c) {
+    if (!c) return;
+    hipSetDevice(c->device);
+    if (c->stream) hipStreamSynchronize(c->stream);
+    if (c->rccl_comm) bce_rccl_shutdown(c);
+    drain_timing(c);
+    {   // schedules nobody destroyed: theirs callers' handles die with the context
+        std::unordered_set<bce_plan*> plans;
+        std::unordered_set<bce_dag*> dags;
+        { std::lock_guard<std::mutex> lk(g_live_mu); plans.swap(c->plans); dags.swap(c->dags); g_live.erase(c); }
+        for (bce_plan* p : plans) delete p;
+        for (bce_dag* g : dags) delete g;
+    }
+    for (auto& p : c->free_events) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
+    const hipStream_t stream = c->stream;
+    delete c;
+    if (stream) hipStreamDestroy(stream);
 }
 
 int bce_dag_set_checks(bce_ctx* c, bce_dag* g, uint32_t n_checks, const uint32_t* tasks, int repair) {
@@ -1604,8 +1519,8 @@ int bce_dag_set_checks(bce_ctx* c, bce_dag* g, uint32_t n_checks, const uint32_t
     g->n_checks = 0; g->expect_instances = 0;      // new lists need their own expected bits
     if (n_checks == 0) return BCE_OK;              // detached: bce_dag_run passes no list to the kernel
     if (const int rc = ensure_check(c)) return rc;
-    if (!g->d_chk_of_task) HIP_TRY(c, hipMalloc(&g->d_chk_of_task, (size_t)g->n_tasks * sizeof(u32)));
-    HIP_TRY(c, hipMemcpy(g->d_chk_of_task, of_task.data(), (size_t)g->n_tasks * sizeof(u32), hipMemcpyHostToDevice));
+    if (!g->d_chk_of_task.get()) HIP_TRY(c, g->d_chk_of_task.alloc(g->n_tasks));
+    HIP_TRY(c, hipMemcpy(g->d_chk_of_task.get(), of_task.data(), (size_t)g->n_tasks * sizeof(u32), hipMemcpyHostToDevice));
     g->n_checks = n_checks;
     g->chk_repair = repair ? 1 : 0;
     return BCE_OK;
@@ -1617,23 +1532,12 @@ int bce_dag_set_expected(bce_ctx* c, bce_dag* g, uint32_t instances, const uint8
     if (instances == 0) return c->fail(BCE_ERR_ARG, "bce_dag_set_expected: no instances");
     if (!g->n_checks) return c->fail(BCE_ERR_STATE, "bce_dag_set_expected: the DAG has no checks (bce_dag_set_checks)");
     const size_t bytes = (size_t)g->n_checks * instances;
-    for (size_t i = 0; i < bytes; ++i)
-        if (expect[i] > 3) return c->fail(BCE_ERR_ARG, "bce_dag_set_expected: expect[%zu] = %u is not a message (0..3)", i, expect[i]);
+    if (const int rc = expected_are_messages(c, "bce_dag_set_expected", expect, bytes)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (g->expect_busy) { HIP_TRY(c, hipEventSynchronize(g->expect_ev)); g->expect_busy = false; }   // the last upload has left the pinned buffer
-    if (bytes > g->expect_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));   // a run in flight may still read the old buffer
-        hipFree(g->d_expect); if (g->h_expect) hipHostFree(g->h_expect);
-        g->d_expect = g->h_expect = nullptr; g->expect_cap = 0; g->expect_instances = 0;
-        HIP_TRY(c, hipMalloc(&g->d_expect, bytes));
-        HIP_TRY(c, hipHostMalloc(&g->h_expect, bytes));
-        g->expect_cap = bytes;
-    }
-    if (!g->expect_ev) HIP_TRY(c, hipEventCreateWithFlags(&g->expect_ev, hipEventDisableTiming));
-    std::memcpy(g->h_expect, expect, bytes);
-    HIP_TRY(c, hipMemcpyAsync(g->d_expect, g->h_expect, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipEventRecord(g->expect_ev, c->stream));
-    g->expect_busy = true;
+    if (bytes > g->expect.capacity()) g->expect_instances = 0;   // the old bits go with the old buffer
+    HIP_TRY(c, g->expect.reserve(bytes, bytes, c->stream));       // exact size; a run in flight may still read the old buffer
+    std::memcpy(g->expect.host(), expect, bytes);
+    HIP_TRY(c, g->expect.send(bytes, c->stream));
     g->expect_instances = instances;
     return BCE_OK;
 }
@@ -1697,21 +1601,15 @@ int bce_dag_create(bce_ctx* c, uint32_t n_tasks, const bce_gate_desc* tasks, con
     }
     g->init_off[kDagQueues] = (u32)g->init_items.size();
     if (g->init_items.empty()) return c->fail(BCE_ERR_ARG, "bce_dag_create: no task is ready at the start");
-    auto up = [&](auto** dst, const auto& v) -> hipError_t {
-        using T = std::remove_reference_t<decltype(v[0])>;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), std::max<size_t>(1, v.size()) * sizeof(T));
-        if (e != hipSuccess) return e;
-        return hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    };
-    HIP_TRY(c, hipMalloc(&g->d_tasks, (size_t)n_tasks * sizeof(bce_gate_desc)));
-    HIP_TRY(c, hipMemcpy(g->d_tasks, tasks, (size_t)n_tasks * sizeof(bce_gate_desc), hipMemcpyHostToDevice));
-    HIP_TRY(c, up(&g->d_cons_off, cons_off));
-    HIP_TRY(c, up(&g->d_cons, cons));
-    HIP_TRY(c, up(&g->d_dep_init, dep));
-    HIP_TRY(c, up(&g->d_init, g->init_items));
-    HIP_TRY(c, up(&g->d_qid, qid));
-    HIP_TRY(c, hipMalloc(&g->d_ctl, kDagCtlWords * sizeof(u32)));
-    HIP_TRY(c, hipMalloc(&g->d_params, sizeof(DagParams)));
+    HIP_TRY(c, g->d_tasks.alloc(n_tasks));
+    HIP_TRY(c, hipMemcpy(g->d_tasks.get(), tasks, (size_t)n_tasks * sizeof(bce_gate_desc), hipMemcpyHostToDevice));
+    HIP_TRY(c, upload_vector(g->d_cons_off, cons_off));
+    HIP_TRY(c, upload_vector(g->d_cons, cons));
+    HIP_TRY(c, upload_vector(g->d_dep_init, dep));
+    HIP_TRY(c, upload_vector(g->d_init, g->init_items));
+    HIP_TRY(c, upload_vector(g->d_qid, qid));
+    HIP_TRY(c, g->d_ctl.alloc(kDagCtlWords));
+    HIP_TRY(c, g->d_params.alloc(1));
     *out = g.release();
     return BCE_OK;
 }
@@ -1719,7 +1617,7 @@ int bce_dag_create(bce_ctx* c, uint32_t n_tasks, const bce_gate_desc* tasks, con
 int bce_dag_debug_block_task(bce_dag* g, uint32_t t) {
     if (!g || t >= g->n_tasks) return BCE_ERR_ARG;
     g->h_dep_init[t] += 1;
-    return hipMemcpy(g->d_dep_init, g->h_dep_init.data(), (size_t)g->n_tasks * sizeof(u32), hipMemcpyHostToDevice) == hipSuccess ? BCE_OK : BCE_ERR_HIP;
+    return hipMemcpy(g->d_dep_init.get(), g->h_dep_init.data(), (size_t)g->n_tasks * sizeof(u32), hipMemcpyHostToDevice) == hipSuccess ? BCE_OK : BCE_ERR_HIP;
 }
 
 int bce_dag_run(bce_ctx* c, bce_dag* g, uint32_t instances, uint32_t slot_stride, uint32_t slot_base) {
@@ -1734,37 +1632,27 @@ int bce_dag_run(bce_ctx* c, bce_dag* g, uint32_t instances, uint32_t slot_stride
     if (items >= 0xFFFFFFF0ull) return c->fail(BCE_ERR_ARG, "bce_dag_run: %llu bootstraps exceed one run's 32-bit item space", (unsigned long long)items);
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->dag_pending >= bce_ctx::kDagRuns) { const int rc = sync_stream(c); if (rc) return rc; }
-    if (!c->d_P) HIP_TRY(c, hipMalloc(&c->d_P, sizeof(DevParams)));
-    if (!c->h_dag_status) HIP_TRY(c, hipHostMalloc(&c->h_dag_status, sizeof(bce_ctx::DagStatus) * bce_ctx::kDagRuns));
-    if (!c->h_dag_stage) HIP_TRY(c, hipHostMalloc(&c->h_dag_stage, sizeof(bce_ctx::DagStage) * bce_ctx::kDagRuns));
+    if (!c->d_P.get()) HIP_TRY(c, c->d_P.alloc(1));
+    if (!c->h_dag_status.get()) HIP_TRY(c, c->h_dag_status.alloc(bce_ctx::kDagRuns));
+    if (!c->h_dag_stage.get()) HIP_TRY(c, c->h_dag_stage.alloc(bce_ctx::kDagRuns));
     // per-run state (a dag object serves one run at a time: runs are ordered on the engine's stream)
-    if (items > g->dep_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        hipFree(g->d_dep); g->d_dep = nullptr;
-        HIP_TRY(c, hipMalloc(&g->d_dep, items * sizeof(u32)));
-        g->dep_cap = items;
-    }
+    HIP_TRY(c, g->d_dep.grow(items, items, c->stream));
     DagParams D{};
     for (u32 q = 0; q < kDagQueues; ++q) {
         const size_t need = (size_t)g->qcount[q] * instances;
-        if (need > g->slots_cap[q]) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            hipFree(g->d_slots[q]); g->d_slots[q] = nullptr;
-            HIP_TRY(c, hipMalloc(&g->d_slots[q], need * sizeof(u32)));
-            g->slots_cap[q] = need;
-        }
-        D.slots[q] = g->d_slots[q];
+        HIP_TRY(c, g->d_slots[q].grow(need, need, c->stream));
+        D.slots[q] = g->d_slots[q].get();
         D.qcap[q] = (u32)need;
         D.init_off[q] = g->init_off[q];
     }
     D.init_off[kDagQueues] = g->init_off[kDagQueues];
-    D.tasks = g->d_tasks; D.cons_off = g->d_cons_off; D.cons = g->d_cons; D.qid = g->d_qid; D.dep_init = g->d_dep_init;
-    D.dep = g->d_dep; D.init_items = g->d_init; D.ctl = g->d_ctl;
+    D.tasks = g->d_tasks.get(); D.cons_off = g->d_cons_off.get(); D.cons = g->d_cons.get(); D.qid = g->d_qid.get(); D.dep_init = g->d_dep_init.get();
+    D.dep = g->d_dep.get(); D.init_items = g->d_init.get(); D.ctl = g->d_ctl.get();
     D.n_tasks = g->n_tasks; D.instances = instances; D.slot_stride = slot_stride; D.slot_base = slot_base;
     if (g->n_checks) {   // verify mode: the worker checks (and repairs) before it releases a task's consumers
         if (const int rc = ensure_check(c)) return rc;
-        D.chk_of_task = g->d_chk_of_task; D.expect = g->d_expect; D.n_checks = g->n_checks; D.repair = (u32)g->chk_repair;
-        D.s8 = c->d_s8; D.report = c->d_check; D.log = c->d_check_log;
+        D.chk_of_task = g->d_chk_of_task.get(); D.expect = static_cast<const uint8_t*>(g->expect.device()); D.n_checks = g->n_checks; D.repair = (u32)g->chk_repair;
+        D.s8 = c->d_s8.get(); D.report = c->d_check(); D.log = c->d_check_log();
     }
     D.lazy_ticks = c->dag_lazy_us * 100u;                     // s_memrealtime: 100 MHz
     D.stall_ticks = c->dag_stall_ms * 100000u;
@@ -1799,19 +1687,20 @@ int bce_dag_run(bce_ctx* c, bce_dag* g, uint32_t instances, uint32_t slot_stride
     // parameter blocks reach the device in stream order (an earlier run may still be reading the previous ones) from
     // pinned staging entries that stay untouched until the next synchronisation
     const int slot = c->dag_pending++;
-    c->h_dag_stage[slot].P = c->P;
-    c->h_dag_stage[slot].D = D;
-    HIP_TRY(c, hipMemcpyAsync(c->d_P, &c->h_dag_stage[slot].P, sizeof(DevParams), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(g->d_params, &c->h_dag_stage[slot].D, sizeof(DagParams), hipMemcpyHostToDevice, c->stream));
+    bce_ctx::DagStage& stage = c->h_dag_stage.get()[slot];
+    stage.P = c->P;
+    stage.D = D;
+    HIP_TRY(c, hipMemcpyAsync(c->d_P.get(), &stage.P, sizeof(DevParams), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(g->d_params.get(), &stage.D, sizeof(DagParams), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, launch_dag_rearm(D, c->stream));
     EventPair e0 = get_events(c, BCE_BR_DAG);
     hipEventRecord(e0.a, c->stream);
-    if (!(dbg && dbg[0] == 'r')) HIP_TRY(c, launch_bootstrap_dag(c->P, c->d_P, g->d_params, wps, grid, c->stream));
+    if (!(dbg && dbg[0] == 'r')) HIP_TRY(c, launch_bootstrap_dag(c->P, c->d_P.get(), g->d_params.get(), wps, grid, c->stream));
     hipEventRecord(e0.b, c->stream);
     c->pending.push_back(e0);
     c->dag_expected[slot] = items;
     c->dag_wps_used[slot] = wps;
-    HIP_TRY(c, hipMemcpyAsync(&c->h_dag_status[slot], g->d_ctl + kDagAbort, sizeof(bce_ctx::DagStatus), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&c->h_dag_status.get()[slot], g->d_ctl.get() + kDagAbort, sizeof(bce_ctx::DagStatus), hipMemcpyDeviceToHost, c->stream));
     c->timing.br_launches[BCE_BR_DAG] += 1;
     c->timing.br_bootstraps[BCE_BR_DAG] += items;
     c->timing.blind_rotate_launches += 1;
@@ -1908,25 +1797,22 @@ int bce_debug_tail(bce_ctx* c, uint32_t count, const uint64_t* acc, const uint32
         if (out_slots[i] >= c->pool_slots) return c->fail(BCE_ERR_POOL, "slot %u outside the pool", out_slots[i]);
         d[i] = bce_gate_desc{BCE_AND, out_slots[i], out_slots[i], out_slots[i], 0, 0};
     }
-    void* d_in = nullptr;
-    u32 *d_lweN = nullptr, *d_ks = nullptr;
-    u64* d_partial = nullptr;
-    HIP_TRY(c, hipMalloc(&d_in, words * c->wbytes));
-    HIP_TRY(c, hipMalloc(&d_lweN, (size_t)count * (c->N + 1) * sizeof(u32)));
-    HIP_TRY(c, hipMalloc(&d_ks, (size_t)count * (c->n + 1) * sizeof(u32)));
-    HIP_TRY(c, hipMalloc(&d_partial, std::max<size_t>(1, tail_partial_words(c->P, count)) * sizeof(u64)));
-    int rc = words_to_device(c, d_in, acc, words, c->is64);
+    DevBuf<char> d_in;
+    DevBuf<u32> d_lweN, d_ks;
+    DevBuf<u64> d_partial;
+    HIP_TRY(c, d_in.alloc(words * c->wbytes));
+    HIP_TRY(c, d_lweN.alloc((size_t)count * (c->N + 1)));
+    HIP_TRY(c, d_ks.alloc((size_t)count * (c->n + 1)));
+    HIP_TRY(c, d_partial.alloc(std::max<size_t>(1, tail_partial_words(c->P, count))));
+    int rc = words_to_device(c, d_in.get(), acc, words, c->is64);
     if (rc) return rc;
-    bce_gate_desc* dd = nullptr;
-    int slot = 0;
-    if ((rc = stage_descs(c, d.data(), count, &dd, &slot))) return rc;
-    HIP_TRY(c, launch_tail(c->P, dd, count, 1, 0, d_in, d_partial, d_lweN, d_ks, c->stream, LaunchEvents{}));
-    hipEventRecord(c->ring_ev[slot], c->stream);
-    c->ring_busy[slot] = true;
+    StagedUpload* slot = nullptr;
+    if ((rc = stage_descs(c, d.data(), count, &slot))) return rc;
+    HIP_TRY(c, launch_tail(c->P, descs_of(slot), count, 1, 0, d_in.get(), d_partial.get(), d_lweN.get(), d_ks.get(), c->stream, LaunchEvents{}));
+    slot->mark(c->stream);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (lweN && (rc = words_from_device(c, lweN, d_lweN, (size_t)count * (c->N + 1), false))) return rc;
-    if (ks && (rc = words_from_device(c, ks, d_ks, (size_t)count * (c->n + 1), false))) return rc;
-    hipFree(d_in); hipFree(d_lweN); hipFree(d_ks); hipFree(d_partial);
+    if (lweN && (rc = words_from_device(c, lweN, d_lweN.get(), (size_t)count * (c->N + 1), false))) return rc;
+    if (ks && (rc = words_from_device(c, ks, d_ks.get(), (size_t)count * (c->n + 1), false))) return rc;
     return BCE_OK;
 }
 
@@ -1939,13 +1825,11 @@ static int pool_pack(bce_ctx* c, const uint32_t* slots, uint32_t count, void* de
         if (slots[i] >= c->pool_slots) return c->fail(BCE_ERR_POOL, "slot %u outside the pool", slots[i]);
         d[i] = bce_gate_desc{BCE_OP_COPY, slots[i], slots[i], slots[i], 0, 0};
     }
-    bce_gate_desc* dd = nullptr;
-    int slot = 0;
-    int rc = stage_descs(c, d.data(), count, &dd, &slot);
+    StagedUpload* slot = nullptr;
+    int rc = stage_descs(c, d.data(), count, &slot);
     if (rc) return rc;
-    HIP_TRY(c, launch_pool_pack(c->P, dd, count, (u32*)dev, to_pool, c->stream));
-    hipEventRecord(c->ring_ev[slot], c->stream);
-    c->ring_busy[slot] = true;
+    HIP_TRY(c, launch_pool_pack(c->P, descs_of(slot), count, (u32*)dev, to_pool, c->stream));
+    slot->mark(c->stream);
     return BCE_OK;
 }
 
@@ -1962,15 +1846,13 @@ int bce_debug_ntt(bce_ctx* c, uint64_t* polys, uint32_t count, int inverse) {
     const size_t words = (size_t)count * c->N;
     for (size_t i = 0; i < words; ++i)
         if (polys[i] >= c->Q) return c->fail(BCE_ERR_ARG, "poly word not reduced mod Q");
-    void* d = nullptr;
-    HIP_TRY(c, hipMalloc(&d, words * c->wbytes));
-    int rc = words_to_device(c, d, polys, words, c->is64);
-    if (!rc) rc = dev_ntt(c, d, count, inverse);
+    DevBuf<char> d;
+    HIP_TRY(c, d.alloc(words * c->wbytes));
+    int rc = words_to_device(c, d.get(), polys, words, c->is64);
+    if (!rc) rc = dev_ntt(c, d.get(), count, inverse);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if ((rc = words_from_device(c, polys, d, words, c->is64))) return rc;
-    hipFree(d);
-    return BCE_OK;
+    return words_from_device(c, polys, d.get(), words, c->is64);
 }
 
 }  // extern "C"
