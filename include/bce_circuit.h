@@ -101,8 +101,9 @@ int bce_circuit_set_xor_fast(bce_circuit*, int on);
  * with xor_fast: BCE_ERR_ARG.  It is ACTIVE (bce_circuit_xor_shared_active) with batched launches on the bootstrap-depth
  * schedule, without gate sharding and without a host-side verify pass (verify without device verify); when it is not, the
  * reference lowering runs exactly as without it.  Graph replay and device verify work with it (the checked registers are
- * the same netlist wires).  The dataflow kernel has no pairs: requested together with dataflow, the step schedule runs and
- * bce_circuit_dataflow_active answers 0.  n_bootstraps, the step sizes, the statistics and the plan hash reflect the mode.
+ * the same netlist wires).  Requested together with dataflow alone, the step schedule runs and
+ * bce_circuit_dataflow_active answers 0; with bce_circuit_set_dataflow_shared on top the dataflow kernel runs the pairs
+ * (below).  n_bootstraps, the step sizes, the statistics and the plan hash reflect the mode.
  * Whether it is active is fixed at SetInput as well: set_batched, set_relevel, set_device_verify and set_verify switch the
  * lowering (and rebuild the schedule) when they change the answer of bce_circuit_xor_shared_active before SetInput; after
  * SetInput such a call is BCE_ERR_STATE and changes nothing, because the pool is laid out for the schedule of one lowering
@@ -155,6 +156,14 @@ int bce_circuit_check_relevel(bce_circuit*);
  * bce_circuit_dataflow_active tells. */
 int bce_circuit_set_dataflow(bce_circuit*, int on);
 int bce_circuit_dataflow_active(const bce_circuit*);   /* 1 if the next encrypted Clock() takes the dataflow path */
+/* opt-in on top of set_dataflow and set_xor_shared: the shared XOR lowering ON the dataflow schedule.  Where the shared
+ * lowering is active the task list then holds, per XOR, a pair task (BCE_PAIR(OR, NAND) into the XOR's own two adjacent
+ * temporaries) and the AND of the two -- two tasks per XOR instead of three, the same slot stride -- and Clock() creates
+ * its DAGs with bce_dag_create_pairs; bce_circuit_dataflow_active and bce_circuit_xor_shared_active both answer 1.  Device
+ * verify on that schedule checks the AND tasks (the same netlist wires).  Without this call the two options together run
+ * the step schedule, as before.  Call it before SetInput: BCE_ERR_STATE after, if it would change the setting.  The plan
+ * hash reflects it. */
+int bce_circuit_set_dataflow_shared(bce_circuit*, int on);
 /* Opt-in for the bootstrap-depth schedule (set_relevel): its launches are captured once into a hipGraph and every
  * Clock() replays them with one launch (bce_plan_run) -- no per-step host call between the dependent kernels.  Same
  * ciphertexts.  Without it the same resident descriptors are walked step by step (bce_plan_run_step).  Not with gate
@@ -182,7 +191,8 @@ int bce_circuit_device_verify_active(const bce_circuit*);
 /* The device's report of the last Clock() on that path (all zero otherwise): checks, mismatches, repairs and the phase
  * error statistics of every checked gate output (noise margin = q/8 - max_abs_err). */
 int bce_circuit_get_check_report(const bce_circuit*, bce_check_report* out);
-/* The task list of the dataflow schedule (what bce_dag_create receives): gates in topological order with SSA slots for
+/* The task list of the dataflow schedule (what bce_dag_create receives; bce_dag_create_pairs under
+ * bce_circuit_set_dataflow_shared, `op` then holds the pair words): gates in topological order with SSA slots for
  * ONE instance (slot < slot_stride of bce_circuit_get_info) and their priority classes.  Writes min(*n_tasks, cap)
  * entries to each non-NULL array and sets *n_tasks to the number of tasks (= bootstraps of one evaluation). */
 int bce_circuit_dataflow_plan(const bce_circuit*, bce_gate_desc* tasks, uint8_t* prio, uint32_t cap, uint32_t* n_tasks);

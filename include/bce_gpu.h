@@ -73,8 +73,8 @@ typedef struct bce_gate_desc {
  * it (the gadget decomposition's rounding is not symmetric under the rotation); its noise is that of a plain gate.
  * Legal: op and op2 two DIFFERENT gates of BCE_OR, BCE_AND, BCE_NOR, BCE_NAND; anything else in bits 8.. is BCE_ERR_ARG.
  * out + 1 obeys every rule out obeys (pool bound: BCE_ERR_POOL; written by this call, read by none of it).
- * Accepted by bce_eval_gates, bce_eval_gates_strided, bce_plan_create and bce_debug_eval_stages; bce_dag_create refuses
- * pairs (BCE_ERR_UNSUPPORTED).  The counters of bce_timing count blind rotations: a pair counts 1.
+ * Accepted by bce_eval_gates, bce_eval_gates_strided, bce_plan_create, bce_debug_eval_stages and bce_dag_create_pairs;
+ * bce_dag_create refuses pairs (BCE_ERR_UNSUPPORTED).  The counters of bce_timing count blind rotations: a pair counts 1.
  * XOR(a, b) = AND(OR(a, b), NAND(a, b)) is then two blind rotations instead of three (bce_circuit_set_xor_shared). */
 #define BCE_PAIR(op, op2) ((uint32_t)(op) | (((uint32_t)(op2) + 1u) << 8))
 
@@ -267,6 +267,14 @@ int bce_check_get(bce_ctx*, bce_check_report*, bce_check_entry* log, uint32_t lo
 typedef struct bce_dag bce_dag;
 int bce_dag_supported(const bce_ctx*);   /* 1 when this context's parameter class has the persistent kernel */
 int bce_dag_create(bce_ctx*, uint32_t n_tasks, const bce_gate_desc* tasks, const uint8_t* prio, bce_dag** out);
+/* The same, with pair descriptors (BCE_PAIR) among the tasks.  A pair task is ONE task with two outputs: the persistent
+ * kernel runs its blind rotation once and the tail twice, and publishes `out` and `out + 1` with one release.  Both slots
+ * obey the SSA rule (written by this task alone, read by later tasks only) and count for the slot range that bce_dag_run
+ * checks against slot_stride (BCE_ERR_ARG) and the pool (BCE_ERR_POOL).  A later task that reads either output, or both,
+ * depends on the pair once.  A pair counts as one bootstrap in bce_timing and bce_dag_last_run and as one level of the
+ * DAG's depth.  Illegal bits 8.. of `op`: BCE_ERR_ARG, as in bce_eval_gates.  Plain task lists give the same DAG as
+ * bce_dag_create. */
+int bce_dag_create_pairs(bce_ctx*, uint32_t n_tasks, const bce_gate_desc* tasks, const uint8_t* prio, bce_dag** out);
 /* instance k of a run uses the DAG's slot numbers shifted by slot_base + k * slot_stride */
 int bce_dag_run(bce_ctx*, bce_dag*, uint32_t instances, uint32_t slot_stride, uint32_t slot_base);
 void bce_dag_destroy(bce_ctx*, bce_dag*);
@@ -275,7 +283,8 @@ void bce_dag_destroy(bce_ctx*, bce_dag*);
  * bootstrap has finished, compares it with the expected message and, with repair != 0, replaces a wrong one BEFORE it
  * releases the task's consumers -- the point at which the reference's Gate::Evaluate does it (src/gate.cpp:153-160); no
  * extra launch.  Report and log: the context's block, bce_check_reset / bce_check_get, as for plans; a log entry carries
- * tag = task index, index = check number.  n_checks == 0 detaches.  Synchronises.  BCE_ERR_NO_KEYS without keys,
+ * tag = task index, index = check number.  A check on a pair task (bce_dag_create_pairs) checks its FIRST output `out`;
+ * second outputs are temporaries and cannot be named.  n_checks == 0 detaches.  Synchronises.  BCE_ERR_NO_KEYS without keys,
  * BCE_ERR_ARG for a task index >= n_tasks, a duplicate task index or a null pointer. */
 int bce_dag_set_checks(bce_ctx*, bce_dag*, uint32_t n_checks, const uint32_t* tasks /*[n_checks], distinct*/, int repair);
 /* The expected messages (0..3) of the next run(s) of `instances` instances, expect[instances][n_checks]; asynchronous

@@ -91,7 +91,7 @@ ENGINE_SYMBOLS = [
     "bce_encrypt_bits", "bce_set_encrypt_seed", "bce_decrypt_bits", "bce_eval_gates", "bce_eval_gates_strided", "bce_synchronize",
     "bce_timing_reset", "bce_timing_get", "bce_timing_set_events", "bce_bytes_per_bootstrap", "bce_bytes_per_bootstrap_parts", "bce_forward_transforms_per_step", "bce_forward_units", "bce_forward_mfma", "bce_lazy_arithmetic", "bce_forward_mfma_tables", "bce_launch_capacity", "bce_rccl_available", "bce_rccl_version", "bce_rccl_unique_id", "bce_rccl_init", "bce_rccl_allgather", "bce_rccl_comm_info",
     "bce_rccl_shutdown", "bce_debug_eval_stages", "bce_debug_ntt", "bce_debug_tail",
-    "bce_dag_supported", "bce_dag_create", "bce_dag_run", "bce_dag_destroy", "bce_dag_set_limits", "bce_dag_last_run", "bce_dag_debug_block_task",
+    "bce_dag_supported", "bce_dag_create", "bce_dag_create_pairs", "bce_dag_run", "bce_dag_destroy", "bce_dag_set_limits", "bce_dag_last_run", "bce_dag_debug_block_task",
     "bce_dag_set_checks", "bce_dag_set_expected",
     "bce_plan_create", "bce_plan_run_step", "bce_plan_run", "bce_plan_destroy",
     "bce_check_slots", "bce_plan_set_checks", "bce_plan_set_expected", "bce_check_reset", "bce_check_get",
@@ -188,6 +188,7 @@ def lib():
     L.bce_debug_tail.argtypes = [vp, u32, vp, vp, vp, vp]
     L.bce_dag_supported.argtypes = [vp]
     L.bce_dag_create.argtypes = [vp, u32, vp, vp, C.POINTER(vp)]
+    L.bce_dag_create_pairs.argtypes = [vp, u32, vp, vp, C.POINTER(vp)]
     L.bce_dag_run.argtypes = [vp, vp, u32, u32, u32]
     L.bce_dag_destroy.argtypes = [vp, vp]
     L.bce_dag_destroy.restype = None
@@ -388,8 +389,9 @@ class BinFHEContext:
     def dag_supported(self):
         return bool(self._L.bce_dag_supported(self.h))
 
-    def dag_create(self, tasks, prio=None):
-        """tasks: (op, in0, in1, out[, neg0, neg1]) in topological order, SSA slots; returns an opaque handle"""
+    def dag_create(self, tasks, prio=None, pairs=False):
+        """tasks: (op, in0, in1, out[, neg0, neg1]) in topological order, SSA slots; returns an opaque handle.
+        pairs=True (bce_dag_create_pairs): PAIR words are tasks with the two outputs out and out + 1"""
         arr = (GateDesc * len(tasks))()
         for i, t in enumerate(tasks):
             arr[i] = GateDesc(*(tuple(t) + (0, 0))[:6])
@@ -397,7 +399,8 @@ class BinFHEContext:
         if prio is not None:
             pr = (C.c_uint8 * len(tasks))(*[int(x) for x in prio])
         h = C.c_void_p()
-        self._ck(self._L.bce_dag_create(self.h, len(tasks), arr, pr, C.byref(h)))
+        create = self._L.bce_dag_create_pairs if pairs else self._L.bce_dag_create
+        self._ck(create(self.h, len(tasks), arr, pr, C.byref(h)))
         return h
 
     def dag_run(self, dag, instances=1, slot_stride=0, slot_base=0):
@@ -605,7 +608,7 @@ CIRCUIT_SYMBOLS = [
     "bce_circuit_create", "bce_circuit_destroy", "bce_circuit_last_error", "bce_circuit_read_file",
     "bce_circuit_read_bristol", "bce_circuit_get_info", "bce_circuit_reset", "bce_circuit_rearm", "bce_circuit_set_plaintext",
     "bce_circuit_set_encrypted", "bce_circuit_set_verify", "bce_circuit_get_flags", "bce_circuit_set_batched",
-    "bce_circuit_set_encrypt_mode", "bce_circuit_get_encrypt_mode", "bce_circuit_plan_hash", "bce_circuit_set_shard_locality", "bce_circuit_set_xor_fast", "bce_circuit_set_xor_shared", "bce_circuit_xor_shared_active", "bce_circuit_set_relevel", "bce_circuit_get_relevel", "bce_circuit_set_dataflow", "bce_circuit_dataflow_active", "bce_circuit_set_graph", "bce_circuit_graph_active", "bce_circuit_set_device_verify", "bce_circuit_device_verify_active", "bce_circuit_get_check_report", "bce_circuit_dataflow_plan", "bce_circuit_set_balance", "bce_circuit_relevel_steps", "bce_circuit_relevel_descs", "bce_circuit_relevel_publications", "bce_circuit_check_relevel", "bce_circuit_set_instances", "bce_circuit_set_input", "bce_circuit_clock",
+    "bce_circuit_set_encrypt_mode", "bce_circuit_get_encrypt_mode", "bce_circuit_plan_hash", "bce_circuit_set_shard_locality", "bce_circuit_set_xor_fast", "bce_circuit_set_xor_shared", "bce_circuit_xor_shared_active", "bce_circuit_set_relevel", "bce_circuit_get_relevel", "bce_circuit_set_dataflow", "bce_circuit_set_dataflow_shared", "bce_circuit_dataflow_active", "bce_circuit_set_graph", "bce_circuit_graph_active", "bce_circuit_set_device_verify", "bce_circuit_device_verify_active", "bce_circuit_get_check_report", "bce_circuit_dataflow_plan", "bce_circuit_set_balance", "bce_circuit_relevel_steps", "bce_circuit_relevel_descs", "bce_circuit_relevel_publications", "bce_circuit_check_relevel", "bce_circuit_set_instances", "bce_circuit_set_input", "bce_circuit_clock",
     "bce_circuit_get_output", "bce_circuit_get_buses", "bce_circuit_get_counts", "bce_circuit_get_stats", "bce_circuit_dump",
     "bce_circuit_set_exchange", "bce_circuit_enable_rccl", "bce_circuit_exchange_capacity", "bce_assemble_bristol", "bce_pool_gather",
     "bce_pool_scatter",
@@ -636,6 +639,7 @@ def _bind_circuit():
     L.bce_circuit_set_instances.argtypes = [vp, u32]
     L.bce_circuit_set_balance.argtypes = [vp, i32, u32, u32]
     L.bce_circuit_set_dataflow.argtypes = [vp, i32]
+    L.bce_circuit_set_dataflow_shared.argtypes = [vp, i32]
     L.bce_circuit_set_graph.argtypes = [vp, i32]
     L.bce_circuit_graph_active.argtypes = [vp]
     L.bce_circuit_set_device_verify.argtypes = [vp, i32]
@@ -821,6 +825,11 @@ class Circuit:
     def setDataflow(self, b):
         """opt-in: the whole bootstrap DAG in one persistent launch (device-side ready-gate rule); before SetInput"""
         self._ck(self._L.bce_circuit_set_dataflow(self.h, int(b)))
+
+    def setDataflowShared(self, b):
+        """opt-in on top of setDataflow and setXorShared: the shared XORs stay on the dataflow schedule as pair tasks
+        (dataflowActive() and xorSharedActive() both True); without it the two together run the step schedule; before SetInput"""
+        self._ck(self._L.bce_circuit_set_dataflow_shared(self.h, int(b)))
 
     def dataflow_plan(self):
         """(tasks, priority classes) of the dataflow schedule: tasks = (op, in0, in1, out, neg0, neg1), one instance"""

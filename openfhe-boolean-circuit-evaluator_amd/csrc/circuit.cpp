@@ -522,6 +522,7 @@ uint64_t Circuit::planHash() const {
     uint64_t h = 0xcbf29ce484222325ull;   // FNV-1a over 64-bit words
     auto mix = [&](uint64_t v) { h = (h ^ v) * 0x100000001b3ull; };
     mix(world_); mix((uint64_t)shard_mode_); mix(stride_); mix(instances_); mix(relevel_ ? 1 : 0); mix((uint64_t)xorMode());
+    if (dataflow_shared_) mix(0x6466736872ull);   // "dfshr"; mixed only when set: the hashes without the flag are pinned (tests/golden)
     for (const auto& lv : shard_.owner) { mix(lv.size()); for (uint8_t o : lv) mix(o); }
     for (const auto& lv : shard_.publish) for (const auto& r : lv) { mix(r.size()); for (int w : r) mix((uint64_t)w); }
     for (const auto& st : steps_.publish) for (const auto& r : st) { mix(r.size()); for (int w : r) mix((uint64_t)w); }
@@ -620,8 +621,8 @@ void Circuit::rebuildRelevel() {
     const auto [lo, hi] = instanceRange();
     const uint64_t K = std::max(1u, hi - lo);
     const uint32_t world = gateSharded() ? world_ : 1;   // gate sharding: every step's units are split over the ranks
-    const bool want_tasks = dataflow_ && units_mode_ != sched::XorMode::Shared;   // the dataflow kernel has no pairs
-    if (!want_tasks || tasks_.tasks.empty()) tasks_ = want_tasks ? sched::lower_tasks(units_, net_.n_wires) : sched::TaskList{};   // a function of the units
+    const bool want_tasks = dataflow_ && tasksExist();   // shared XORs: pair tasks, with setDataflowShared only
+    if (!want_tasks || tasks_.tasks.empty()) tasks_ = want_tasks ? lowerTasks() : sched::TaskList{};   // a function of the units
     auto plan = [&](bool by_slack) {   // returns the slot stride the schedules need
         if (by_slack && !units_.units.empty()) {
             const auto [lone, full] = launchCapacity();
@@ -813,13 +814,14 @@ void Circuit::compareOutputs(unsigned lo, unsigned hi) {
 // ---- dataflow schedule: the whole bootstrap DAG in one persistent launch (bce_dag_*) -------------------------------
 // Tasks = the units of the bootstrap-depth schedule in topological order, an XOR as its two ANDs and its OR with
 // temporaries of its own (SSA: the device runs independent tasks in any order, so no slot may be reused); sched::lower_tasks.
+// Under the shared lowering there is a list only with setDataflowShared: a pair task into the same two temporaries, then the AND.
 void Circuit::setDataflow(bool b) {
     if (inputs_set_) {
         // the pool layout is fixed.  The schedule can be switched off and on again while that layout has room for its
         // temporaries (it was chosen when the inputs were set; tools/verify_cost.py alternates the schedules on one set of
         // input ciphertexts): only the choice changes, the schedules and their resident plans and DAGs stay as they are
-        if (b && tasks_.tasks.empty() && units_mode_ != sched::XorMode::Shared) {
-            sched::TaskList t = sched::lower_tasks(units_, net_.n_wires);
+        if (b && tasks_.tasks.empty() && tasksExist()) {
+            sched::TaskList t = lowerTasks();
             if (t.stride > stride_) throw std::logic_error("setDataflow: choose the dataflow schedule before SetInput (it lays the pool out with its own temporaries)");
             tasks_ = std::move(t);
         }
@@ -830,11 +832,26 @@ void Circuit::setDataflow(bool b) {
     rebuildRelevel();
 }
 
+// Opt-in: shared XORs on the dataflow schedule.  The task list is then lowered in XorMode::Shared -- a pair task and an AND
+// per XOR -- and goes to the engine through bce_dag_create_pairs.  Part of the pool layout and of the lowering: before SetInput.
+void Circuit::setDataflowShared(bool b) {
+    if (inputs_set_ && b != dataflow_shared_) throw std::logic_error("setDataflowShared: choose the dataflow schedule of the shared XOR lowering before SetInput");
+    if (b == dataflow_shared_) return;
+    dataflow_shared_ = b;
+    tasks_ = {};          // the list depends on the flag where the units are shared
+    rebuildRelevel();
+}
+
+void Circuit::createDag(bce_dag** g) {
+    const auto create = tasksHavePairs() ? bce_dag_create_pairs : bce_dag_create;
+    ck(create(cc, (uint32_t)tasks_.tasks.size(), tasks_.tasks.data(), tasks_.prio.data(), g), "Clock(dataflow DAG)");
+}
+
 void Circuit::clockDataflow() {
     const auto [lo, hi] = instanceRange();
     if (tasks_.stride > stride_) throw std::logic_error("dataflow schedule needs more scratch slots than the pool stride");
     if (steps_.steps.empty()) rebuildRelevel();
-    if (!dag_) ck(bce_dag_create(cc, (uint32_t)tasks_.tasks.size(), tasks_.tasks.data(), tasks_.prio.data(), &dag_), "Clock(dataflow DAG)");
+    if (!dag_) createDag(&dag_);
     if (hi > lo) {
         ck(bce_dag_run(cc, dag_, hi - lo, stride_, lo * stride_), "Clock(dataflow run)");
         ++stats_.sublaunches;
@@ -856,7 +873,7 @@ void Circuit::clockDataflowVerify() {
     for (size_t l = 0; l < levels_.size(); ++l) plainRound(l);
     check_report_ = bce_check_report{};
     if (!vdag_) {   // a DAG of its own: the verify-off runs keep theirs
-        ck(bce_dag_create(cc, (uint32_t)tasks_.tasks.size(), tasks_.tasks.data(), tasks_.prio.data(), &vdag_), "Clock(dataflow DAG)");
+        createDag(&vdag_);
         task_checks_ = sched::task_checks(tasks_, units_, net_);
         ck(bce_dag_set_checks(cc, vdag_, (uint32_t)task_checks_.tasks.size(), task_checks_.tasks.data(), 1), "Clock(check list)");
     }

@@ -131,8 +131,8 @@ public:
     // of two refreshed ciphertexts.  The XOR's two temporaries hold other ciphertexts than the reference lowering's; every
     // netlist wire holds the same BIT.  Before SetInput; not together with setXorFast.  Active with batched launches on the
     // bootstrap-depth schedule, without gate sharding and without a host-side verify pass (setVerify without
-    // setDeviceVerify); otherwise the reference lowering runs exactly as without it.  The dataflow kernel has no pairs:
-    // with setDataflow on top the step schedule runs (dataflowActive() is false).
+    // setDeviceVerify); otherwise the reference lowering runs exactly as without it.  With setDataflow on top the step
+    // schedule runs (dataflowActive() is false) unless setDataflowShared is on too: then the dataflow kernel runs pair tasks.
     // The lowering is fixed at SetInput, and so is whether it is active: setBatched, setRelevel, setDeviceVerify and
     // setVerify rebuild the units and the schedule when they change xorSharedActive() before SetInput, and are refused
     // (std::logic_error, BCE_ERR_STATE; the flag keeps its value) when they would change it after.  The pool is laid out
@@ -160,6 +160,13 @@ public:
     // (bce_dag_set_checks), between a bootstrap and the release of its consumers.
     void setDataflow(bool b);
     bool getDataflow() const { return dataflow_; }
+    // opt-in on top of setDataflow and setXorShared: keep the shared lowering on the dataflow schedule.  The task list is
+    // then lowered in XorMode::Shared (per XOR a pair task writing the XOR's own two temporaries and an AND of the two: two
+    // tasks instead of three, the same slot stride) and goes to the engine through bce_dag_create_pairs; dataflowActive()
+    // and xorSharedActive() are both true.  Verify mode on the device checks the AND tasks.  Without it the two options
+    // together run the step schedule, as they always did.  Before SetInput (std::logic_error after, if it would change).
+    void setDataflowShared(bool b);
+    bool getDataflowShared() const { return dataflow_shared_; }
     // opt-in: replay the bootstrap-depth schedule's launches as ONE hipGraph per Clock() (bce_plan_run) instead of one
     // host call per step.  Same ciphertexts.  Not with gate sharding (the per-step exchange is a host call) or verify mode on
     // the host path (setDeviceVerify: the checks are captured with the steps).
@@ -177,7 +184,7 @@ public:
     bool getDeviceVerify() const { return device_verify_; }
     bool deviceVerifyActive() const { return device_verify_ && verify_flag && encrypted_flag && cc && batched_ && relevel_ && !gateSharded(); }
     const bce_check_report& checkReport() const { return check_report_; }   // of the last Clock() on the device path
-    bool dataflowActive() const { return dataflow_ && !xorSharedActive() && cc && (!verify_flag || deviceVerifyActive()) && !gateSharded() && bce_dag_supported(cc) && !tasks_.tasks.empty(); }
+    bool dataflowActive() const { return dataflow_ && (!xorSharedActive() || dataflow_shared_) && cc && (!verify_flag || deviceVerifyActive()) && !gateSharded() && bce_dag_supported(cc) && !tasks_.tasks.empty(); }
     const std::vector<bce_gate_desc>& dataflowTasks() const { return tasks_.tasks; }
     const std::vector<uint8_t>& dataflowPriorities() const { return tasks_.prio; }
     bool getBalance() const { return balance_; }
@@ -287,7 +294,11 @@ private:
     bool balance_ = true;
     uint32_t cap_lone_ = 0, cap_full_ = 0;
     std::pair<uint32_t, uint32_t> launchCapacity() const;   // (lone, full) of the launch staircase: set by the caller, else the engine's
-    bool dataflow_ = false;
+    bool dataflow_ = false, dataflow_shared_ = false;
+    bool tasksHavePairs() const { return units_mode_ == sched::XorMode::Shared; }          // of a task list lowered from units_
+    bool tasksExist() const { return !tasksHavePairs() || dataflow_shared_; }              // the dataflow schedule has a list for units_
+    sched::TaskList lowerTasks() const { return sched::lower_tasks(units_, net_.n_wires, tasksHavePairs()); }
+    void createDag(bce_dag** g);               // bce_dag_create, or bce_dag_create_pairs for a list with pairs
     bce_dag* dag_ = nullptr;
     bool graph_ = false;
     bce_plan* plan_ = nullptr;                 // the schedule's descriptors resident on the device (and its captured graph)

@@ -90,6 +90,7 @@ int bce_circuit_set_shard_locality(bce_circuit* h, int on) { return guarded(h, [
 uint64_t bce_circuit_plan_hash(const bce_circuit* h) { return h ? h->c.planHash() : 0; }
 int bce_circuit_get_encrypt_mode(const bce_circuit* h) { return h ? h->c.getEncryptMode() : -1; }
 int bce_circuit_set_dataflow(bce_circuit* h, int on) { return guarded(h, [&] { h->c.setDataflow(on != 0); }); }
+int bce_circuit_set_dataflow_shared(bce_circuit* h, int on) { return guarded(h, [&] { h->c.setDataflowShared(on != 0); }); }
 int bce_circuit_dataflow_active(const bce_circuit* h) { return h && h->c.dataflowActive() ? 1 : 0; }
 int bce_circuit_set_graph(bce_circuit* h, int on) { return guarded(h, [&] { h->c.setGraph(on != 0); }); }
 int bce_circuit_graph_active(const bce_circuit* h) { return h && h->c.graphActive() ? 1 : 0; }

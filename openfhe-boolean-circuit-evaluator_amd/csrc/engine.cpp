@@ -1542,23 +1542,31 @@ int bce_dag_set_expected(bce_ctx* c, bce_dag* g, uint32_t instances, const uint8
     return BCE_OK;
 }
 
-int bce_dag_create(bce_ctx* c, uint32_t n_tasks, const bce_gate_desc* tasks, const uint8_t* prio, bce_dag** out) {
+}  // extern "C" (the shared body of the two constructors is C++)
+
+// bce_dag_create and bce_dag_create_pairs.  allow_pairs: a pair descriptor (BCE_PAIR) is a task with two outputs, `out` and
+// `out + 1`; both count for max_slot, the SSA rule and writer[], so a later task that reads either output -- or both, like
+// the AND of a shared XOR -- depends on the pair once (p1 == p0 collapses).  One bootstrap, one item, one level of depth.
+static int dag_create(bce_ctx* c, uint32_t n_tasks, const bce_gate_desc* tasks, const uint8_t* prio, bce_dag** out, bool allow_pairs) {
     if (!c || !out) return BCE_ERR_ARG;
     *out = nullptr;
     if (!tasks || n_tasks == 0) return c->fail(BCE_ERR_ARG, "bce_dag_create: empty task list");
     if (!dag_kernel_available(c->P)) return c->fail(BCE_ERR_UNSUPPORTED, "bce_dag_create: no persistent kernel for this parameter class (N = 1024, 4 gadget digits, Q < 2^28; N = 2048, Q < 2^39, AP with the folded key)");
     if ((u64)n_tasks >= (1ull << 31)) return c->fail(BCE_ERR_ARG, "bce_dag_create: too many tasks");
     HIP_TRY(c, hipSetDevice(c->device));
-    u32 max_slot = 0;
+    u64 max_slot64 = 0;
     for (u32 i = 0; i < n_tasks; ++i) {
         const bce_gate_desc& g = tasks[i];
-        if (pair_kind(g.op) > 0) return c->fail(BCE_ERR_UNSUPPORTED, "bce_dag_create: task %u is a pair descriptor (BCE_PAIR): the dataflow kernel runs one tail per bootstrap; use bce_eval_gates or a bce_plan", i);
-        const bool two = g.op <= BCE_XNOR_FAST;
+        const bool pair = pair_kind(g.op) > 0;
+        if (pair && !allow_pairs) return c->fail(BCE_ERR_UNSUPPORTED, "bce_dag_create: task %u is a pair descriptor (BCE_PAIR): bce_dag_create_pairs takes them, or use bce_eval_gates or a bce_plan", i);
+        const bool two = pair || g.op <= BCE_XNOR_FAST;
         if (!two && g.op != BCE_OP_REFRESH) return c->fail(BCE_ERR_ARG, "bce_dag_create: task %u is not a bootstrapped gate (op %u)", i, g.op);
         if (prio && prio[i] >= kDagQueues) return c->fail(BCE_ERR_ARG, "bce_dag_create: task %u has priority class %u (0..%u)", i, prio[i], kDagQueues - 1);
-        max_slot = std::max(max_slot, std::max(g.in0, g.out));
-        if (two) max_slot = std::max(max_slot, g.in1);
+        max_slot64 = std::max<u64>(max_slot64, std::max<u64>(g.in0, (u64)g.out + pair));   // a pair writes out and out + 1
+        if (two) max_slot64 = std::max<u64>(max_slot64, g.in1);
     }
+    if (max_slot64 >= 0xFFFFFFFFull) return c->fail(BCE_ERR_POOL, "bce_dag_create: slot %llu outside any pool", (unsigned long long)max_slot64);
+    const u32 max_slot = (u32)max_slot64;
     // producers by slot: SSA form is required (a slot is written once and read only by later tasks), so that the order in
     // which the device runs independent tasks cannot matter
     std::vector<int32_t> writer((size_t)max_slot + 1, -1);
@@ -1568,13 +1576,16 @@ int bce_dag_create(bce_ctx* c, uint32_t n_tasks, const bce_gate_desc* tasks, con
     u32 depth = 0;
     for (u32 i = 0; i < n_tasks; ++i) {
         const bce_gate_desc& g = tasks[i];
-        const bool two = g.op <= BCE_XNOR_FAST;
+        const bool pair = pair_kind(g.op) > 0;
+        const bool two = pair || g.op <= BCE_XNOR_FAST;
         p0[i] = writer[g.in0]; read_before[g.in0] = 1;
         if (two) { p1[i] = writer[g.in1]; read_before[g.in1] = 1; }
         if (p1[i] == p0[i]) p1[i] = -1;
-        if (writer[g.out] >= 0) return c->fail(BCE_ERR_ARG, "bce_dag_create: slot %u is written by tasks %d and %u (SSA form required)", g.out, writer[g.out], i);
-        if (read_before[g.out]) return c->fail(BCE_ERR_ARG, "bce_dag_create: task %u writes slot %u that an earlier task (or itself) reads", i, g.out);
-        writer[g.out] = (int32_t)i;
+        for (u32 o = g.out, last = g.out + (pair ? 1u : 0u); o <= last; ++o) {
+            if (writer[o] >= 0) return c->fail(BCE_ERR_ARG, "bce_dag_create: slot %u is written by tasks %d and %u (SSA form required)", o, writer[o], i);
+            if (read_before[o]) return c->fail(BCE_ERR_ARG, "bce_dag_create: task %u writes slot %u that an earlier task (or itself) reads", i, o);
+            writer[o] = (int32_t)i;
+        }
         for (int32_t p : {p0[i], p1[i]})
             if (p >= 0) { ++dep[i]; ++cons_cnt[p + 1]; lvl[i] = std::max(lvl[i], lvl[p] + 1); }
         depth = std::max(depth, lvl[i]);
@@ -1612,6 +1623,15 @@ int bce_dag_create(bce_ctx* c, uint32_t n_tasks, const bce_gate_desc* tasks, con
     HIP_TRY(c, g->d_params.alloc(1));
     *out = g.release();
     return BCE_OK;
+}
+
+extern "C" {
+
+int bce_dag_create(bce_ctx* c, uint32_t n_tasks, const bce_gate_desc* tasks, const uint8_t* prio, bce_dag** out) {
+    return dag_create(c, n_tasks, tasks, prio, out, false);
+}
+int bce_dag_create_pairs(bce_ctx* c, uint32_t n_tasks, const bce_gate_desc* tasks, const uint8_t* prio, bce_dag** out) {
+    return dag_create(c, n_tasks, tasks, prio, out, true);
 }
 
 int bce_dag_debug_block_task(bce_dag* g, uint32_t t) {

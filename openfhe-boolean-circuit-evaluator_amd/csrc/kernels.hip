@@ -1522,14 +1522,15 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
         if (P.ksk_u16) fused_tail<uint16_t, T>(P, acc, rowidx, red, outp, boot, dbg_lweN, dbg_ks);
         else fused_tail<u32, T>(P, acc, rowidx, red, outp, boot, dbg_lweN, dbg_ks);
         // a pair descriptor (BCE_PAIR) runs the tail a second time, on X^e * acc, into slot out + 1 (debug rows: a second block
-        // of gridDim.x rows); the branch is workgroup-uniform, the barrier frees rowidx / red.  The dataflow kernel has no pairs.
-        if constexpr (!PERSIST) {
-            if (g.op >> 8) {
-                __syncthreads();
-                const u32 e = pair_rotation(P, g.op), row = boot + gridDim.x;
-                if (P.ksk_u16) fused_tail<uint16_t, T>(P, acc, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, e);
-                else fused_tail<u32, T>(P, acc, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, e);
-            }
+        // of gridDim.x rows); the branch is workgroup-uniform, the barrier frees rowidx / red.  The dataflow kernel runs the
+        // same pass (bce_dag_create_pairs): g came from D.tasks[t] through the constant address space, so the test is scalar,
+        // and both rows are stored before the worker's drain / barrier / release (dag_worker).  Its debug pointers are null:
+        // the row index stays `boot`.
+        if (g.op >> 8) {
+            __syncthreads();
+            const u32 e = pair_rotation(P, g.op), row = PERSIST ? boot : boot + gridDim.x;
+            if (P.ksk_u16) fused_tail<uint16_t, T>(P, acc, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, e);
+            else fused_tail<u32, T>(P, acc, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, e);
         }
     }
 }

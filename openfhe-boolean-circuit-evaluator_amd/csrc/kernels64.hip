@@ -1424,14 +1424,13 @@ __device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g,
         const u64* coef = reinterpret_cast<const u64*>(acc);
         if (P.ksk_u16) fused_tail<uint16_t, T>(P, coef, rowidx, red, outp, boot, dbg_lweN, dbg_ks);
         else fused_tail<u32, T>(P, coef, rowidx, red, outp, boot, dbg_lweN, dbg_ks);
-        // a pair descriptor (BCE_PAIR): second tail pass on X^e * acc into slot out + 1, as in lat_bootstrap (kernels.hip)
-        if constexpr (!PERSIST) {
-            if (g.op >> 8) {
-                __syncthreads();
-                const u32 e = pair_rotation(P, g.op), row = boot + gridDim.x;
-                if (P.ksk_u16) fused_tail<uint16_t, T>(P, coef, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, e);
-                else fused_tail<u32, T>(P, coef, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, e);
-            }
+        // a pair descriptor (BCE_PAIR): second tail pass on X^e * acc into slot out + 1, as in lat_bootstrap (kernels.hip);
+        // in the dataflow kernel too (scalar test of the task's word, debug pointers null: the row index stays `boot`)
+        if (g.op >> 8) {
+            __syncthreads();
+            const u32 e = pair_rotation(P, g.op), row = PERSIST ? boot : boot + gridDim.x;
+            if (P.ksk_u16) fused_tail<uint16_t, T>(P, coef, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, e);
+            else fused_tail<u32, T>(P, coef, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, e);
         }
     }
 }

@@ -264,7 +264,8 @@ StepPlan lower_steps(const Units& S, const Dag& dag, uint32_t rank, uint32_t wor
 
 // Tasks = the units in topological order.  Priority class of a task = slack of its unit (ALAP step - ASAP step) with the
 // bounds 0, 1, 2 (0,2,8 and 1,4,16 are 2-3 % slower on AES at K = 4 / 8): the device pulls the critical path first.
-TaskList lower_tasks(const Units& S, uint32_t n_wires) {
+// A shared unit (pairs = true) is two tasks: the pair into the XOR's own two adjacent temporaries, then the AND of the two.
+TaskList lower_tasks(const Units& S, uint32_t n_wires, bool pairs) {
     TaskList T;
     uint32_t nx = 0;
     for (size_t i = 0; i < S.units.size(); ++i) {
@@ -272,12 +273,14 @@ TaskList lower_tasks(const Units& S, uint32_t n_wires) {
         const uint32_t slack = S.alap[i] - u.asap;
         const uint8_t pc = slack == 0 ? 0 : slack <= 1 ? 1 : slack <= 2 ? 2 : 3;
         if (u.lat == 1) { T.tasks.push_back(u.d); T.prio.push_back(pc); continue; }
-        if (u.shared) throw std::logic_error("lower_tasks: the dataflow schedule has no shared XORs");
+        if (u.shared && !pairs) throw std::logic_error("lower_tasks: shared XORs need the task list with pairs (bce_dag_create_pairs)");
         bce_gate_desc x[3];
-        xor_lower(u.d, n_wires + 2 * nx, n_wires + 2 * nx + 1, x);
+        const uint32_t n = u.shared ? 2 : 3;
+        if (u.shared) xor_lower_shared(u.d, n_wires + 2 * nx, x);
+        else xor_lower(u.d, n_wires + 2 * nx, n_wires + 2 * nx + 1, x);
         ++nx;
-        T.tasks.insert(T.tasks.end(), x, x + 3);
-        T.prio.insert(T.prio.end(), 3, pc);
+        T.tasks.insert(T.tasks.end(), x, x + n);
+        T.prio.insert(T.prio.end(), n, pc);
     }
     T.stride = n_wires + 2 * nx;
     return T;

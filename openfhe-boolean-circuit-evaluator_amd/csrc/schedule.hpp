@@ -69,8 +69,10 @@ struct StepPlan {
 };
 StepPlan lower_steps(const Units&, const Dag&, uint32_t rank, uint32_t world, uint64_t K);   // world 1 = not sharded
 struct TaskList { std::vector<bce_gate_desc> tasks; std::vector<uint8_t> prio; uint32_t stride = 0; };
-TaskList lower_tasks(const Units&, uint32_t n_wires);   // SSA: every XOR owns its temporaries; prio = slack class (no shared XORs:
-                                                         // the dataflow kernel runs one tail per bootstrap)
+// SSA: every XOR owns its two temporaries n_wires + 2 x, n_wires + 2 x + 1; prio = slack class of the unit.  pairs: the caller
+// hands the list to bce_dag_create_pairs, so a shared XOR is lowered to its pair descriptor and its AND (two tasks, both of the
+// unit's class); without it shared units are refused (std::logic_error), because bce_dag_create refuses pair descriptors
+TaskList lower_tasks(const Units&, uint32_t n_wires, bool pairs = false);
 // every step reads only what earlier steps wrote (or received), every XOR temporary is read one step after it is written; a
 // pair descriptor writes two adjacent temporaries
 bool check(const StepPlan&, const Dag&, uint32_t rank, uint32_t world, std::string* why = nullptr);
