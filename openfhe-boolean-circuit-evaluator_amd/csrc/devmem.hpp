@@ -1,4 +1,4 @@
-// devmem.hpp -- the owners of the host side's device and pinned memory (engine.cpp): DevBuf, one allocation with its
+// devmem.hpp -- the owners of the host side's device and pinned memory (engine.cpp, engine_plan.cpp, engine_dag.cpp): DevBuf, one allocation with its
 // capacity, and StagedUpload, a pinned-to-device upload with its event.  Move-only; no HIP call except where a comment says
 // so (tests/integration/devmem_selftest.cpp counts them against stand-ins of the runtime).
 #pragma once

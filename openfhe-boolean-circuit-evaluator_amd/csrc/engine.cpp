@@ -5,30 +5,27 @@
 // (src/circuit.cpp:506,800) and the per-gate EvalBinGate / EvalNOT calls
 // (src/gate.cpp:112,133,172,198-202), the latter batched per ready frontier.
 // There is no CPU compute path here: without a HIP device every call fails loudly.
-#include <hip/hip_runtime_api.h>
+// This file: the context (derivation, tables, keys, pool and LWE I/O), one frontier of gates, timing and the debug entry
+// points.  The schedules built on it live in engine_plan.cpp (bce_plan, bce_check_*) and engine_dag.cpp (bce_dag).
 #include <sys/random.h>
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
-#include <mutex>
-#include <unordered_set>
-#include <string>
-#include <vector>
 
 #include "../../include/bce_circuit.h"
-#include "../../include/bce_gpu.h"
-#include "devmem.hpp"
+#include "desc.hpp"
+#include "engine_internal.hpp"
 #include "fwd_mfma.hpp"
 #include "host_math.hpp"
-#include "kernels.hpp"
 #include "keygen.hpp"
 #include "prng.hpp"
 
 using namespace bce;
+
+std::mutex bce::g_live_mu;
+std::unordered_set<const bce_ctx*> bce::g_live;
 
 static_assert(sizeof(bce_check_report) == 48 && sizeof(bce_check_entry) == 24, "layout of the check structs (include/bce_gpu.h; the kernel writes them)");
 
@@ -51,8 +48,6 @@ const ParamRow kParamTable[] = {
     {29, 4096, 990, 2048, 1u << 14, 1u << 7, 1u << 8, 46},   // STD256_OPT
 };
 
-struct EventPair { hipEvent_t a, b; int kind; };
-
 // 32 bytes from the operating system's entropy pool (getrandom, then /dev/urandom).  There is no fixed
 // fallback value: a context that cannot get entropy fails to draw keys / encryption randomness.
 bool os_entropy(uint8_t out[32]) {
@@ -69,107 +64,6 @@ bool os_entropy(uint8_t out[32]) {
     std::fclose(f);
     return n == 32;
 }
-
-}  // namespace
-
-// Contexts that exist, and the schedules each one owns.  A bce_plan / bce_dag belongs to the context it was created on: the
-// context's destruction releases whatever its callers left behind, and bce_plan_destroy / bce_dag_destroy on a context that is
-// already gone (a Circuit destroyed after its engine) is a no-op instead of a read of freed memory.
-struct bce_plan;
-struct bce_dag;
-namespace {
-std::mutex g_live_mu;
-std::unordered_set<const bce_ctx*> g_live;
-}  // namespace
-
-struct bce_ctx {
-    std::unordered_set<bce_plan*> plans;
-    std::unordered_set<bce_dag*> dags;
-    // parameters
-    u32 n = 0, N = 0, logN = 0;
-    u64 q = 0, Q = 0, qKS = 0, psi = 0;
-    u32 baseKS = 0, dKS = 0, baseG = 0, gBits = 0, dG = 0, baseR = 0, dR = 0;
-    int method = 0, device = 0;
-    std::string err;
-
-    // every device / pinned buffer below owns its memory (devmem.hpp); bce_ctx_destroy keeps what has an order
-    hipStream_t stream = nullptr;
-    DevParams P{};   // its pointers mirror the owning members below, set where those are allocated
-    // device tables / keys
-    DevBuf<uint2> d_twf;
-    DevBuf<u32> d_fwd_mfma, d_psi, d_psi_r2, d_xcd_gate;
-    DevBuf<char> d_bsk;          // u32 words (Q < 2^28) or u64 words (is64)
-    DevBuf<ulonglong2> d_tw64;
-    DevBuf<double2> d_tw64d;      // (w, w / Q) for the double-precision formulation
-    bool is64 = false;
-    size_t wbytes = 4;
-    DevBuf<char> d_ksk;
-    u64 bsk_polys = 0;
-    bool have_keys = false;
-    // host secrets
-    std::vector<int32_t> s, z;
-    uint8_t seed[32] = {0};       // key-generation seed (bce_keygen); zero after bce_import_keys
-    // Encryption randomness is independent of the key seed: drawn from OS entropy when the context is created,
-    // consumed through a per-context counter that only moves forward, so no (a, e) pair is ever reused.
-    // bce_set_encrypt_seed() switches to the deterministic, caller-indexed streams of the parity tests.
-    uint8_t enc_seed[32] = {0};
-    bool enc_seed_ok = false, enc_deterministic = false;
-    uint64_t enc_counter = 0;
-    void* rccl_comm = nullptr;   // ncclComm_t of the in-library all-gather (rccl_xchg.cpp), if enabled
-    // pool
-    DevBuf<u32> d_pool;
-    u32 pool_slots = 0;
-    // work buffers
-    DevBuf<char> d_acc;             // accumulators of the largest launch so far
-    DevBuf<u64> d_tail_partial;     // partial key-switch sums (kernels.hip, k_tail_gather)
-    bool events_on = true;                 // per-launch HIP events (bce_timing_set_events): off = counters only, no event packets between dependent kernels
-    DevBuf<u32> d_io;               // staging of bce_lwe_read for scattered slots (device gather + one pinned copy)
-    DevBuf<u32, true> h_io;
-    static constexpr int kRing = 4;
-    StagedUpload ring[kRing];       // descriptor lists of the launches in flight (stage_descs)
-    int ring_pos = 0;
-    // verify mode on the device (bce_check_*): the LWE secret as int8[n padded to 64] (uploaded wherever `s` is set), the
-    // report block followed by the mismatch log, and the staging pair of bce_check_slots (slot list + expected bits)
-    DevBuf<int8_t> d_s8;            // allocated once per context, never reallocated: captured plans point to it
-    DevBuf<char> d_check_mem;
-    bce_check_report* d_check() const { return reinterpret_cast<bce_check_report*>(d_check_mem.get()); }
-    bce_check_entry* d_check_log() const { return reinterpret_cast<bce_check_entry*>(d_check_mem.get() + sizeof(bce_check_report)); }
-    StagedUpload chk_stage;
-    // timing
-    std::vector<EventPair> pending, free_events;
-    bce_timing timing{};
-    // dependency-driven runs (bce_dag_*): device copy of P, knobs, and the status words of runs not yet checked
-    DevBuf<DevParams> d_P;
-    int dag_wg_per_cu = 0, dag_placement = 1;
-    uint32_t dag_lazy_us = 20, dag_stall_ms = 4000;
-    struct DagStatus { uint32_t abort, done, lazy_waits, pad; uint64_t busy_ticks, wait_ticks, gate_ticks; };
-    static constexpr int kDagRuns = 32;
-    DevBuf<DagStatus, true> h_dag_status;     // pinned, kDagRuns entries
-    struct DagStage { DevParams P; DagParams D; };
-    DevBuf<DagStage, true> h_dag_stage;       // pinned, kDagRuns entries: sources of the stream-ordered parameter uploads
-    uint64_t dag_expected[kDagRuns] = {0};
-    int dag_wps_used[kDagRuns] = {0};
-    int dag_pending = 0;
-    uint64_t dag_last[7] = {0, 0, 0, 0, 0, 0, 0};
-
-    int fail(int code, const char* fmt, ...) {
-        char buf[512];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof buf, fmt, ap);
-        va_end(ap);
-        err = buf;
-        return code;
-    }
-};
-
-#define HIP_TRY(ctx, call)                                                                      \
-    do {                                                                                        \
-        hipError_t e_ = (call);                                                                 \
-        if (e_ != hipSuccess) return (ctx)->fail(BCE_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
-
-namespace {
 
 // development / parity knobs that default to on: NAME=0 switches the feature off
 bool env_off(const char* name) {
@@ -359,13 +253,6 @@ int derive_ctx(bce_ctx* c, u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 
     return BCE_OK;
 }
 
-// device copy of a host vector in a buffer that is still empty (one element at least)
-template <class T>
-hipError_t upload_vector(DevBuf<T>& dst, const std::vector<T>& v) {
-    const hipError_t e = dst.alloc(std::max<size_t>(1, v.size()));
-    return e != hipSuccess ? e : hipMemcpy(dst.get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-}
-
 // Second half: stream, and the tables of derive_ctx on the device
 int upload_ctx(bce_ctx* c, const HostTables& T) {
     DevParams& P = c->P;
@@ -490,24 +377,6 @@ int upload_secret(bce_ctx* c) {
     return BCE_OK;
 }
 
-// report block + mismatch log of the device-side checks: one allocation per context, zeroed
-int ensure_check(bce_ctx* c) {
-    if (c->d_check_mem.get()) return BCE_OK;
-    const size_t bytes = sizeof(bce_check_report) + (size_t)kCheckLogCap * sizeof(bce_check_entry);
-    DevBuf<char> mem;
-    HIP_TRY(c, mem.alloc(bytes));
-    if (hipMemset(mem.get(), 0, bytes) != hipSuccess) return c->fail(BCE_ERR_HIP, "hipMemset(check report) failed");
-    c->d_check_mem = std::move(mem);
-    return BCE_OK;
-}
-
-// accumulators for `boots` bootstraps: at least doubled when they grow, after the work in flight
-int ensure_acc(bce_ctx* c, size_t boots) {
-    const size_t need = boots * 2 * c->N * c->wbytes;
-    HIP_TRY(c, c->d_acc.grow(need, std::max(need, 2 * c->d_acc.capacity()), c->stream));
-    return BCE_OK;
-}
-
 // Stage a descriptor list into the next ring slot (1,024 descriptors at least).  The caller launches the kernel that reads
 // descs_of(slot) and then marks the slot: its event must follow that kernel, not just the copy.
 int stage_descs(bce_ctx* c, const bce_gate_desc* d, size_t n, StagedUpload** slot) {
@@ -522,19 +391,6 @@ int stage_descs(bce_ctx* c, const bce_gate_desc* d, size_t n, StagedUpload** slo
 }
 const bce_gate_desc* descs_of(const StagedUpload* slot) { return static_cast<const bce_gate_desc*>(slot->device()); }
 
-EventPair get_events(bce_ctx* c, int kind) {
-    EventPair p;
-    if (!c->free_events.empty()) {
-        p = c->free_events.back();
-        c->free_events.pop_back();
-    } else {
-        hipEventCreate(&p.a);
-        hipEventCreate(&p.b);
-    }
-    p.kind = kind;
-    return p;
-}
-
 void drain_timing(bce_ctx* c) {
     for (auto& p : c->pending) {
         float ms = 0.f;
@@ -545,13 +401,6 @@ void drain_timing(bce_ctx* c) {
         c->free_events.push_back(p);
     }
     c->pending.clear();
-}
-// after a launch: keeps the list of event pairs short
-int drain_if_long(bce_ctx* c) {
-    if (c->pending.size() <= 4096) return BCE_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    drain_timing(c);
-    return BCE_OK;
 }
 
 // uint64_t words of the ABI <-> words in device memory: u64 as they are (wide), u32 through a staging vector.  The
@@ -658,17 +507,125 @@ int check_dag_runs(bce_ctx* c) {
     return rc;
 }
 
+int eval_impl(bce_ctx* c, u32 n_desc, const bce_gate_desc* descs, u32 instances, u32 slot_stride, u64* dbg_acc,
+              u64* dbg_lweN, u64* dbg_ks) {
+    if (n_desc == 0 || instances == 0) return BCE_OK;
+    if (!descs) return c->fail(BCE_ERR_ARG, "null descriptor list");
+    if (const int rc = need_keys(c)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    std::vector<bce_gate_desc> boot, unary;
+    boot.reserve(n_desc);
+    const u64 max_slot = (u64)(instances - 1) * slot_stride;
+    u32 n_pairs = 0;
+    for (u32 i = 0; i < n_desc; ++i) {
+        const bce_gate_desc& g = descs[i];
+        const DescKind k = desc_kind(g.op);
+        if (k.cls == DescClass::None) return c->fail(BCE_ERR_ARG, "descriptor %u: unknown op %u", i, g.op);
+        n_pairs += k.pair();
+        const u64 hi = top_slot(g, k);
+        if (hi + max_slot >= c->pool_slots) return c->fail(BCE_ERR_POOL, "descriptor %u: slot %llu outside the pool (%u slots)", i, (unsigned long long)(hi + max_slot), c->pool_slots);
+        (k.boot() ? boot : unary).push_back(g);
+    }
+    if (!boot.empty()) {
+        const size_t nb = boot.size() * (size_t)instances;
+        int rc = ensure_acc(c, nb);
+        if (rc) return rc;
+        StagedUpload* slot = nullptr;
+        rc = stage_descs(c, boot.data(), boot.size(), &slot);
+        if (rc) return rc;
+        DevBuf<u32> d_lweN, d_ks;
+        // staged outputs of a launch with pairs: the kernels write the second outputs to a second block of nb rows
+        const size_t dbg_rows = n_pairs ? 2 * nb : nb;
+        if (dbg_lweN) HIP_TRY(c, d_lweN.alloc(dbg_rows * (c->N + 1)));
+        if (dbg_ks) HIP_TRY(c, d_ks.alloc(dbg_rows * (c->n + 1)));
+        rc = launch_bootstraps(c, descs_of(slot), (u32)boot.size(), instances, slot_stride, c->d_acc.get(), d_lweN.get(), d_ks.get(), true, nullptr, n_pairs != 0);
+        if (rc) return rc;
+        slot->mark(c->stream);
+        if (dbg_acc || dbg_lweN || dbg_ks) {
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            if (dbg_acc && (rc = words_from_device(c, dbg_acc, c->d_acc.get(), nb * 2 * c->N, c->is64))) return rc;
+            if (dbg_lweN && (rc = words_from_device(c, dbg_lweN, d_lweN.get(), nb * (c->N + 1), false))) return rc;
+            if (dbg_ks && (rc = words_from_device(c, dbg_ks, d_ks.get(), nb * (c->n + 1), false))) return rc;
+            // ... which the caller gets packed, in descriptor order, from row nb on (bce_debug_eval_stages: one instance)
+            if (n_pairs) {
+                auto pack = [&](u64* dst, const u32* dev, size_t w) {   // the second block in one copy, then packed on the host
+                    std::vector<u64> second(nb * w);
+                    const int e = words_from_device(c, second.data(), dev + nb * w, nb * w, false);
+                    for (size_t i = 0, row = nb; !e && i < nb; ++i)
+                        if (pair_kind(boot[i].op) > 0) std::copy_n(second.data() + i * w, w, dst + row++ * w);
+                    return e;
+                };
+                if (dbg_lweN) rc = pack(dbg_lweN, d_lweN.get(), c->N + 1);
+                if (dbg_ks && !rc) rc = pack(dbg_ks, d_ks.get(), c->n + 1);
+            }
+            if (rc) return rc;
+        }
+        if (const int rc2 = drain_if_long(c)) return rc2;
+    }
+    if (!unary.empty()) {
+        StagedUpload* slot = nullptr;
+        int rc = stage_descs(c, unary.data(), unary.size(), &slot);
+        if (rc) return rc;
+        HIP_TRY(c, launch_lwe_unary(c->P, descs_of(slot), (u32)unary.size(), instances, slot_stride, c->stream));
+        slot->mark(c->stream);
+    }
+    return BCE_OK;
+}
+
+}  // namespace
+
+// ---- shared with engine_plan.cpp and engine_dag.cpp (engine_internal.hpp) ----------------------------------------------
+namespace bce {
+
+// report block + mismatch log of the device-side checks: one allocation per context, zeroed
+int ensure_check(bce_ctx* c) {
+    if (c->d_check_mem.get()) return BCE_OK;
+    const size_t bytes = sizeof(bce_check_report) + (size_t)kCheckLogCap * sizeof(bce_check_entry);
+    DevBuf<char> mem;
+    HIP_TRY(c, mem.alloc(bytes));
+    if (hipMemset(mem.get(), 0, bytes) != hipSuccess) return c->fail(BCE_ERR_HIP, "hipMemset(check report) failed");
+    c->d_check_mem = std::move(mem);
+    return BCE_OK;
+}
+
+// accumulators for `boots` bootstraps: at least doubled when they grow, after the work in flight
+int ensure_acc(bce_ctx* c, size_t boots) {
+    const size_t need = boots * 2 * c->N * c->wbytes;
+    HIP_TRY(c, c->d_acc.grow(need, std::max(need, 2 * c->d_acc.capacity()), c->stream));
+    return BCE_OK;
+}
+
+EventPair get_events(bce_ctx* c, int kind) {
+    EventPair p;
+    if (!c->free_events.empty()) {
+        p = c->free_events.back();
+        c->free_events.pop_back();
+    } else {
+        hipEventCreate(&p.a);
+        hipEventCreate(&p.b);
+    }
+    p.kind = kind;
+    return p;
+}
+
+// after a launch: keeps the list of event pairs short
+int drain_if_long(bce_ctx* c) {
+    if (c->pending.size() <= 4096) return BCE_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    drain_timing(c);
+    return BCE_OK;
+}
+
 int sync_stream(bce_ctx* c) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return check_dag_runs(c);
 }
 
-// The descriptor word `op`: bits 0..7 the gate, bits 8..15 the second gate + 1 of a pair (BCE_PAIR, two different gates of
-// OR, AND, NOR, NAND on one blind rotation).  0: plain descriptor, 1: legal pair, -1: anything else in the high bits.
-int pair_kind(u32 op) {
-    if (op <= 0xFFu) return 0;
-    const u32 lo = op & 0xFFu, hi = op >> 8;
-    return (lo <= BCE_NAND && hi >= 1 && hi - 1 <= BCE_NAND && hi - 1 != lo) ? 1 : -1;
+// the expected bits of a check list are messages; `who` names the call in the message
+int expected_are_messages(bce_ctx* c, const char* who, const uint8_t* expect, size_t count) {
+    for (size_t i = 0; i < count; ++i)
+        if (expect[i] > 3) return c->fail(BCE_ERR_ARG, "%s: expect[%zu] = %u is not a message (0..3)", who, i, expect[i]);
+    return BCE_OK;
 }
 
 // One frontier of bootstrapped gates whose descriptors already sit on the device: blind rotation (+ the tail kernels
@@ -676,7 +633,7 @@ int pair_kind(u32 op) {
 // bce_timing; untimed (stream capture of bce_plan_run): launches only, *fused_out says whether the tail was fused.
 // pairs: at least one descriptor is a pair (its second tail pass runs in the fused epilogue or as a second tail launch).
 int launch_bootstraps(bce_ctx* c, const bce_gate_desc* dd, u32 n, u32 instances, u32 slot_stride, void* d_acc,
-                      u32* d_lweN, u32* d_ks, bool timed, bool* fused_out, bool pairs, u64* d_partial = nullptr) {
+                      u32* d_lweN, u32* d_ks, bool timed, bool* fused_out, bool pairs, u64* d_partial) {
     const size_t nb = (size_t)n * instances;
     int kid = 0;
     bool tail_fused = false;
@@ -728,75 +685,7 @@ int launch_bootstraps(bce_ctx* c, const bce_gate_desc* dd, u32 n, u32 instances,
     return BCE_OK;
 }
 
-int eval_impl(bce_ctx* c, u32 n_desc, const bce_gate_desc* descs, u32 instances, u32 slot_stride, u64* dbg_acc,
-              u64* dbg_lweN, u64* dbg_ks) {
-    if (n_desc == 0 || instances == 0) return BCE_OK;
-    if (!descs) return c->fail(BCE_ERR_ARG, "null descriptor list");
-    if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "bce_keygen / bce_import_keys has not been called");
-    HIP_TRY(c, hipSetDevice(c->device));
-    std::vector<bce_gate_desc> boot, unary;
-    boot.reserve(n_desc);
-    const u64 max_slot = (u64)(instances - 1) * slot_stride;
-    u32 n_pairs = 0;
-    for (u32 i = 0; i < n_desc; ++i) {
-        const bce_gate_desc& g = descs[i];
-        const int pair = pair_kind(g.op);
-        const bool is_boot = pair > 0 || g.op <= BCE_XNOR_FAST || g.op == BCE_OP_REFRESH;
-        const bool is_unary = g.op == BCE_OP_NOT || g.op == BCE_OP_COPY;
-        if (!is_boot && !is_unary) return c->fail(BCE_ERR_ARG, "descriptor %u: unknown op %u", i, g.op);
-        n_pairs += pair > 0;
-        u64 hi = std::max<u64>(g.in0, (u64)g.out + (pair > 0));   // a pair writes out and out + 1
-        if (pair > 0 || g.op <= BCE_XNOR_FAST) hi = std::max<u64>(hi, g.in1);
-        if (hi + max_slot >= c->pool_slots) return c->fail(BCE_ERR_POOL, "descriptor %u: slot %llu outside the pool (%u slots)", i, (unsigned long long)(hi + max_slot), c->pool_slots);
-        (is_boot ? boot : unary).push_back(g);
-    }
-    if (!boot.empty()) {
-        const size_t nb = boot.size() * (size_t)instances;
-        int rc = ensure_acc(c, nb);
-        if (rc) return rc;
-        StagedUpload* slot = nullptr;
-        rc = stage_descs(c, boot.data(), boot.size(), &slot);
-        if (rc) return rc;
-        DevBuf<u32> d_lweN, d_ks;
-        // staged outputs of a launch with pairs: the kernels write the second outputs to a second block of nb rows
-        const size_t dbg_rows = n_pairs ? 2 * nb : nb;
-        if (dbg_lweN) HIP_TRY(c, d_lweN.alloc(dbg_rows * (c->N + 1)));
-        if (dbg_ks) HIP_TRY(c, d_ks.alloc(dbg_rows * (c->n + 1)));
-        rc = launch_bootstraps(c, descs_of(slot), (u32)boot.size(), instances, slot_stride, c->d_acc.get(), d_lweN.get(), d_ks.get(), true, nullptr, n_pairs != 0);
-        if (rc) return rc;
-        slot->mark(c->stream);
-        if (dbg_acc || dbg_lweN || dbg_ks) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            if (dbg_acc && (rc = words_from_device(c, dbg_acc, c->d_acc.get(), nb * 2 * c->N, c->is64))) return rc;
-            if (dbg_lweN && (rc = words_from_device(c, dbg_lweN, d_lweN.get(), nb * (c->N + 1), false))) return rc;
-            if (dbg_ks && (rc = words_from_device(c, dbg_ks, d_ks.get(), nb * (c->n + 1), false))) return rc;
-            // ... which the caller gets packed, in descriptor order, from row nb on (bce_debug_eval_stages: one instance)
-            if (n_pairs) {
-                auto pack = [&](u64* dst, const u32* dev, size_t w) {   // the second block in one copy, then packed on the host
-                    std::vector<u64> second(nb * w);
-                    const int e = words_from_device(c, second.data(), dev + nb * w, nb * w, false);
-                    for (size_t i = 0, row = nb; !e && i < nb; ++i)
-                        if (pair_kind(boot[i].op) > 0) std::copy_n(second.data() + i * w, w, dst + row++ * w);
-                    return e;
-                };
-                if (dbg_lweN) rc = pack(dbg_lweN, d_lweN.get(), c->N + 1);
-                if (dbg_ks && !rc) rc = pack(dbg_ks, d_ks.get(), c->n + 1);
-            }
-            if (rc) return rc;
-        }
-        if (const int rc2 = drain_if_long(c)) return rc2;
-    }
-    if (!unary.empty()) {
-        StagedUpload* slot = nullptr;
-        int rc = stage_descs(c, unary.data(), unary.size(), &slot);
-        if (rc) return rc;
-        HIP_TRY(c, launch_lwe_unary(c->P, descs_of(slot), (u32)unary.size(), instances, slot_stride, c->stream));
-        slot->mark(c->stream);
-    }
-    return BCE_OK;
-}
-
-}  // namespace
+}  // namespace bce
 
 extern "C" {
 
@@ -812,10 +701,32 @@ int bce_ctx_create_custom(uint32_t n, uint32_t N, uint64_t q, uint64_t Q, uint64
     return build_ctx(n, N, q, Q, qKS, baseKS, baseG, baseR, method, device, out);
 }
 
+int bce_rccl_shutdown(bce_ctx* c);   // rccl_xchg.cpp
+
+// The order is kept in this body rather than in the order of bce_ctx's members: the stream is synchronised first, every
+// buffer of the context and of its schedules is released by its owner (devmem.hpp), the stream is destroyed last.
+void bce_ctx_destroy(bce_ctx* c) {
+    if (!c) return;
+    hipSetDevice(c->device);
+    if (c->stream) hipStreamSynchronize(c->stream);
+    if (c->rccl_comm) bce_rccl_shutdown(c);
+    drain_timing(c);
+    {   // schedules nobody destroyed: theirs callers' handles die with the context
+        std::unordered_set<bce_plan*> plans;
+        std::unordered_set<bce_dag*> dags;
+        { std::lock_guard<std::mutex> lk(g_live_mu); plans.swap(c->plans); dags.swap(c->dags); g_live.erase(c); }
+        for (bce_plan* p : plans) delete_leftover(p);
+        for (bce_dag* g : dags) delete_leftover(g);
+    }
+    for (auto& p : c->free_events) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
+    const hipStream_t stream = c->stream;
+    delete c;
+    if (stream) hipStreamDestroy(stream);
+}
+
 hipStream_t bce_internal_stream(bce_ctx* c) { return c->stream; }
 void** bce_internal_comm_slot(bce_ctx* c) { return &c->rccl_comm; }
 int bce_internal_device(bce_ctx* c) { return c->device; }
-int bce_rccl_shutdown(bce_ctx* c);
 
 int bce_set_error(bce_ctx* c, int code, const char* msg) {  // for the other translation units of the library (keyfile.cpp)
     if (c) c->err = msg ? msg : "";
@@ -1142,593 +1053,6 @@ int bce_synchronize(bce_ctx* c) {
     return sync_stream(c);
 }
 
-// ---- a whole step schedule at once (include/bce_gpu.h, "a whole step schedule at once") ---------------------------
-}  // extern "C" (the object below is C++)
-
-struct bce_plan {
-    std::vector<u32> off, cnt;                 // step s = descriptors [off[s], off[s] + cnt[s])
-    std::vector<uint8_t> pairs;                // step s holds at least one pair descriptor (BCE_PAIR)
-    u32 instances = 0, slot_stride = 0, slot_base = 0;
-    u32 max_step = 0;                          // descriptors of the largest step
-    u64 boots_per_run = 0;
-    DevBuf<bce_gate_desc> d_descs;             // all steps, resident
-    // captured form (bce_plan_run): its own accumulator / partial-sum scratch, so that nothing the graph points to is ever
-    // re-allocated by other calls on the context.  d_descs, d_acc, d_partial, d_chk_slots and `expect` never move while
-    // `exec` exists: each is allocated once, the check lists only after bce_plan_set_checks dropped the capture.
-    DevBuf<char> d_acc;
-    DevBuf<u64> d_partial;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    u64 fused_launches = 0;
-    // the captured kernels hold the context's device pointers and kernel choices by value: what they were at capture
-    const void* cap_ptrs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    u32 cap_flags[3] = {0, 0, 0};
-    // device-side checks (bce_plan_set_checks): step s checks the slots [chk_off[s], chk_off[s] + chk_cnt[s]) of d_chk_slots
-    // against the same range of every instance's row of `expect` ([instances][chk_total], one fixed buffer: the captured
-    // graph points into it; bce_plan_set_expected refills it through its pinned half)
-    std::vector<u32> chk_off, chk_cnt;
-    u32 chk_total = 0;
-    int chk_repair = 0;
-    bool expected_set = false;
-    DevBuf<u32> d_chk_slots;
-    StagedUpload expect;
-    const uint8_t* d_expect() const { return static_cast<const uint8_t*>(expect.device()); }
-
-    void drop_capture() {
-        if (exec) { hipGraphExecDestroy(exec); exec = nullptr; }
-        if (graph) { hipGraphDestroy(graph); graph = nullptr; }
-    }
-    ~bce_plan() { drop_capture(); }   // the graph goes before the buffers it points to
-};
-
-namespace {
-bool plan_capture_is_current(const bce_ctx* c, const bce_plan* p) {
-    const void* now[6] = {c->P.pool, c->P.bsk, c->P.bsk64, c->P.ksk, c->P.tw_f, c->P.psi_tab};
-    const u32 flags[3] = {c->P.variant, c->P.fuse_tail, c->P.fold};
-    return std::memcmp(now, p->cap_ptrs, sizeof now) == 0 && std::memcmp(flags, p->cap_flags, sizeof flags) == 0;
-}
-void plan_free_checks(bce_plan* p) {
-    p->d_chk_slots.reset();
-    p->expect.reset();
-    p->chk_off.clear(); p->chk_cnt.clear();
-    p->chk_total = 0; p->expected_set = false;
-}
-// the checks of plan step s, after its kernels (no allocation, no synchronisation: also runs under stream capture)
-int plan_check_step(bce_ctx* c, const bce_plan* p, size_t s) {
-    if (!p->chk_total || !p->chk_cnt[s]) return BCE_OK;
-    HIP_TRY(c, launch_lwe_check(c->P, c->d_s8.get(), p->d_chk_slots.get() + p->chk_off[s], p->d_expect() + p->chk_off[s], p->chk_cnt[s], p->chk_total,
-                                p->instances, p->slot_stride, p->chk_repair, (u32)s, c->d_check(), c->d_check_log(), c->stream));
-    return BCE_OK;
-}
-// the expected bits of a check list are messages; `who` names the call in the message
-int expected_are_messages(bce_ctx* c, const char* who, const uint8_t* expect, size_t count) {
-    for (size_t i = 0; i < count; ++i)
-        if (expect[i] > 3) return c->fail(BCE_ERR_ARG, "%s: expect[%zu] = %u is not a message (0..3)", who, i, expect[i]);
-    return BCE_OK;
-}
-// every checked slot, at every instance (span = the distance of the last instance's copy), lies in the pool
-int checked_slots_in_pool(bce_ctx* c, const char* who, const uint32_t* slots, u64 count, u64 span) {
-    for (u64 i = 0; i < count; ++i)
-        if (slots[i] + span >= c->pool_slots) return c->fail(BCE_ERR_POOL, "%s: check %llu: slot %llu outside the pool (%u slots)", who, (unsigned long long)i, (unsigned long long)(slots[i] + span), c->pool_slots);
-    return BCE_OK;
-}
-int plan_checks_ready(bce_ctx* c, const bce_plan* p, const char* who) {
-    if (p->chk_total && !p->expected_set) return c->fail(BCE_ERR_STATE, "%s: the plan has checks but bce_plan_set_expected has not been called", who);
-    return BCE_OK;
-}
-}  // namespace
-
-extern "C" {
-
-void bce_plan_destroy(bce_ctx* c, bce_plan* p) {
-    if (!p || !c) return;
-    {   // a context that no longer exists took its plans along (bce_ctx_destroy): nothing left to free, nothing to touch
-        std::lock_guard<std::mutex> lk(g_live_mu);
-        if (!g_live.count(c) || !c->plans.erase(p)) return;
-    }
-    hipSetDevice(c->device);
-    if (c->stream) hipStreamSynchronize(c->stream);
-    delete p;
-}
-
-int bce_plan_create(bce_ctx* c, uint32_t n_steps, const uint32_t* step_sizes, const bce_gate_desc* descs, uint32_t instances,
-                    uint32_t slot_stride, uint32_t slot_base, bce_plan** out) {
-    if (!c || !out) return BCE_ERR_ARG;
-    *out = nullptr;
-    if (!step_sizes || !descs || n_steps == 0 || instances == 0) return c->fail(BCE_ERR_ARG, "bce_plan_create: empty schedule");
-    if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "bce_keygen / bce_import_keys has not been called");
-    HIP_TRY(c, hipSetDevice(c->device));
-    struct Deleter { bce_ctx* c; void operator()(bce_plan* p) const { bce_plan_destroy(c, p); } };
-    std::unique_ptr<bce_plan, Deleter> p(new bce_plan, Deleter{c});
-    { std::lock_guard<std::mutex> lk(g_live_mu); c->plans.insert(p.get()); }
-    p->instances = instances; p->slot_stride = slot_stride; p->slot_base = slot_base;
-    u64 total = 0;
-    for (u32 s = 0; s < n_steps; ++s) {
-        if (step_sizes[s] == 0) return c->fail(BCE_ERR_ARG, "bce_plan_create: step %u is empty", s);
-        p->off.push_back((u32)total); p->cnt.push_back(step_sizes[s]);
-        p->max_step = std::max(p->max_step, step_sizes[s]);
-        total += step_sizes[s];
-        if (total >= (1ull << 31)) return c->fail(BCE_ERR_ARG, "bce_plan_create: too many descriptors");
-    }
-    std::vector<bce_gate_desc> d(descs, descs + total);
-    const u64 span = (u64)slot_base + (u64)(instances - 1) * slot_stride;
-    p->pairs.assign(n_steps, 0);
-    u32 step = 0;
-    for (u64 i = 0; i < total; ++i) {
-        bce_gate_desc& g = d[i];
-        const int pair = pair_kind(g.op);
-        const bool two = pair > 0 || g.op <= BCE_XNOR_FAST;
-        if (!two && g.op != BCE_OP_REFRESH) return c->fail(BCE_ERR_ARG, "bce_plan_create: descriptor %llu is not a bootstrapped gate (op %u)", (unsigned long long)i, g.op);
-        if (pair > 0) {
-            while (step + 1 < n_steps && i >= (u64)p->off[step + 1]) ++step;
-            p->pairs[step] = 1;
-        }
-        u64 hi = std::max<u64>(g.in0, (u64)g.out + (pair > 0));   // a pair writes out and out + 1
-        if (two) hi = std::max<u64>(hi, g.in1);
-        if (hi + span >= c->pool_slots) return c->fail(BCE_ERR_POOL, "bce_plan_create: descriptor %llu: slot %llu outside the pool (%u slots)", (unsigned long long)i, (unsigned long long)(hi + span), c->pool_slots);
-        g.in0 += slot_base; g.in1 += slot_base; g.out += slot_base;
-    }
-    p->boots_per_run = total * instances;
-    HIP_TRY(c, upload_vector(p->d_descs, d));
-    *out = p.release();
-    return BCE_OK;
-}
-
-int bce_plan_run_step(bce_ctx* c, bce_plan* p, uint32_t step) {
-    if (!c || !p) return BCE_ERR_ARG;
-    if (step >= p->cnt.size()) return c->fail(BCE_ERR_ARG, "bce_plan_run_step: step %u of %zu", step, p->cnt.size());
-    if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "bce_keygen / bce_import_keys has not been called");
-    if (const int rc = plan_checks_ready(c, p, "bce_plan_run_step")) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int rc = ensure_acc(c, (size_t)p->cnt[step] * p->instances);
-    if (rc) return rc;
-    const int rc2 = launch_bootstraps(c, p->d_descs.get() + p->off[step], p->cnt[step], p->instances, p->slot_stride, c->d_acc.get(), nullptr, nullptr, true, nullptr, p->pairs[step] != 0);
-    if (rc2) return rc2;
-    if (const int rc3 = plan_check_step(c, p, step)) return rc3;
-    return drain_if_long(c);
-}
-
-int bce_plan_run(bce_ctx* c, bce_plan* p) {
-    if (!c || !p) return BCE_ERR_ARG;
-    if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "bce_keygen / bce_import_keys has not been called");
-    if (const int rc = plan_checks_ready(c, p, "bce_plan_run")) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (p->exec && !plan_capture_is_current(c, p)) {
-        // the pool grew (bce_pool_reserve) or keys were re-imported since the capture: the graph's kernel arguments are stale
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        p->drop_capture();
-    }
-    if (!p->exec) {
-        // scratch of the captured launches, sized for the largest step
-        const size_t nb = (size_t)p->max_step * p->instances;
-        if (!p->d_acc.get()) HIP_TRY(c, p->d_acc.alloc(nb * 2 * c->N * c->wbytes));
-        if (!p->d_partial.get()) HIP_TRY(c, p->d_partial.alloc(std::max<size_t>(1, tail_partial_words(c->P, (u32)nb))));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        // relaxed mode: the launchers set kernel attributes (dynamic LDS size) while the stream is capturing
-        HIP_TRY(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
-        int rc = BCE_OK;
-        u64 fused = 0;
-        for (size_t s = 0; s < p->cnt.size() && rc == BCE_OK; ++s) {
-            bool f = false;
-            rc = launch_bootstraps(c, p->d_descs.get() + p->off[s], p->cnt[s], p->instances, p->slot_stride, p->d_acc.get(), nullptr, nullptr, false, &f, p->pairs[s] != 0, p->d_partial.get());
-            fused += f ? 1 : 0;
-            if (rc == BCE_OK) rc = plan_check_step(c, p, s);
-        }
-        hipGraph_t g = nullptr;
-        const hipError_t e = hipStreamEndCapture(c->stream, &g);   // always end the capture, also after a failed launch
-        if (rc != BCE_OK) { if (g) hipGraphDestroy(g); return rc; }
-        if (e != hipSuccess || !g) return c->fail(BCE_ERR_HIP, "bce_plan_run: stream capture failed: %s", hipGetErrorString(e));
-        p->graph = g;
-        p->fused_launches = fused;
-        { const void* now[6] = {c->P.pool, c->P.bsk, c->P.bsk64, c->P.ksk, c->P.tw_f, c->P.psi_tab}; std::memcpy(p->cap_ptrs, now, sizeof now); }
-        p->cap_flags[0] = c->P.variant; p->cap_flags[1] = c->P.fuse_tail; p->cap_flags[2] = c->P.fold;
-        const hipError_t e2 = hipGraphInstantiate(&p->exec, p->graph, nullptr, nullptr, 0);
-        if (e2 != hipSuccess) { p->exec = nullptr; return c->fail(BCE_ERR_HIP, "bce_plan_run: hipGraphInstantiate: %s", hipGetErrorString(e2)); }
-    }
-    EventPair e0 = get_events(c, BCE_BR_GRAPH);
-    hipEventRecord(e0.a, c->stream);
-    HIP_TRY(c, hipGraphLaunch(p->exec, c->stream));
-    hipEventRecord(e0.b, c->stream);
-    c->pending.push_back(e0);
-    c->timing.br_launches[BCE_BR_GRAPH] += p->cnt.size();
-    c->timing.br_bootstraps[BCE_BR_GRAPH] += p->boots_per_run;
-    c->timing.blind_rotate_launches += p->cnt.size();
-    c->timing.bootstraps += p->boots_per_run;
-    c->timing.fused_tail_launches += p->fused_launches;
-    return drain_if_long(c);
-}
-
-// ---- verify mode on the device (include/bce_gpu.h, "verify mode on the device") -----------------------------------
-int bce_check_slots(bce_ctx* c, uint32_t count, const uint32_t* slots, const uint8_t* expect, uint32_t instances,
-                    uint32_t slot_stride, int repair, uint32_t tag) {
-    if (!c) return BCE_ERR_ARG;
-    if (!slots || !expect) return c->fail(BCE_ERR_ARG, "bce_check_slots: null pointer");
-    if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "bce_keygen / bce_import_keys has not been called");
-    if (count == 0 || instances == 0) return BCE_OK;
-    const u64 items = (u64)count * instances;
-    if (items > (1ull << 31)) return c->fail(BCE_ERR_ARG, "bce_check_slots: too many checks");
-    if (const int rc = checked_slots_in_pool(c, "bce_check_slots", slots, count, (u64)(instances - 1) * slot_stride)) return rc;
-    if (const int rc = expected_are_messages(c, "bce_check_slots", expect, items)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (const int rc = ensure_check(c)) return rc;
-    const size_t slot_bytes = (size_t)count * sizeof(u32), bytes = slot_bytes + items;
-    StagedUpload& st = c->chk_stage;   // slot list, then expected bits: 64 KiB at least, grown after the work in flight
-    HIP_TRY(c, st.reserve(bytes, std::max(bytes, (size_t)1 << 16), c->stream));
-    std::memcpy(st.host(), slots, slot_bytes);
-    std::memcpy(static_cast<char*>(st.host()) + slot_bytes, expect, items);
-    HIP_TRY(c, st.send(bytes, c->stream));
-    const char* dev = static_cast<const char*>(st.device());
-    HIP_TRY(c, launch_lwe_check(c->P, c->d_s8.get(), reinterpret_cast<const u32*>(dev), reinterpret_cast<const uint8_t*>(dev + slot_bytes),
-                                count, count, instances, slot_stride, repair, tag, c->d_check(), c->d_check_log(), c->stream));
-    return BCE_OK;
-}
-
-int bce_plan_set_checks(bce_ctx* c, bce_plan* p, const uint32_t* check_sizes, const uint32_t* slots, int repair) {
-    if (!c || !p) return BCE_ERR_ARG;
-    if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "bce_keygen / bce_import_keys has not been called");
-    const size_t n_steps = p->cnt.size();
-    u64 total = 0;
-    for (size_t s = 0; check_sizes && s < n_steps; ++s) total += check_sizes[s];
-    if (total && !slots) return c->fail(BCE_ERR_ARG, "bce_plan_set_checks: null slot list");
-    if (total * p->instances > (1ull << 31)) return c->fail(BCE_ERR_ARG, "bce_plan_set_checks: too many checks");
-    const u64 span = (u64)p->slot_base + (u64)(p->instances - 1) * p->slot_stride;   // the span rule of bce_plan_create
-    if (const int rc = checked_slots_in_pool(c, "bce_plan_set_checks", slots, total, span)) return rc;
-    std::vector<u32> shifted(total);
-    for (u64 i = 0; i < total; ++i) shifted[i] = slots[i] + p->slot_base;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    p->drop_capture();   // its launches would miss (or still hold) the old lists: captured again at the next bce_plan_run
-    plan_free_checks(p);
-    if (total == 0) return BCE_OK;
-    if (const int rc = ensure_check(c)) return rc;
-    for (size_t s = 0, at = 0; s < n_steps; ++s) { p->chk_off.push_back((u32)at); p->chk_cnt.push_back(check_sizes[s]); at += check_sizes[s]; }
-    const size_t ebytes = (size_t)total * p->instances;
-    HIP_TRY(c, upload_vector(p->d_chk_slots, shifted));
-    HIP_TRY(c, p->expect.reserve(ebytes, ebytes, nullptr));   // once, here: the next capture points into it
-    p->chk_total = (u32)total;
-    p->chk_repair = repair;
-    return BCE_OK;
-}
-
-int bce_plan_set_expected(bce_ctx* c, bce_plan* p, const uint8_t* expect) {
-    if (!c || !p) return BCE_ERR_ARG;
-    if (!expect) return c->fail(BCE_ERR_ARG, "bce_plan_set_expected: null pointer");
-    if (!p->chk_total) return c->fail(BCE_ERR_STATE, "bce_plan_set_expected: the plan has no checks (bce_plan_set_checks)");
-    const size_t bytes = (size_t)p->chk_total * p->instances;
-    if (const int rc = expected_are_messages(c, "bce_plan_set_expected", expect, bytes)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, p->expect.reserve(bytes, bytes, nullptr));   // its size since bce_plan_set_checks: only waits for the last upload
-    std::memcpy(p->expect.host(), expect, bytes);
-    HIP_TRY(c, p->expect.send(bytes, c->stream));
-    p->expected_set = true;
-    return BCE_OK;
-}
-
-int bce_check_reset(bce_ctx* c) {
-    if (!c) return BCE_ERR_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (const int rc = ensure_check(c)) return rc;
-    HIP_TRY(c, hipMemsetAsync(c->d_check(), 0, sizeof(bce_check_report), c->stream));
-    return BCE_OK;
-}
-
-int bce_check_get(bce_ctx* c, bce_check_report* out, bce_check_entry* log, uint32_t log_cap) {
-    if (!c) return BCE_ERR_ARG;
-    if (!out || (log_cap && !log)) return c->fail(BCE_ERR_ARG, "bce_check_get: null pointer");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (const int rc = ensure_check(c)) return rc;
-    if (const int rc = sync_stream(c)) return rc;
-    HIP_TRY(c, hipMemcpy(out, c->d_check(), sizeof *out, hipMemcpyDeviceToHost));
-    out->log_count = std::min<u32>(out->log_count, kCheckLogCap);   // the device counter goes on counting past the log's end
-    const u32 n = std::min(out->log_count, log_cap);
-    if (n) HIP_TRY(c, hipMemcpy(log, c->d_check_log(), (size_t)n * sizeof *log, hipMemcpyDeviceToHost));
-    return BCE_OK;
-}
-
-// ---- dependency-driven evaluation (include/bce_gpu.h, "the hot path, dependency-driven") --------------------------
-}  // extern "C" (the object below is C++)
-
-struct bce_dag {
-    u32 n_tasks = 0;
-    u32 max_slot = 0;
-    u32 qcount[kDagQueues] = {0, 0, 0, 0};        // tasks per priority class
-    u32 depth = 0;                                 // longest producer chain (bootstraps)
-    std::vector<u32> h_dep_init;
-    std::vector<u32> init_items;                   // initially ready tasks by class
-    u32 init_off[kDagQueues + 1] = {0, 0, 0, 0, 0};
-    // immutable device arrays
-    DevBuf<bce_gate_desc> d_tasks;
-    DevBuf<u32> d_cons_off, d_cons, d_dep_init, d_init;
-    DevBuf<uint8_t> d_qid;
-    // per-run state, grown on demand to the exact size, after the work in flight
-    DevBuf<u32> d_dep;
-    DevBuf<u32> d_slots[kDagQueues];
-    DevBuf<u32> d_ctl;
-    DevBuf<DagParams> d_params;
-    // verify mode (bce_dag_set_checks / bce_dag_set_expected): check number + 1 per task, and the expected bits of the next
-    // run(s) with their pinned staging buffer, grown on demand
-    u32 n_checks = 0;
-    int chk_repair = 0;
-    DevBuf<u32> d_chk_of_task;
-    StagedUpload expect;
-    u32 expect_instances = 0;                      // the instance count the expected bits were set for, 0 = not set
-};
-
-extern "C" {
-
-int bce_dag_supported(const bce_ctx* c) { return c && dag_kernel_available(c->P) ? 1 : 0; }
-
-int bce_dag_set_limits(bce_ctx* c, int workgroups_per_cu, int placement, uint32_t lazy_us, uint32_t stall_ms) {
-    if (!c || workgroups_per_cu < 0 || workgroups_per_cu > 2) return c ? c->fail(BCE_ERR_ARG, "workgroups_per_cu must be 0, 1 or 2") : BCE_ERR_ARG;
-    if (stall_ms == 0 || stall_ms > 40000) return c->fail(BCE_ERR_ARG, "stall_ms must be in 1..40000");
-    c->dag_wg_per_cu = workgroups_per_cu; c->dag_placement = placement ? 1 : 0; c->dag_lazy_us = lazy_us; c->dag_stall_ms = stall_ms;
-    return BCE_OK;
-}
-
-int bce_dag_last_run(bce_ctx* c, uint64_t out[7]) {
-    if (!c || !out) return BCE_ERR_ARG;
-    for (int i = 0; i < 7; ++i) out[i] = c->dag_last[i];
-    return BCE_OK;
-}
-
-void bce_dag_destroy(bce_ctx* c, bce_dag* g) {
-    if (!g || !c) return;
-    {
-        std::lock_guard<std::mutex> lk(g_live_mu);
-        if (!g_live.count(c) || !c->dags.erase(g)) return;
-    }
-    hipSetDevice(c->device);
-    if (c->stream) hipStreamSynchronize(c->stream);
-    delete g;
-}
-
-// (Here, where bce_plan and bce_dag are complete.)  The order is kept in this body rather than in the order of bce_ctx's
-// members: the stream is synchronised first, every buffer of the context and of its schedules is released by its owner
-// (devmem.hpp), the stream is destroyed last.
-void bce_ctx_destroy(bce_ctx* c) {
-    if (!c) return;
-    hipSetDevice(c->device);
-    if (c->stream) hipStreamSynchronize(c->stream);
-    if (c->rccl_comm) bce_rccl_shutdown(c);
-    drain_timing(c);
-    {   // schedules nobody destroyed: theirs callers' handles die with the context
-        std::unordered_set<bce_plan*> plans;
-        std::unordered_set<bce_dag*> dags;
-        { std::lock_guard<std::mutex> lk(g_live_mu); plans.swap(c->plans); dags.swap(c->dags); g_live.erase(c); }
-        for (bce_plan* p : plans) delete p;
-        for (bce_dag* g : dags) delete g;
-    }
-    for (auto& p : c->free_events) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
-    const hipStream_t stream = c->stream;
-    delete c;
-    if (stream) hipStreamDestroy(stream);
-}
-
-int bce_dag_set_checks(bce_ctx* c, bce_dag* g, uint32_t n_checks, const uint32_t* tasks, int repair) {
-    if (!c || !g) return BCE_ERR_ARG;
-    if (n_checks && !tasks) return c->fail(BCE_ERR_ARG, "bce_dag_set_checks: null task list");
-    if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "bce_keygen / bce_import_keys has not been called");
-    std::vector<u32> of_task(g->n_tasks, 0);
-    for (u32 i = 0; i < n_checks; ++i) {
-        if (tasks[i] >= g->n_tasks) return c->fail(BCE_ERR_ARG, "bce_dag_set_checks: check %u names task %u of %u", i, tasks[i], g->n_tasks);
-        if (of_task[tasks[i]]) return c->fail(BCE_ERR_ARG, "bce_dag_set_checks: task %u is listed twice (checks %u and %u)", tasks[i], of_task[tasks[i]] - 1, i);
-        of_task[tasks[i]] = i + 1;
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // a run in flight may still read the old list
-    g->n_checks = 0; g->expect_instances = 0;      // new lists need their own expected bits
-    if (n_checks == 0) return BCE_OK;              // detached: bce_dag_run passes no list to the kernel
-    if (const int rc = ensure_check(c)) return rc;
-    if (!g->d_chk_of_task.get()) HIP_TRY(c, g->d_chk_of_task.alloc(g->n_tasks));
-    HIP_TRY(c, hipMemcpy(g->d_chk_of_task.get(), of_task.data(), (size_t)g->n_tasks * sizeof(u32), hipMemcpyHostToDevice));
-    g->n_checks = n_checks;
-    g->chk_repair = repair ? 1 : 0;
-    return BCE_OK;
-}
-
-int bce_dag_set_expected(bce_ctx* c, bce_dag* g, uint32_t instances, const uint8_t* expect) {
-    if (!c || !g) return BCE_ERR_ARG;
-    if (!expect) return c->fail(BCE_ERR_ARG, "bce_dag_set_expected: null pointer");
-    if (instances == 0) return c->fail(BCE_ERR_ARG, "bce_dag_set_expected: no instances");
-    if (!g->n_checks) return c->fail(BCE_ERR_STATE, "bce_dag_set_expected: the DAG has no checks (bce_dag_set_checks)");
-    const size_t bytes = (size_t)g->n_checks * instances;
-    if (const int rc = expected_are_messages(c, "bce_dag_set_expected", expect, bytes)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (bytes > g->expect.capacity()) g->expect_instances = 0;   // the old bits go with the old buffer
-    HIP_TRY(c, g->expect.reserve(bytes, bytes, c->stream));       // exact size; a run in flight may still read the old buffer
-    std::memcpy(g->expect.host(), expect, bytes);
-    HIP_TRY(c, g->expect.send(bytes, c->stream));
-    g->expect_instances = instances;
-    return BCE_OK;
-}
-
-}  // extern "C" (the shared body of the two constructors is C++)
-
-// bce_dag_create and bce_dag_create_pairs.  allow_pairs: a pair descriptor (BCE_PAIR) is a task with two outputs, `out` and
-// `out + 1`; both count for max_slot, the SSA rule and writer[], so a later task that reads either output -- or both, like
-// the AND of a shared XOR -- depends on the pair once (p1 == p0 collapses).  One bootstrap, one item, one level of depth.
-static int dag_create(bce_ctx* c, uint32_t n_tasks, const bce_gate_desc* tasks, const uint8_t* prio, bce_dag** out, bool allow_pairs) {
-    if (!c || !out) return BCE_ERR_ARG;
-    *out = nullptr;
-    if (!tasks || n_tasks == 0) return c->fail(BCE_ERR_ARG, "bce_dag_create: empty task list");
-    if (!dag_kernel_available(c->P)) return c->fail(BCE_ERR_UNSUPPORTED, "bce_dag_create: no persistent kernel for this parameter class (N = 1024, 4 gadget digits, Q < 2^28; N = 2048, Q < 2^39, AP with the folded key)");
-    if ((u64)n_tasks >= (1ull << 31)) return c->fail(BCE_ERR_ARG, "bce_dag_create: too many tasks");
-    HIP_TRY(c, hipSetDevice(c->device));
-    u64 max_slot64 = 0;
-    for (u32 i = 0; i < n_tasks; ++i) {
-        const bce_gate_desc& g = tasks[i];
-        const bool pair = pair_kind(g.op) > 0;
-        if (pair && !allow_pairs) return c->fail(BCE_ERR_UNSUPPORTED, "bce_dag_create: task %u is a pair descriptor (BCE_PAIR): bce_dag_create_pairs takes them, or use bce_eval_gates or a bce_plan", i);
-        const bool two = pair || g.op <= BCE_XNOR_FAST;
-        if (!two && g.op != BCE_OP_REFRESH) return c->fail(BCE_ERR_ARG, "bce_dag_create: task %u is not a bootstrapped gate (op %u)", i, g.op);
-        if (prio && prio[i] >= kDagQueues) return c->fail(BCE_ERR_ARG, "bce_dag_create: task %u has priority class %u (0..%u)", i, prio[i], kDagQueues - 1);
-        max_slot64 = std::max<u64>(max_slot64, std::max<u64>(g.in0, (u64)g.out + pair));   // a pair writes out and out + 1
-        if (two) max_slot64 = std::max<u64>(max_slot64, g.in1);
-    }
-    if (max_slot64 >= 0xFFFFFFFFull) return c->fail(BCE_ERR_POOL, "bce_dag_create: slot %llu outside any pool", (unsigned long long)max_slot64);
-    const u32 max_slot = (u32)max_slot64;
-    // producers by slot: SSA form is required (a slot is written once and read only by later tasks), so that the order in
-    // which the device runs independent tasks cannot matter
-    std::vector<int32_t> writer((size_t)max_slot + 1, -1);
-    std::vector<uint8_t> read_before((size_t)max_slot + 1, 0);
-    std::vector<u32> dep(n_tasks, 0), lvl(n_tasks, 1), cons_cnt(n_tasks + 1, 0);
-    std::vector<int32_t> p0(n_tasks, -1), p1(n_tasks, -1);
-    u32 depth = 0;
-    for (u32 i = 0; i < n_tasks; ++i) {
-        const bce_gate_desc& g = tasks[i];
-        const bool pair = pair_kind(g.op) > 0;
-        const bool two = pair || g.op <= BCE_XNOR_FAST;
-        p0[i] = writer[g.in0]; read_before[g.in0] = 1;
-        if (two) { p1[i] = writer[g.in1]; read_before[g.in1] = 1; }
-        if (p1[i] == p0[i]) p1[i] = -1;
-        for (u32 o = g.out, last = g.out + (pair ? 1u : 0u); o <= last; ++o) {
-            if (writer[o] >= 0) return c->fail(BCE_ERR_ARG, "bce_dag_create: slot %u is written by tasks %d and %u (SSA form required)", o, writer[o], i);
-            if (read_before[o]) return c->fail(BCE_ERR_ARG, "bce_dag_create: task %u writes slot %u that an earlier task (or itself) reads", i, o);
-            writer[o] = (int32_t)i;
-        }
-        for (int32_t p : {p0[i], p1[i]})
-            if (p >= 0) { ++dep[i]; ++cons_cnt[p + 1]; lvl[i] = std::max(lvl[i], lvl[p] + 1); }
-        depth = std::max(depth, lvl[i]);
-    }
-    std::vector<u32> cons_off(cons_cnt);
-    for (u32 i = 0; i < n_tasks; ++i) cons_off[i + 1] += cons_off[i];
-    std::vector<u32> cons(std::max<u32>(1, cons_off[n_tasks])), fill(cons_off.begin(), cons_off.end() - 1);
-    for (u32 i = 0; i < n_tasks; ++i)
-        for (int32_t p : {p0[i], p1[i]}) if (p >= 0) cons[fill[p]++] = i;
-    std::vector<uint8_t> qid(n_tasks, 0);
-    if (prio) qid.assign(prio, prio + n_tasks);
-
-    struct Deleter { bce_ctx* c; void operator()(bce_dag* g) const { bce_dag_destroy(c, g); } };
-    std::unique_ptr<bce_dag, Deleter> g(new bce_dag, Deleter{c});
-    { std::lock_guard<std::mutex> lk(g_live_mu); c->dags.insert(g.get()); }
-    g->n_tasks = n_tasks; g->max_slot = max_slot; g->depth = depth; g->h_dep_init = dep;
-    for (u32 q = 0; q < kDagQueues; ++q) {
-        g->init_off[q] = (u32)g->init_items.size();
-        for (u32 i = 0; i < n_tasks; ++i) {
-            if (qid[i] != q) continue;
-            ++g->qcount[q];
-            if (dep[i] == 0) g->init_items.push_back(i);
-        }
-    }
-    g->init_off[kDagQueues] = (u32)g->init_items.size();
-    if (g->init_items.empty()) return c->fail(BCE_ERR_ARG, "bce_dag_create: no task is ready at the start");
-    HIP_TRY(c, g->d_tasks.alloc(n_tasks));
-    HIP_TRY(c, hipMemcpy(g->d_tasks.get(), tasks, (size_t)n_tasks * sizeof(bce_gate_desc), hipMemcpyHostToDevice));
-    HIP_TRY(c, upload_vector(g->d_cons_off, cons_off));
-    HIP_TRY(c, upload_vector(g->d_cons, cons));
-    HIP_TRY(c, upload_vector(g->d_dep_init, dep));
-    HIP_TRY(c, upload_vector(g->d_init, g->init_items));
-    HIP_TRY(c, upload_vector(g->d_qid, qid));
-    HIP_TRY(c, g->d_ctl.alloc(kDagCtlWords));
-    HIP_TRY(c, g->d_params.alloc(1));
-    *out = g.release();
-    return BCE_OK;
-}
-
-extern "C" {
-
-int bce_dag_create(bce_ctx* c, uint32_t n_tasks, const bce_gate_desc* tasks, const uint8_t* prio, bce_dag** out) {
-    return dag_create(c, n_tasks, tasks, prio, out, false);
-}
-int bce_dag_create_pairs(bce_ctx* c, uint32_t n_tasks, const bce_gate_desc* tasks, const uint8_t* prio, bce_dag** out) {
-    return dag_create(c, n_tasks, tasks, prio, out, true);
-}
-
-int bce_dag_debug_block_task(bce_dag* g, uint32_t t) {
-    if (!g || t >= g->n_tasks) return BCE_ERR_ARG;
-    g->h_dep_init[t] += 1;
-    return hipMemcpy(g->d_dep_init.get(), g->h_dep_init.data(), (size_t)g->n_tasks * sizeof(u32), hipMemcpyHostToDevice) == hipSuccess ? BCE_OK : BCE_ERR_HIP;
-}
-
-int bce_dag_run(bce_ctx* c, bce_dag* g, uint32_t instances, uint32_t slot_stride, uint32_t slot_base) {
-    if (!c || !g) return BCE_ERR_ARG;
-    if (instances == 0) return BCE_OK;
-    if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "bce_keygen / bce_import_keys has not been called");
-    if (g->n_checks && g->expect_instances == 0) return c->fail(BCE_ERR_STATE, "bce_dag_run: the DAG has checks but bce_dag_set_expected has not been called");
-    if (g->n_checks && g->expect_instances != instances) return c->fail(BCE_ERR_STATE, "bce_dag_run: %u instances, but the expected bits were set for %u", instances, g->expect_instances);
-    if (instances > 1 && slot_stride <= g->max_slot) return c->fail(BCE_ERR_ARG, "bce_dag_run: slot_stride %u does not cover the DAG's slots (0..%u)", slot_stride, g->max_slot);
-    if ((u64)slot_base + g->max_slot + (u64)(instances - 1) * slot_stride >= c->pool_slots) return c->fail(BCE_ERR_POOL, "bce_dag_run: slot %llu outside the pool (%u slots)", (unsigned long long)((u64)slot_base + g->max_slot + (u64)(instances - 1) * slot_stride), c->pool_slots);
-    const u64 items = (u64)g->n_tasks * instances;
-    if (items >= 0xFFFFFFF0ull) return c->fail(BCE_ERR_ARG, "bce_dag_run: %llu bootstraps exceed one run's 32-bit item space", (unsigned long long)items);
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->dag_pending >= bce_ctx::kDagRuns) { const int rc = sync_stream(c); if (rc) return rc; }
-    if (!c->d_P.get()) HIP_TRY(c, c->d_P.alloc(1));
-    if (!c->h_dag_status.get()) HIP_TRY(c, c->h_dag_status.alloc(bce_ctx::kDagRuns));
-    if (!c->h_dag_stage.get()) HIP_TRY(c, c->h_dag_stage.alloc(bce_ctx::kDagRuns));
-    // per-run state (a dag object serves one run at a time: runs are ordered on the engine's stream)
-    HIP_TRY(c, g->d_dep.grow(items, items, c->stream));
-    DagParams D{};
-    for (u32 q = 0; q < kDagQueues; ++q) {
-        const size_t need = (size_t)g->qcount[q] * instances;
-        HIP_TRY(c, g->d_slots[q].grow(need, need, c->stream));
-        D.slots[q] = g->d_slots[q].get();
-        D.qcap[q] = (u32)need;
-        D.init_off[q] = g->init_off[q];
-    }
-    D.init_off[kDagQueues] = g->init_off[kDagQueues];
-    D.tasks = g->d_tasks.get(); D.cons_off = g->d_cons_off.get(); D.cons = g->d_cons.get(); D.qid = g->d_qid.get(); D.dep_init = g->d_dep_init.get();
-    D.dep = g->d_dep.get(); D.init_items = g->d_init.get(); D.ctl = g->d_ctl.get();
-    D.n_tasks = g->n_tasks; D.instances = instances; D.slot_stride = slot_stride; D.slot_base = slot_base;
-    if (g->n_checks) {   // verify mode: the worker checks (and repairs) before it releases a task's consumers
-        if (const int rc = ensure_check(c)) return rc;
-        D.chk_of_task = g->d_chk_of_task.get(); D.expect = static_cast<const uint8_t*>(g->expect.device()); D.n_checks = g->n_checks; D.repair = (u32)g->chk_repair;
-        D.s8 = c->d_s8.get(); D.report = c->d_check(); D.log = c->d_check_log();
-    }
-    D.lazy_ticks = c->dag_lazy_us * 100u;                     // s_memrealtime: 100 MHz
-    D.stall_ticks = c->dag_stall_ms * 100000u;
-    D.policy = c->dag_placement ? 1u : 0u;
-    D.gate_ticks = 15000;        // 150 us: the finish times of bootstraps that started together spread less than that
-    D.gate_backlog = 8;          // (64 / 16 / 4 / 1: AES K = 8 at 150 / 153 / 154 / 155 k; with the classes below 157 k, profiles/r03_dataflow_vs_steps.jsonl)
-    if (const char* e = std::getenv("BCE_DAG_GATE_US")) D.gate_ticks = (u32)std::atoi(e) * 100u;
-    if (const char* e = std::getenv("BCE_DAG_GATE_BACKLOG")) D.gate_backlog = (u32)std::atoi(e);
-    // one or two workgroups per CU: two run 512 bootstraps per ~3.1 ms, one runs 256 per ~1.9 ms -- with less work per
-    // dependency level than the CUs can hold alone, the shorter bootstrap wins
-    int wps = c->dag_wg_per_cu == 1 ? 2 : 4;
-    if (c->dag_wg_per_cu == 0) {
-        // lower bound of the run under either residency, in units of one bootstrap with a CU to itself: the DAG's longest
-        // chain against the work over the chip's rate.  Two workgroups per CU take 1.6 x as long per bootstrap (3.1 vs
-        // 1.93 ms) and deliver 1.26 x the rate (165 vs 131 k/s); the cheaper bound wins (AES-expanded: K <= 2 one per CU,
-        // K >= 4 two; md5 K = 16 and adder_64 K = 64 one.  Against the earlier rule "work per level <= 3/4 of the CUs":
-        // adder_64 K = 64 97.9 -> 117.9 k/s, AES K = 2 115.7 -> 109.6 k, md5 K = 16 114.0 -> 110.1 k,
-        // profiles/r03_dataflow_vs_steps.jsonl)
-        const double D = (double)std::max<u32>(1, g->depth), W = (double)items, cus = (double)std::max<u32>(1, c->P.cu_count);
-        const double t1 = std::max(D, W / cus), t2 = std::max(1.6 * D, W / (1.26 * cus));
-        wps = t1 <= t2 ? 2 : 4;
-    }
-    if (const char* e = std::getenv("BCE_DAG_WPS")) { if (e[0] == '2') wps = 2; else if (e[0] == '4') wps = 4; }
-    if (kernel_class(c->P).wg_per_cu_full == 1) wps = 2;   // the config-5 kernel: one 1,024-thread workgroup is all a CU's LDS holds
-    if (const char* e = std::getenv("BCE_DAG_PLACE")) D.policy = e[0] == '0' ? 0u : 1u;
-    const char* dbg = std::getenv("BCE_DAG_DEBUG");   // development: 'r' = re-arm only, 'd' = dry run (no bootstraps)
-    if (dbg && dbg[0] == 'd') D.policy |= 2u;
-    // the XCD start gate pays where two workgroups per CU share the L2 in the saturated regime (development knob BCE_DAG_GATE=0 / 1)
-    { const char* e = std::getenv("BCE_DAG_GATE"); if (e ? e[0] != '0' : wps == 4) D.policy |= 4u; }
-    { const char* e = std::getenv("BCE_DAG_TICKETS"); if (e && e[0] == '1') D.policy |= 8u; }   // development: round 3's claim rule
-    const u32 grid = c->P.cu_count * (wps == 2 ? 1u : 2u);
-    // parameter blocks reach the device in stream order (an earlier run may still be reading the previous ones) from
-    // pinned staging entries that stay untouched until the next synchronisation
-    const int slot = c->dag_pending++;
-    bce_ctx::DagStage& stage = c->h_dag_stage.get()[slot];
-    stage.P = c->P;
-    stage.D = D;
-    HIP_TRY(c, hipMemcpyAsync(c->d_P.get(), &stage.P, sizeof(DevParams), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(g->d_params.get(), &stage.D, sizeof(DagParams), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, launch_dag_rearm(D, c->stream));
-    EventPair e0 = get_events(c, BCE_BR_DAG);
-    hipEventRecord(e0.a, c->stream);
-    if (!(dbg && dbg[0] == 'r')) HIP_TRY(c, launch_bootstrap_dag(c->P, c->d_P.get(), g->d_params.get(), wps, grid, c->stream));
-    hipEventRecord(e0.b, c->stream);
-    c->pending.push_back(e0);
-    c->dag_expected[slot] = items;
-    c->dag_wps_used[slot] = wps;
-    HIP_TRY(c, hipMemcpyAsync(&c->h_dag_status.get()[slot], g->d_ctl.get() + kDagAbort, sizeof(bce_ctx::DagStatus), hipMemcpyDeviceToHost, c->stream));
-    c->timing.br_launches[BCE_BR_DAG] += 1;
-    c->timing.br_bootstraps[BCE_BR_DAG] += items;
-    c->timing.blind_rotate_launches += 1;
-    c->timing.fused_tail_launches += 1;
-    c->timing.bootstraps += items;
-    return BCE_OK;
-}
-
 int bce_timing_reset(bce_ctx* c) {
     if (!c) return BCE_ERR_ARG;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1797,7 +1121,7 @@ int bce_debug_eval_stages(bce_ctx* c, uint32_t n_desc, const bce_gate_desc* desc
                           uint64_t* ks) {
     if (!c) return BCE_ERR_ARG;
     for (u32 i = 0; i < n_desc; ++i)
-        if (!(pair_kind(descs[i].op) > 0 || descs[i].op <= BCE_XNOR_FAST || descs[i].op == BCE_OP_REFRESH)) return c->fail(BCE_ERR_ARG, "staged outputs need bootstrapped ops only");
+        if (!desc_kind(descs[i].op).boot()) return c->fail(BCE_ERR_ARG, "staged outputs need bootstrapped ops only");
     return eval_impl(c, n_desc, descs, 1, 0, acc, lweN, ks);
 }
 
@@ -1807,7 +1131,7 @@ int bce_debug_eval_stages(bce_ctx* c, uint32_t n_desc, const bce_gate_desc* desc
 int bce_debug_tail(bce_ctx* c, uint32_t count, const uint64_t* acc, const uint32_t* out_slots, uint64_t* lweN, uint64_t* ks) {
     if (!c || !acc || !out_slots) return BCE_ERR_ARG;
     if (count == 0) return BCE_OK;
-    if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "bce_keygen / bce_import_keys has not been called");
+    if (const int rc = need_keys(c)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t words = (size_t)count * 2 * c->N;
     for (size_t i = 0; i < words; ++i)

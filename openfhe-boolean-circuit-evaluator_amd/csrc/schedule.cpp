@@ -5,6 +5,8 @@
 #include <queue>
 #include <stdexcept>
 
+#include "desc.hpp"
+
 namespace bce::sched {
 
 uint32_t gate_weight(Op op, XorMode mode) {
@@ -303,7 +305,7 @@ bool check(const StepPlan& P, const Dag& dag, uint32_t rank, uint32_t world, std
                 }
             }
         for (const auto& d : P.steps[s]) {
-            const uint32_t outs = (d.op >> 8) ? 2 : 1;   // a pair writes out and out + 1, both temporaries
+            const uint32_t outs = desc_kind(d.op).outputs;   // a pair writes out and out + 1, both temporaries
             if (outs == 2 && d.out < W) return fail("a pair writes a netlist register");
             for (uint32_t o = d.out; o < d.out + outs; ++o) {
                 if (o >= P.stride) return fail("output slot outside the stride");
