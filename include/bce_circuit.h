@@ -111,6 +111,15 @@ int bce_circuit_set_xor_fast(bce_circuit*, int on);
  * it.  Without the option these calls are unrestricted, as before. */
 int bce_circuit_set_xor_shared(bce_circuit*, int on);
 int bce_circuit_xor_shared_active(const bce_circuit*);
+/* opt-in extension, NOT an OpenFHE gate: every XOR gate as ONE BCE_XOR bootstrap of ct1 + ct2 (three-level test polynomial,
+ * bce_gpu.h): the bootstrap count and the depth of XOR_FAST, but the input is the plain sum of two refreshed ciphertexts and
+ * every level sits q/8 from both boundaries, so the failure probability is a plain gate's class, not XOR_FAST's.  Runs on
+ * every path xor_fast runs on: per-gate evaluation and gate-level rounds (host verify included: the XOR's output is a
+ * netlist wire), the bootstrap-depth schedule with slack filling, graph replay, the dataflow schedule, device verify and
+ * gate sharding.  n_bootstraps, the step sizes, the statistics and the plan hash reflect the mode.  Call it before SetInput
+ * (the slot stride depends on it; BCE_ERR_STATE after); together with xor_fast or xor_shared: BCE_ERR_ARG. */
+int bce_circuit_set_xor_single(bce_circuit*, int on);
+int bce_circuit_get_xor_single(const bce_circuit*);
 /* Schedule by bootstrap depth (NOTs folded into consumers, an XOR's OR launched with the next level's ANDs): the
  * same ciphertext in every bootstrapped register as the reference's gate-level rounds -- asserted register by register on
  * AES-expanded, tests/test_gpu_circuit.py -- in fewer dependent launches (AES-expanded: 416 instead of 496, one block

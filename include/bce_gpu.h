@@ -36,6 +36,8 @@ enum bce_method { BCE_AP = 1, BCE_GINX = 2 };
 /* lbcrypto::BINGATE for EvalBinGate (src/gate.cpp:133,172) + the unary ops the driver issues */
 enum bce_op {
     BCE_OR = 0, BCE_AND = 1, BCE_NOR = 2, BCE_NAND = 3, BCE_XOR_FAST = 4, BCE_XNOR_FAST = 5,
+    BCE_XOR = 0x10006,   /* XOR in one bootstrap of ct1 + ct2: three-level test polynomial, see below; NOT an OpenFHE gate.
+                            Gate byte 6 with bit 16 set: the bare codes 6 .. 15 and 19 .. 255 stay no op (BCE_ERR_ARG), as they always were */
     BCE_OP_NOT = 16,     /* EvalNOT, src/gate.cpp:112,198-199 : no bootstrap      */
     BCE_OP_REFRESH = 17, /* Bootstrap(ct) as run by Encrypt(BOOTSTRAPPED)         */
     BCE_OP_COPY = 18     /* OUTPUT gate copy, src/gate.cpp:90-94                  */
@@ -55,7 +57,7 @@ enum { BCE_P_n = 0, BCE_P_N, BCE_P_q, BCE_P_Q, BCE_P_qKS, BCE_P_baseKS, BCE_P_dK
  * bootstrap's LWE prep, which is how XOR = (a AND !b) OR (!a AND b)
  * (src/gate.cpp:198-202) is issued without materialising the NOTs. */
 typedef struct bce_gate_desc {
-    uint32_t op;   /* enum bce_op in bits 0..7; bits 8..15: 0, or the second gate + 1 of a pair (BCE_PAIR) */
+    uint32_t op;   /* enum bce_op: the gate in bits 0..7; bits 8..15: 0, or the second gate + 1 of a pair (BCE_PAIR); bit 16: BCE_XOR only */
     uint32_t in0;  /* pool slot */
     uint32_t in1;  /* pool slot (ignored by 1-input ops) */
     uint32_t out;  /* pool slot */
@@ -77,6 +79,25 @@ typedef struct bce_gate_desc {
  * bce_dag_create refuses pairs (BCE_ERR_UNSUPPORTED).  The counters of bce_timing count blind rotations: a pair counts 1.
  * XOR(a, b) = AND(OR(a, b), NAND(a, b)) is then two blind rotations instead of three (bce_circuit_set_xor_shared). */
 #define BCE_PAIR(op, op2) ((uint32_t)(op) | (((uint32_t)(op2) + 1u) << 8))
+
+/* XOR in ONE bootstrap at a plain gate's noise (BCE_XOR; NOT a gate of OpenFHE v1.0.x, whose one-bootstrap XOR is XOR_FAST).
+ * The plain sum ct1 + ct2 of two bits encoded in multiples of q/4 (with the folded EvalNOTs of neg0 / neg1, exactly the
+ * preparation of AND and OR) has phase 0, q/4 or q/2, and XOR is 1 exactly at q/4.  With f = 2N/q, b the last word of the sum
+ * and one = 2(Q/8 + 1) mod Q the test polynomial is, for j = 0 .. q/2 - 1 and t = (b - j) mod q,
+ *   m[j f] = one       if  q/8 <= t < 3q/8
+ *   m[j f] = Q - one   if 5q/8 <= t < 7q/8
+ *   m[j f] = 0         otherwise                     (every other coefficient 0)
+ * i.e. the function +one on [q/8, 3q/8), -one on [5q/8, 7q/8), 0 elsewhere, which is negacyclic (f(t + q/2) = -f(t)) and so a
+ * legal test polynomial of the same blind rotation; the tail extracts b' = acc[1][0] WITHOUT the Q/8 + 1 every other gate adds,
+ * so the nominal outputs are 0 and 2(Q/8 + 1), the levels of every other gate: consumers need no change.
+ * Margin: each level (0, q/4, q/2) is q/8 away from BOTH neighbouring boundaries, where a plain gate has q/8 on its near side;
+ * the input noise is that of AND's sum (XOR_FAST doubles it: 2(ct1 - ct2) in OR's window), so the failure probability is at
+ * most twice a plain gate's one-sided tail.  Output noise is a plain gate's: the accumulator's noise comes from the external
+ * products, not from the polynomial's values.  neg0 / neg1 negate the inputs; XNOR is BCE_XOR with one of them set.
+ * Accepted wherever a plain gate is (bce_eval_gates[_strided], bce_debug_eval_stages, bce_plan_create, bce_dag_create[_pairs]),
+ * one bootstrap in bce_timing; NOT inside BCE_PAIR (its polynomial is no rotation of a plain gate's): BCE_ERR_ARG.
+ * The word is 0x10006 and nothing else: the code 6 alone, and bit 16 on any other word, are BCE_ERR_ARG.
+ * bce_circuit_set_xor_single evaluates every XOR gate of a circuit this way. */
 
 /* which blind-rotation kernel a launch used (chosen by parameter set and launch size) */
 enum bce_br_kernel {
@@ -204,7 +225,7 @@ int bce_synchronize(bce_ctx*);
  *   bce_plan_run       = every step's launches captured once into a hipGraph and replayed with one hipGraphLaunch:
  *                        no per-step host call, no upload, no event between dependent kernels.  Timed as one unit
  *                        (BCE_BR_GRAPH).  Same ciphertexts in every register as the step-by-step form.
- * Steps hold bootstrapped ops only (BCE_AND .. BCE_XNOR_FAST, BCE_OP_REFRESH, BCE_PAIR descriptors); `descs` = the steps' descriptors back to
+ * Steps hold bootstrapped ops only (BCE_OR .. BCE_XNOR_FAST, BCE_XOR, BCE_OP_REFRESH, BCE_PAIR descriptors); `descs` = the steps' descriptors back to
  * back, step s has step_sizes[s] of them.  instances / slot_stride as in bce_eval_gates_strided; the slots are fixed at
  * creation (slot_base shifts them all, e.g. a rank's first instance). */
 typedef struct bce_plan bce_plan;

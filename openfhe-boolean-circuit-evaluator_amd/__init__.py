@@ -20,6 +20,7 @@ LIB_PATH = os.path.join(_HERE, "libbce_amd.so")
 TOY, MEDIUM, STD128_AP, STD128_APOPT, STD128, STD128_OPT, STD192, STD192_OPT, STD256, STD256_OPT = range(10)
 AP, GINX = 1, 2
 OR, AND, NOR, NAND, XOR_FAST, XNOR_FAST = range(6)
+XOR = 0x10006   # BCE_XOR (gate byte 6 with bit 16; the bare code 6 is no op): XOR in one bootstrap of ct1 + ct2 (three-level test polynomial); not an OpenFHE gate
 OP_NOT, OP_REFRESH, OP_COPY = 16, 17, 18
 
 
@@ -560,7 +561,7 @@ class BinFHEContext:
         descriptor order, after the len(descs) rows of the first outputs"""
         arr = make_descs(descs)
         nb = len(arr)
-        rows = nb + sum(1 for d in arr if d.op >> 8)
+        rows = nb + sum(1 for d in arr if (d.op >> 8) & 0xFF)
         acc = np.zeros((nb, 2 * self.N), dtype=np.uint64)
         lweN = np.zeros((rows, self.N + 1), dtype=np.uint64)
         ks = np.zeros((rows, self.n + 1), dtype=np.uint64)
@@ -608,7 +609,7 @@ CIRCUIT_SYMBOLS = [
     "bce_circuit_create", "bce_circuit_destroy", "bce_circuit_last_error", "bce_circuit_read_file",
     "bce_circuit_read_bristol", "bce_circuit_get_info", "bce_circuit_reset", "bce_circuit_rearm", "bce_circuit_set_plaintext",
     "bce_circuit_set_encrypted", "bce_circuit_set_verify", "bce_circuit_get_flags", "bce_circuit_set_batched",
-    "bce_circuit_set_encrypt_mode", "bce_circuit_get_encrypt_mode", "bce_circuit_plan_hash", "bce_circuit_set_shard_locality", "bce_circuit_set_xor_fast", "bce_circuit_set_xor_shared", "bce_circuit_xor_shared_active", "bce_circuit_set_relevel", "bce_circuit_get_relevel", "bce_circuit_set_dataflow", "bce_circuit_set_dataflow_shared", "bce_circuit_dataflow_active", "bce_circuit_set_graph", "bce_circuit_graph_active", "bce_circuit_set_device_verify", "bce_circuit_device_verify_active", "bce_circuit_get_check_report", "bce_circuit_dataflow_plan", "bce_circuit_set_balance", "bce_circuit_relevel_steps", "bce_circuit_relevel_descs", "bce_circuit_relevel_publications", "bce_circuit_check_relevel", "bce_circuit_set_instances", "bce_circuit_set_input", "bce_circuit_clock",
+    "bce_circuit_set_encrypt_mode", "bce_circuit_get_encrypt_mode", "bce_circuit_plan_hash", "bce_circuit_set_shard_locality", "bce_circuit_set_xor_fast", "bce_circuit_set_xor_shared", "bce_circuit_xor_shared_active", "bce_circuit_set_xor_single", "bce_circuit_get_xor_single", "bce_circuit_set_relevel", "bce_circuit_get_relevel", "bce_circuit_set_dataflow", "bce_circuit_set_dataflow_shared", "bce_circuit_dataflow_active", "bce_circuit_set_graph", "bce_circuit_graph_active", "bce_circuit_set_device_verify", "bce_circuit_device_verify_active", "bce_circuit_get_check_report", "bce_circuit_dataflow_plan", "bce_circuit_set_balance", "bce_circuit_relevel_steps", "bce_circuit_relevel_descs", "bce_circuit_relevel_publications", "bce_circuit_check_relevel", "bce_circuit_set_instances", "bce_circuit_set_input", "bce_circuit_clock",
     "bce_circuit_get_output", "bce_circuit_get_buses", "bce_circuit_get_counts", "bce_circuit_get_stats", "bce_circuit_dump",
     "bce_circuit_set_exchange", "bce_circuit_enable_rccl", "bce_circuit_exchange_capacity", "bce_assemble_bristol", "bce_pool_gather",
     "bce_pool_scatter",
@@ -633,7 +634,7 @@ def _bind_circuit():
     L.bce_circuit_get_info.argtypes = [vp, C.POINTER(CircuitInfo)]
     for name in ("reset", "rearm", "clock"):
         getattr(L, "bce_circuit_" + name).argtypes = [vp]
-    for name in ("set_plaintext", "set_encrypted", "set_verify", "set_batched", "set_encrypt_mode", "set_xor_fast", "set_xor_shared", "set_relevel", "dump"):
+    for name in ("set_plaintext", "set_encrypted", "set_verify", "set_batched", "set_encrypt_mode", "set_xor_fast", "set_xor_shared", "set_xor_single", "set_relevel", "dump"):
         getattr(L, "bce_circuit_" + name).argtypes = [vp, i32]
     L.bce_circuit_get_flags.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.bce_circuit_set_instances.argtypes = [vp, u32]
@@ -652,6 +653,7 @@ def _bind_circuit():
     L.bce_circuit_plan_hash.restype = u64
     L.bce_circuit_dataflow_active.argtypes = [vp]
     L.bce_circuit_xor_shared_active.argtypes = [vp]
+    L.bce_circuit_get_xor_single.argtypes = [vp]
     L.bce_circuit_dataflow_plan.argtypes = [vp, vp, vp, u32, C.POINTER(u32)]
     L.bce_circuit_relevel_steps.argtypes = [vp, C.POINTER(u32), u32, C.POINTER(u32)]
     L.bce_circuit_relevel_descs.argtypes = [vp, vp, u32, C.POINTER(u32)]
@@ -808,6 +810,14 @@ class Circuit:
         """opt-in: XOR as AND(OR, NAND) with the OR and the NAND from one blind rotation (a PAIR descriptor): two blind
         rotations per XOR instead of three, same depth, same bits on every netlist wire; before SetInput, not with setXorFast"""
         self._ck(self._L.bce_circuit_set_xor_shared(self.h, int(b)))
+
+    def setXorSingle(self, b):
+        """opt-in, not an OpenFHE gate: XOR as one XOR bootstrap (op XOR) of ct1 + ct2 with a three-level test polynomial: the
+        count and depth of XOR_FAST at a plain gate's noise; before SetInput, not with setXorFast / setXorShared"""
+        self._ck(self._L.bce_circuit_set_xor_single(self.h, int(b)))
+
+    def getXorSingle(self):
+        return bool(self._L.bce_circuit_get_xor_single(self.h))
 
     def xorSharedActive(self):
         """True if the next Clock() on the bootstrap-depth schedule lowers its XORs that way (batched launches, no gate

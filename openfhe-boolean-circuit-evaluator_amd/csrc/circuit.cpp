@@ -113,8 +113,8 @@ void Gate::Evaluate(const GateEvalParams& gep) {
             break;
         case GateEnum::XOR:
             if (pt) { plainout.resize(1); plainout[0] = plainin[0] ^ plainin[1]; }
-            if (en && gep.xor_fast) {
-                bce_gate_desc d{BCE_XOR_FAST, encin[0], encin[1], enc_dst(), 0, 0};
+            if (en && (gep.xor_fast || gep.xor_single)) {
+                bce_gate_desc d{(uint32_t)(gep.xor_single ? BCE_XOR : BCE_XOR_FAST), encin[0], encin[1], enc_dst(), 0, 0};
                 gate_ck(gep, bce_eval_gates(gep.cc, 1, &d), name);
                 if (vf) verify_fix(gep, "XOR", encout[0], plainout[0], true, name);
             } else if (en) {
@@ -483,7 +483,7 @@ void Circuit::SetInput(unsigned inst, const Inputs& input, bool verbose) {
 
 // ---- sharding plan --------------------------------------------------------------------------
 void Circuit::buildShardPlan() {
-    shard_ = gateSharded() ? sched::shard_levels(net_, world_, xor_fast_) : sched::LevelShard{};
+    shard_ = gateSharded() ? sched::shard_levels(net_, world_, xor_single_ ? sched::XorMode::Single : sched::xor_mode(xor_fast_)) : sched::LevelShard{};
 }
 
 uint64_t Circuit::exchangeCapacity(uint32_t world, int shard_mode, bool encrypted) const {
@@ -657,6 +657,7 @@ std::vector<uint32_t> Circuit::relevelPublications() const {
 
 void Circuit::setXorFast(bool b) {
     if (b && xor_shared_) throw std::invalid_argument("setXorFast: not together with setXorShared");
+    if (b && xor_single_) throw std::invalid_argument("setXorFast: not together with setXorSingle");
     xor_fast_ = gep.xor_fast = b;
     buildUnits();
     buildShardPlan();
@@ -665,9 +666,19 @@ void Circuit::setXorFast(bool b) {
 
 void Circuit::setXorShared(bool b) {
     if (b && xor_fast_) throw std::invalid_argument("setXorShared: not together with setXorFast");
+    if (b && xor_single_) throw std::invalid_argument("setXorShared: not together with setXorSingle");
     if (inputs_set_ && b != xor_shared_) throw std::logic_error("setXorShared: choose the XOR lowering before SetInput");
     xor_shared_ = b;
     syncXorMode();
+}
+
+void Circuit::setXorSingle(bool b) {
+    if (b && (xor_fast_ || xor_shared_)) throw std::invalid_argument("setXorSingle: not together with setXorFast or setXorShared");
+    if (inputs_set_ && b != xor_single_) throw std::logic_error("setXorSingle: choose the XOR lowering before SetInput");
+    xor_single_ = gep.xor_single = b;
+    buildUnits();
+    buildShardPlan();
+    rebuildRelevel();
 }
 
 // The two lowerings use the same temporaries (two adjacent slots per XOR): under the same placement the slot stride does
@@ -991,8 +1002,8 @@ void Circuit::executeRound(size_t level) {
             for (size_t k = 0; k < L.gates.size(); ++k) {
                 const GateRec& g = allGates[L.gates[k]];
                 const bool me = mine(k);
-                if (g.op == GateEnum::XOR && xor_fast_) {
-                    if (me) A.push_back({BCE_XOR_FAST, (uint32_t)g.in[0], (uint32_t)g.in[1], (uint32_t)g.out, 0, 0});
+                if (g.op == GateEnum::XOR && (xor_fast_ || xor_single_)) {
+                    if (me) A.push_back({(uint32_t)(xor_single_ ? BCE_XOR : BCE_XOR_FAST), (uint32_t)g.in[0], (uint32_t)g.in[1], (uint32_t)g.out, 0, 0});
                 } else if (g.op == GateEnum::XOR) {
                     const uint32_t t1 = tmp0 + 2 * x, t2 = t1 + 1;
                     ++x;

@@ -61,6 +61,7 @@ public:
     bool verify_flag = false;
     bce_ctx* cc = nullptr;
     bool xor_fast = false;            // opt-in: XOR as ONE bootstrap of 2*(ct1-ct2) (BCE_XOR_FAST), not the reference's 3
+    bool xor_single = false;          // opt-in: XOR as ONE bootstrap of ct1+ct2 (BCE_XOR, three-level test polynomial)
     int encrypt_mode = BCE_BOOTSTRAPPED;  // output mode of the verify-mode re-encryptions (cc.Encrypt(sk, bit), src/gate.cpp:118,...)
     uint64_t* enc_counter = nullptr;  // PRNG stream index for verify-mode re-encryptions
     unsigned int* fixes = nullptr;    // counts "Bad <OP> fixing" events
@@ -140,6 +141,12 @@ public:
     // ones, so the other lowering can need more temporaries per step than the stride has (adder_64bit, K = 64: 899
     // slots laid out, 923 needed).  With the option off these calls behave as they always did.  Reset() lifts it.
     void setXorShared(bool b);
+    // opt-in, not an OpenFHE gate: XOR as ONE BCE_XOR bootstrap of ct1 + ct2 (three-level test polynomial, bce_gpu.h): the
+    // bootstrap count and depth of XOR_FAST at a plain gate's noise (every level q/8 from both boundaries).  On every path
+    // XOR_FAST runs on.  Before SetInput (the slot stride depends on it: std::logic_error after); not together with
+    // setXorFast or setXorShared (std::invalid_argument).
+    void setXorSingle(bool b);
+    bool getXorSingle() const { return xor_single_; }
     bool getXorShared() const { return xor_shared_; }
     bool xorSharedActive() const { return xor_shared_ && batched_ && relevel_ && !gateSharded() && !(verify_flag && !device_verify_); }
     // opt-in: schedule by BOOTSTRAP depth instead of gate level -- NOT gates are folded into their
@@ -236,7 +243,7 @@ private:
     bce_ctx* cc = nullptr;
     bool owns_engine_ = false;
     bool plaintext_flag = false, encrypted_flag = false, verify_flag = false;
-    bool done = false, inputs_set_ = false, quiet_ = false, batched_ = true, xor_fast_ = false, xor_shared_ = false;
+    bool done = false, inputs_set_ = false, quiet_ = false, batched_ = true, xor_fast_ = false, xor_shared_ = false, xor_single_ = false;
     int encrypt_mode_ = BCE_BOOTSTRAPPED;
     GateEvalParams gep;
 
@@ -284,7 +291,7 @@ private:
     sched::Dag net_;          // the levelised netlist as the schedule module reads it
     sched::Units units_;      // rebuilt when the netlist or the XOR mode changes
     sched::XorMode units_mode_ = sched::XorMode::Reference;   // the mode units_ were built for
-    sched::XorMode xorMode() const { return xor_fast_ ? sched::XorMode::Fast : xorSharedActive() ? sched::XorMode::Shared : sched::XorMode::Reference; }
+    sched::XorMode xorMode() const { return xor_fast_ ? sched::XorMode::Fast : xor_single_ ? sched::XorMode::Single : xorSharedActive() ? sched::XorMode::Shared : sched::XorMode::Reference; }
     void buildUnits() { units_mode_ = xorMode(); units_ = sched::build_units(net_, units_mode_); tasks_ = {}; }
     void syncXorMode();       // after a change of anything xorSharedActive() reads: units and schedules for the mode that now holds
     void setModeFlag(bool& flag, bool b, const char* who);   // sets one of those flags; refused after SetInput where it would switch the lowering

@@ -82,6 +82,8 @@ int bce_circuit_set_encrypt_mode(bce_circuit* h, int mode) {
 }
 int bce_circuit_set_xor_fast(bce_circuit* h, int on) { return guarded(h, [&] { h->c.setXorFast(on != 0); }); }
 int bce_circuit_set_xor_shared(bce_circuit* h, int on) { return guarded(h, [&] { h->c.setXorShared(on != 0); }); }
+int bce_circuit_set_xor_single(bce_circuit* h, int on) { return guarded(h, [&] { h->c.setXorSingle(on != 0); }); }
+int bce_circuit_get_xor_single(const bce_circuit* h) { return h && h->c.getXorSingle() ? 1 : 0; }
 int bce_circuit_xor_shared_active(const bce_circuit* h) { return h && h->c.xorSharedActive() ? 1 : 0; }
 int bce_circuit_set_relevel(bce_circuit* h, int on) { return guarded(h, [&] { h->c.setRelevel(on != 0); }); }
 int bce_circuit_get_relevel(bce_circuit* h) { return h && h->c.getRelevel() ? 1 : 0; }

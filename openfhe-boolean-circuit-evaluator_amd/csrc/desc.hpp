@@ -9,16 +9,17 @@
 namespace bce {
 
 // The descriptor word `op`: bits 0..7 the gate, bits 8..15 the second gate + 1 of a pair (BCE_PAIR, two different gates of
-// OR, AND, NOR, NAND on one blind rotation).  0: plain descriptor, 1: legal pair, -1: anything else in the high bits.
+// OR, AND, NOR, NAND on one blind rotation); BCE_XOR is gate byte 6 with bit 16, and the only word with a bit above 15.
+// 0: plain descriptor, 1: legal pair, -1: anything else in the high bits.
 inline int pair_kind(uint32_t op) {
-    if (op <= 0xFFu) return 0;
+    if (op <= 0xFFu || op == BCE_XOR) return 0;
     const uint32_t lo = op & 0xFFu, hi = op >> 8;
     return (lo <= BCE_NAND && hi >= 1 && hi - 1 <= BCE_NAND && hi - 1 != lo) ? 1 : -1;
 }
 
 enum class DescClass : uint8_t {
     None,      // no op of the engine: an unknown code, or illegal bits 8..
-    Gate,      // bootstrapped, two inputs: a plain gate up to BCE_XNOR_FAST, or a legal pair
+    Gate,      // bootstrapped, two inputs: a plain gate up to BCE_XNOR_FAST, BCE_XOR, or a legal pair
     Refresh,   // BCE_OP_REFRESH: bootstrapped, one input
     Unary,     // BCE_OP_NOT, BCE_OP_COPY: one input, no bootstrap
 };
@@ -30,7 +31,7 @@ struct DescKind {
 };
 inline DescKind desc_kind(uint32_t op) {
     if (pair_kind(op) > 0) return {DescClass::Gate, 2, 2};
-    if (op <= BCE_XNOR_FAST) return {DescClass::Gate, 2, 1};
+    if (op <= BCE_XNOR_FAST || op == BCE_XOR) return {DescClass::Gate, 2, 1};
     if (op == BCE_OP_REFRESH) return {DescClass::Refresh, 1, 1};
     if (op == BCE_OP_NOT || op == BCE_OP_COPY) return {DescClass::Unary, 1, 1};
     return {DescClass::None, 0, 1};

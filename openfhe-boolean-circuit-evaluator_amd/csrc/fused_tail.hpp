@@ -24,6 +24,21 @@ __device__ __forceinline__ u32 gate_const(u32 op, u32 q) {
     }
 }
 
+// ---- XOR in one bootstrap (BCE_XOR, include/bce_gpu.h) -----------------------------------------------------------------
+// Level of its test polynomial at t = (b - j) mod q: +1 on [q/8, 3q/8), -1 on [5q/8, 7q/8), 0 elsewhere (times 2(Q/8 + 1)).
+// The levels sit where every other gate's are, 0 and 2(Q/8 + 1), once the tail leaves its Q/8 + 1 out: tail_offset.
+constexpr u32 kXorGate = BCE_XOR & 0xFFu;   // the gate byte of BCE_XOR (bit 16 of the word tells it from the bare code, on the host)
+__device__ __forceinline__ int xor_level(u32 t, u32 q) {
+    const u32 e = q >> 3;
+    return (t >= e && t < 3 * e) ? 1 : (t >= 5 * e && t < 7 * e) ? -1 : 0;
+}
+// what the tail adds to acc[1][0] before the switch to qKS (CW: the tail's coefficient word)
+template <typename CW, typename PT>
+__device__ __forceinline__ u64 tail_offset(const PT& P, u32 op) {
+    if ((op & 0xFFu) == kXorGate) return 0;
+    return sizeof(CW) == 8 ? (u64)P.Q8p1_64 : (u64)P.Q8p1;
+}
+
 // ---- two gates from one blind rotation (BCE_PAIR, include/bce_gpu.h) ---------------------------------------------
 // BootstrapGateCore's test polynomial depends on the gate only through (b - q1) mod q, so the polynomial of gate op2 is
 // X^e times that of gate op (mod X^N + 1), e = ((q1 - q1') mod q) * (2N / q), and the monomial commutes with the blind
@@ -55,15 +70,15 @@ __device__ __forceinline__ u64 rotated_coef(const CW* p, u32 i, u32 e, u32 N, u6
 // separate kernel between two dependent blind-rotation launches.
 //   coef : [2][N] coefficient-form accumulator in LDS        rowidx : [N * dKS] row numbers in LDS
 //   red  : [SL][Gv * VW] u64 partial sums in LDS (SL row slices, one per RW = ceil(Gv / 64) waves)
+//   off  : added to acc[1][0] (tail_offset)
 //   rot  : the tail runs on X^rot * acc (pair_rotation; 0 = the accumulator itself)
 // T threads (a multiple of 64); every thread of the workgroup must call it.
 template <typename KT, u32 T, typename CW, typename PT>
 __device__ __forceinline__ void fused_tail(const PT& P, const CW* coef, u32* rowidx, u64* red, u32* out, u32 boot,
-                                           u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks, u32 rot = 0) {
+                                           u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks, u64 off, u32 rot = 0) {
     constexpr u32 VW = 16 / sizeof(KT), W = T / 64;
     const u32 N = P.N, n = P.n, qKS = P.qKS, B = P.baseKS, D = P.dKS;
     const u64 Q = sizeof(CW) == 8 ? (u64)P.Q64 : (u64)P.Q;            // coefficient words: u32 (Q < 2^28) or u64
-    const u64 Q8p1 = sizeof(CW) == 8 ? (u64)P.Q8p1_64 : (u64)P.Q8p1;
     const u32 tid = threadIdx.x, lane = tid & 63;
     const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // transpose (X -> X^-1) of acc[0]: a'_0 = a_0, a'_{N-i} = -a_i; ModSwitch(Q -> qKS); digits -> row numbers
@@ -127,7 +142,7 @@ __device__ __forceinline__ void fused_tail(const PT& P, const CW* coef, u32* row
         for (u32 e = 0; e < VW; ++e) red[(size_t)slice * Gv * VW + group * VW + e] = tot[e];
     }
     __syncthreads();
-    // KeySwitch: a' = -sum_rows A[row], b' = b - sum_rows B[row] (mod qKS), b = acc[1][0] + Q/8 + 1 mod-switched;
+    // KeySwitch: a' = -sum_rows A[row], b' = b - sum_rows B[row] (mod qKS), b = acc[1][0] + off (Q/8 + 1; BCE_XOR: 0) mod-switched;
     // then ModSwitch(qKS -> q) into the pool
     for (u32 k = tid; k <= n; k += T) {
         u64 sum = 0;
@@ -135,7 +150,7 @@ __device__ __forceinline__ void fused_tail(const PT& P, const CW* coef, u32* row
         const u32 sm = (u32)(sum % qKS);
         u32 base = 0;
         if (k == n) {
-            u64 b = rotated_coef(coef + N, 0, rot, N, Q, false) + Q8p1;
+            u64 b = rotated_coef(coef + N, 0, rot, N, Q, false) + off;
             b = b >= Q ? b - Q : b;
             base = round_qQ(b, qKS, Q);
             if (dbg_lweN) dbg_lweN[(size_t)boot * (N + 1) + N] = base;

@@ -824,7 +824,7 @@ __device__ __forceinline__ void bootstrap_prologue(const PT& P, const bce_gate_d
     {   // EvalBinGate LWE prep with folded EvalNOT: (-a, q/4 - b)
         const u32* in0 = P.pool + (size_t)(g.in0 + soff) * P.pool_stride;
         const u32* in1 = P.pool + (size_t)(g.in1 + soff) * P.pool_stride;
-        const bool two = op <= BCE_XNOR_FAST;
+        const bool two = op <= kXorGate;
         for (u32 i = tid; i <= n; i += T) {
             u32 v0 = in0[i];
             if (g.neg0) v0 = ((i == n ? (q >> 2) : 0u) - v0) & qm;
@@ -840,7 +840,7 @@ __device__ __forceinline__ void bootstrap_prologue(const PT& P, const bce_gate_d
         }
     }
     __syncthreads();
-    {   // BootstrapGateCore: acc = (0, m(X)), m sparse with +-(Q/8+1)
+    {   // BootstrapGateCore: acc = (0, m(X)), m sparse with +-(Q/8+1); BCE_XOR: 0 and +-2(Q/8+1) (xor_level)
         const u32 b = av[n];
         const u32 q1 = gate_const(op, q), q2 = (q1 + (q >> 1)) & qm;
         const u32 pos = P.Q8p1, neg = Q - P.Q8p1;
@@ -848,8 +848,13 @@ __device__ __forceinline__ void bootstrap_prologue(const PT& P, const bce_gate_d
             u32 v = 0;
             if (j % P.factor == 0) {
                 u32 t = (b - j / P.factor) & qm;
-                bool in = (q1 < q2) ? (t >= q1 && t < q2) : !(t >= q2 && t < q1);
-                v = in ? neg : pos;
+                if (op == kXorGate) {
+                    const int lv = xor_level(t, q);
+                    v = lv > 0 ? 2 * pos : lv < 0 ? Q - 2 * pos : 0u;
+                } else {
+                    bool in = (q1 < q2) ? (t >= q1 && t < q2) : !(t >= q2 && t < q1);
+                    v = in ? neg : pos;
+                }
             }
             acc[phys(j)] = 0;
             acc[NP + phys(j)] = v;
@@ -1519,18 +1524,19 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
         u32* rowidx = dct;
         u64* red = reinterpret_cast<u64*>(dct + ((N * P.dKS + 3) & ~3u));
         u32* outp = P.pool + (size_t)(g.out + soff) * P.pool_stride;
-        if (P.ksk_u16) fused_tail<uint16_t, T>(P, acc, rowidx, red, outp, boot, dbg_lweN, dbg_ks);
-        else fused_tail<u32, T>(P, acc, rowidx, red, outp, boot, dbg_lweN, dbg_ks);
+        const u64 off = tail_offset<u32>(P, g.op);
+        if (P.ksk_u16) fused_tail<uint16_t, T>(P, acc, rowidx, red, outp, boot, dbg_lweN, dbg_ks, off);
+        else fused_tail<u32, T>(P, acc, rowidx, red, outp, boot, dbg_lweN, dbg_ks, off);
         // a pair descriptor (BCE_PAIR) runs the tail a second time, on X^e * acc, into slot out + 1 (debug rows: a second block
         // of gridDim.x rows); the branch is workgroup-uniform, the barrier frees rowidx / red.  The dataflow kernel runs the
         // same pass (bce_dag_create_pairs): g came from D.tasks[t] through the constant address space, so the test is scalar,
         // and both rows are stored before the worker's drain / barrier / release (dag_worker).  Its debug pointers are null:
         // the row index stays `boot`.
-        if (g.op >> 8) {
+        if ((g.op >> 8) & 0xFFu) {   // (bit 16 is BCE_XOR's, not a pair's)
             __syncthreads();
             const u32 e = pair_rotation(P, g.op), row = PERSIST ? boot : boot + gridDim.x;
-            if (P.ksk_u16) fused_tail<uint16_t, T>(P, acc, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, e);
-            else fused_tail<u32, T>(P, acc, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, e);
+            if (P.ksk_u16) fused_tail<uint16_t, T>(P, acc, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, off, e);
+            else fused_tail<u32, T>(P, acc, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, off, e);
         }
     }
 }
@@ -1795,7 +1801,7 @@ __global__ __launch_bounds__(256) void k_tail_gather(DevParams P, u32 S, const A
     u32 rot = 0, dbg_row = boot;
     if constexpr (PAIR) {
         const u32 op = descs[boot % n_desc].op;
-        if (!(op >> 8)) return;
+        if (!((op >> 8) & 0xFFu)) return;
         rot = pair_rotation(P, op);
         dbg_row = boot + gridDim.x / S;
     }
@@ -1897,25 +1903,25 @@ __global__ __launch_bounds__(256) void k_tail_finish(DevParams P, const bce_gate
                                                      u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks) {
     const u32 N = P.N, n = P.n, qKS = P.qKS;
     const u64 Q = sizeof(AW) == 8 ? P.Q64 : (u64)P.Q;
-    const u64 Q8p1 = sizeof(AW) == 8 ? P.Q8p1_64 : (u64)P.Q8p1;
     const u32 boot = blockIdx.x;
     const bce_gate_desc g = descs[boot % n_desc];
+    const u64 off = tail_offset<AW>(P, g.op);
     u32 rot = 0, dbg_row = boot;
     if constexpr (PAIR) {
-        if (!(g.op >> 8)) return;
+        if (!((g.op >> 8) & 0xFFu)) return;
         rot = pair_rotation(P, g.op);
         dbg_row = boot + gridDim.x;
     }
     u32* out = P.pool + (size_t)(g.out + (PAIR ? 1u : 0u) + (boot / n_desc) * slot_stride) * P.pool_stride;
     const u64* part = partial + (size_t)boot * S * (n + 1);
-    // KeySwitch: a' = -sum_rows A[row], b' = b - sum_rows B[row]   (mod qKS), b = acc[1][0] + Q/8 + 1 mod-switched
+    // KeySwitch: a' = -sum_rows A[row], b' = b - sum_rows B[row]   (mod qKS), b = acc[1][0] + off (Q/8 + 1; BCE_XOR: 0) mod-switched
     for (u32 k = threadIdx.x; k <= n; k += 256) {
         u64 sum = 0;
         for (u32 s = 0; s < S; ++s) sum += part[(size_t)s * (n + 1) + k];
         const u32 sm = (u32)(sum % qKS);
         u32 base = 0;
         if (k == n) {
-            u64 b = rotated_coef(acc_in + (size_t)boot * 2 * N + N, 0, rot, N, Q, false) + Q8p1;
+            u64 b = rotated_coef(acc_in + (size_t)boot * 2 * N + N, 0, rot, N, Q, false) + off;
             b = b >= Q ? b - Q : b;
             base = round_qQ(b, qKS, Q);
             if (dbg_lweN) dbg_lweN[(size_t)dbg_row * (N + 1) + N] = base;

@@ -268,7 +268,7 @@ __global__ __launch_bounds__(128 * DG) void k_blind_rotate64(DevParams P, const 
     {
         const u32* in0 = P.pool + (size_t)(g.in0 + soff) * P.pool_stride;
         const u32* in1 = P.pool + (size_t)(g.in1 + soff) * P.pool_stride;
-        const bool two = op <= BCE_XNOR_FAST;
+        const bool two = op <= kXorGate;
         for (u32 i = tid; i <= n; i += T) {
             u32 v0 = in0[i];
             if (g.neg0) v0 = ((i == n ? (q >> 2) : 0u) - v0) & qm;
@@ -292,8 +292,13 @@ __global__ __launch_bounds__(128 * DG) void k_blind_rotate64(DevParams P, const 
             u64 v = 0;
             if (j % P.factor == 0) {
                 u32 t = (b - j / P.factor) & qm;
-                bool in = (q1 < q2) ? (t >= q1 && t < q2) : !(t >= q2 && t < q1);
-                v = in ? neg : pos;
+                if (op == kXorGate) {   // three levels, 0 and +-2(Q/8+1) (xor_level, fused_tail.hpp)
+                    const int lv = xor_level(t, q);
+                    v = lv > 0 ? 2 * pos : lv < 0 ? Q - 2 * pos : (u64)0;
+                } else {
+                    bool in = (q1 < q2) ? (t >= q1 && t < q2) : !(t >= q2 && t < q1);
+                    v = in ? neg : pos;
+                }
             }
             acc[phys(j)] = 0;
             acc[NP + phys(j)] = v;
@@ -1124,7 +1129,7 @@ __device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g,
     {
         const u32* in0 = P.pool + (size_t)(g.in0 + soff) * P.pool_stride;
         const u32* in1 = P.pool + (size_t)(g.in1 + soff) * P.pool_stride;
-        const bool two = op <= BCE_XNOR_FAST;
+        const bool two = op <= kXorGate;
         for (u32 i = tid; i <= n; i += T) {
             u32 v0 = in0[i];
             if (g.neg0) v0 = ((i == n ? (q >> 2) : 0u) - v0) & qm;
@@ -1148,8 +1153,12 @@ __device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g,
             double v = 0.0;
             if (j % P.factor == 0) {
                 u32 t = (b - j / P.factor) & qm;
-                bool in = (q1 < q2) ? (t >= q1 && t < q2) : !(t >= q2 && t < q1);
-                v = in ? neg : pos;
+                if (op == kXorGate) {   // three levels, 0 and +-2(Q/8+1) (xor_level, fused_tail.hpp)
+                    v = (double)xor_level(t, q) * (2.0 * pos);
+                } else {
+                    bool in = (q1 < q2) ? (t >= q1 && t < q2) : !(t >= q2 && t < q1);
+                    v = in ? neg : pos;
+                }
             }
             acc[phys(j)] = 0.0;
             acc[NP + phys(j)] = v;
@@ -1422,15 +1431,16 @@ __device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g,
         u64* red = reinterpret_cast<u64*>(rowidx + ((N * P.dKS + 3) & ~3u));
         u32* outp = P.pool + (size_t)(g.out + soff) * P.pool_stride;
         const u64* coef = reinterpret_cast<const u64*>(acc);
-        if (P.ksk_u16) fused_tail<uint16_t, T>(P, coef, rowidx, red, outp, boot, dbg_lweN, dbg_ks);
-        else fused_tail<u32, T>(P, coef, rowidx, red, outp, boot, dbg_lweN, dbg_ks);
+        const u64 off = tail_offset<u64>(P, g.op);
+        if (P.ksk_u16) fused_tail<uint16_t, T>(P, coef, rowidx, red, outp, boot, dbg_lweN, dbg_ks, off);
+        else fused_tail<u32, T>(P, coef, rowidx, red, outp, boot, dbg_lweN, dbg_ks, off);
         // a pair descriptor (BCE_PAIR): second tail pass on X^e * acc into slot out + 1, as in lat_bootstrap (kernels.hip);
         // in the dataflow kernel too (scalar test of the task's word, debug pointers null: the row index stays `boot`)
-        if (g.op >> 8) {
+        if ((g.op >> 8) & 0xFFu) {   // (bit 16 is BCE_XOR's, not a pair's)
             __syncthreads();
             const u32 e = pair_rotation(P, g.op), row = PERSIST ? boot : boot + gridDim.x;
-            if (P.ksk_u16) fused_tail<uint16_t, T>(P, coef, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, e);
-            else fused_tail<u32, T>(P, coef, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, e);
+            if (P.ksk_u16) fused_tail<uint16_t, T>(P, coef, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, off, e);
+            else fused_tail<u32, T>(P, coef, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, off, e);
         }
     }
 }

@@ -10,7 +10,7 @@
 namespace bce::sched {
 
 uint32_t gate_weight(Op op, XorMode mode) {
-    return op == Op::XOR ? (mode == XorMode::Fast ? 1 : mode == XorMode::Shared ? 2 : 3) : (op == Op::AND || op == Op::OR) ? 1 : 0;
+    return op == Op::XOR ? (mode == XorMode::Fast || mode == XorMode::Single ? 1 : mode == XorMode::Shared ? 2 : 3) : (op == Op::AND || op == Op::OR) ? 1 : 0;
 }
 
 void xor_lower(const bce_gate_desc& u, uint32_t t1, uint32_t t2, bce_gate_desc out[3]) {
@@ -51,6 +51,8 @@ Units build_units(const Dag& dag, XorMode mode) {
                 // XOR_FAST of negated inputs: NOT a XOR NOT b = a XOR b; one negation flips the result
                 u.d.op = (uint32_t)((n0 ^ n1) ? BCE_XNOR_FAST : BCE_XOR_FAST);
                 u.d.neg0 = u.d.neg1 = 0;
+            } else if (mode == XorMode::Single) {
+                u.d.op = BCE_XOR;   // of the inputs as negated: the flags stay, as for AND
             } else {
                 u.lat = 2;
                 u.shared = mode == XorMode::Shared;
@@ -371,10 +373,10 @@ TaskChecks task_checks(const TaskList& T, const Units& S, const Dag& dag) {
     return C;
 }
 
-LevelShard shard_levels(const Dag& dag, uint32_t world, bool xor_fast) {
+LevelShard shard_levels(const Dag& dag, uint32_t world, XorMode mode) {
     LevelShard L;
     const size_t Lc = dag.level_off.empty() ? 0 : dag.level_off.size() - 1;
-    auto cost = [&](const DagGate& g) { return (uint64_t)4 * gate_weight(g.op, xor_fast) + 1; };   // NOT/OUTPUT weigh 1/4 bootstrap
+    auto cost = [&](const DagGate& g) { return (uint64_t)4 * gate_weight(g.op, mode) + 1; };   // NOT/OUTPUT weigh 1/4 bootstrap
     L.owner.resize(Lc);
     std::vector<uint8_t> gate_owner(dag.gates.size(), 0xFF);   // 0xFF = everyone (OUTPUT)
     for (size_t l = 0; l < Lc; ++l) {

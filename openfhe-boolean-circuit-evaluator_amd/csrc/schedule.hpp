@@ -23,7 +23,8 @@ struct Dag {
 // How an XOR gate is evaluated.  Reference: the reference's three bootstraps (src/gate.cpp:198-202).  Fast: one XOR_FAST
 // bootstrap of 2 (ct1 - ct2) (eight times the input variance).  Shared: AND(OR(a, b), NAND(a, b)) with the OR and the NAND
 // from ONE blind rotation (a BCE_PAIR descriptor): two blind rotations, the same depth and the same inputs' noise as Reference.
-enum class XorMode : uint8_t { Reference, Fast, Shared };
+// Single: one BCE_XOR bootstrap of ct1 + ct2 (three-level test polynomial, include/bce_gpu.h): depth 1, a plain gate's noise.
+enum class XorMode : uint8_t { Reference, Fast, Shared, Single };
 inline XorMode xor_mode(bool xor_fast) { return xor_fast ? XorMode::Fast : XorMode::Reference; }
 uint32_t gate_weight(Op op, XorMode mode);   // blind rotations per gate (src/gate.cpp:133,172,200-202)
 inline uint32_t gate_weight(Op op, bool xor_fast) { return gate_weight(op, xor_mode(xor_fast)); }
@@ -33,7 +34,7 @@ void xor_lower(const bce_gate_desc& u, uint32_t t1, uint32_t t2, bce_gate_desc o
 //   the pair (a OR b) -> t, (a NAND b) -> t + 1 from one blind rotation, then t AND (t + 1) -> u.out
 void xor_lower_shared(const bce_gate_desc& u, uint32_t t, bce_gate_desc out[2]);
 
-// Units of the schedule: a single bootstrap (AND / OR / XOR_FAST; its output is ready one step later) or an XOR of lat 2:
+// Units of the schedule: a single bootstrap (AND / OR / XOR_FAST / BCE_XOR; its output is ready one step later) or an XOR of lat 2:
 // built as the reference builds it (two ANDs in step `start`, their OR in step start + 1) or, `shared`, as a pair in step
 // `start` and an AND in step start + 1; d holds in0, in1, out, neg0, neg1.
 struct Unit {
@@ -79,7 +80,7 @@ bool check(const StepPlan&, const Dag&, uint32_t rank, uint32_t world, std::stri
 
 // Verify mode on the step schedule (the reference decrypts and compares every GATE output, src/gate.cpp:153-160): per step,
 // the descriptors whose `out` is a netlist wire -- AND, OR, the final OR (AND, in shared mode) of a lowered XOR, XOR_FAST /
-// XNOR_FAST -- as the register they write and the gate (index into Dag::gates) that owns it.  An XOR's two temporaries are not listed.  NOT
+// XNOR_FAST / BCE_XOR -- as the register they write and the gate (index into Dag::gates) that owns it.  An XOR's two temporaries are not listed.  NOT
 // gates have no register on this schedule: a wrong NOT input shows at its consumer.
 struct CheckLists {
     std::vector<std::vector<uint32_t>> wires;   // [step] -> registers written in that step, in descriptor order
@@ -97,6 +98,7 @@ struct LevelShard {
     std::vector<std::vector<uint8_t>> owner;                 // [level][k]
     std::vector<std::vector<std::vector<int>>> publish;      // [level][rank]
 };
-LevelShard shard_levels(const Dag&, uint32_t world, bool xor_fast);
+LevelShard shard_levels(const Dag&, uint32_t world, XorMode mode);
+inline LevelShard shard_levels(const Dag& dag, uint32_t world, bool xor_fast) { return shard_levels(dag, world, xor_mode(xor_fast)); }
 
 }  // namespace bce::sched

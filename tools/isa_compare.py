@@ -13,6 +13,12 @@ function number taken out of the local labels (.LBB<n>_ -> .LBB_).  Kernels are 
 name, so renamed instantiations pair up; the table has old name, new name, hash, and VGPRs / SGPRs / spilled VGPRs /
 scratch bytes of both sides.  Exit status 1 if the two multisets of hashes differ, a body refers to a kernel by name
 (the names would then enter the hash; a device variable's name does, rightly), or a pair differs in one of the four numbers.
+
+    python tools/isa_compare.py --by-name old.s new.s
+
+pairs the kernels by NAME instead, for a change that touches the bodies: same / CHANGED with the four numbers of both sides, and
+whether the body's hash is the same.  Exit status 1 if the two sets of names differ, or a kernel uses more VGPRs, spills more or has
+more scratch than before (SGPRs may move: they do not limit occupancy on gfx950 below 106).
 """
 import collections
 import hashlib
@@ -56,7 +62,29 @@ def demangle(names):
     return {n: re.sub(r"^void |\((?:[^()]|\([^()]*\))*\)$", "", d) for n, d in zip(names, got)}
 
 
+def by_name(old, new, old_path, new_path):
+    pretty = demangle(sorted(set(old) | set(new)))
+    bad = changed = 0
+    print("# %d kernels in %s, %d in %s, paired by name; columns: vgpr / sgpr / spilled vgpr / scratch bytes (old -> new), body, name"
+          % (len(old), old_path.split("/")[-1], len(new), new_path.split("/")[-1]))
+    for name in sorted(set(old) | set(new), key=lambda n: pretty[n]):
+        if name not in old or name not in new:
+            bad += 1
+            print("%-8s  %-44s  %-9s  %s" % ("ADDED" if name in new else "MISSING", "/".join(map(str, (new.get(name) or old[name])[1])), "", pretty[name]))
+            continue
+        (ho, mo), (hn, mn) = old[name], new[name]
+        worse = mn[0] > mo[0] or mn[2] > mo[2] or mn[3] > mo[3]
+        bad += worse
+        changed += mo != mn
+        print("%-8s  %-44s  %-9s  %s" % ("MORE" if worse else "same" if mo == mn else "CHANGED", "/".join(map(str, mo)) + ("" if mo == mn else " -> " + "/".join(map(str, mn))),
+                                          "same body" if ho == hn else "new body", pretty[name]))
+    print("# %s" % ("%d kernels, none with more VGPRs, spills or scratch; %d with other SGPR counts" % (len(old), changed) if not bad else "%d with MORE VGPRs, spills or scratch, or unpaired" % bad))
+    return 1 if bad else 0
+
+
 def main():
+    if sys.argv[1] == "--by-name":
+        return by_name(kernels(sys.argv[2]), kernels(sys.argv[3]), sys.argv[2], sys.argv[3])
     old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
     by_hash = collections.defaultdict(list)
     for name, (h, _) in new.items():
