@@ -22,12 +22,18 @@ Operand families (one test id each, per kernel class and selector):
            (u32 partial sums folded every 64 / 8 rows).
 
 The CPU half (not marked gpu) asserts on the oracle alone that the operands are what they claim to be.
+
+Every gate here reads the all-zero second input with neg0 = neg1 = 0 and starts from a plain gate's test polynomial.  The
+descriptors with two real inputs -- BCE_XOR, BCE_PAIR, the preparation under negations, the persistent kernel -- run on this
+file's row table, key families and steering in tests/test_gpu_worst_case_ops.py; _tail_accumulators (an offset) and
+_rotated_tail_targets (a pair's second tail) build their tails' boundary accumulators.
 """
 import functools
 
 import numpy as np
 import pytest
 
+import pair_model as pm
 import worst_case as wc
 
 gpu = pytest.mark.gpu
@@ -488,14 +494,21 @@ def _round_boundaries(o, count=64):
     return ts, vals
 
 
-def _tail_accumulators(o, rng):
-    """accumulators [count][2][N]: component 0 holds the boundary values (directly at coefficient 0, negated elsewhere: the
-    extraction reads a(X^-1)), acc[1][0] walks through 0, 1, Q - 1, the two residues round the conditional subtraction of
-    b + Q/8 + 1, and boundary values shifted by -(Q/8 + 1)"""
+def _tail_accumulators(o, rng, off=None):
+    """accumulators [count][2][N] for a tail that extracts b' = acc[1][0] + off (default Q/8 + 1, every gate's; 0: BCE_XOR's):
+    component 0 holds the boundary values (directly at coefficient 0, negated elsewhere: the extraction reads a(X^-1)),
+    acc[1][0] walks through 0, 1, Q - 1, the two residues round the conditional subtraction of b + off (off > 0), and
+    boundary values shifted by -off: with off = 0 the boundary values themselves, both neighbours of the first, the middle
+    and the last boundary (the last is the result qKS that wraps to 0 wherever it has a preimage)"""
     Q, N = o.params["Q"], o.N
+    off = Q // 8 + 1 if off is None else off
     _, vals = _round_boundaries(o)
     assert len(vals) <= N
-    b0 = [0, 1, Q - 1, Q - Q // 8 - 1, Q - Q // 8 - 2] + [(v - (Q // 8 + 1)) % Q for v in (vals[0], vals[1], vals[-2], vals[-1], vals[len(vals) // 2])]
+    if off:
+        b0 = [0, 1, Q - 1, Q - off, Q - off - 1] + [(v - off) % Q for v in (vals[0], vals[1], vals[-2], vals[-1], vals[len(vals) // 2])]
+    else:
+        mid = 2 * (len(vals) // 4)                  # vals = [below, at] per boundary
+        b0 = [0, 1, Q - 1, vals[0], vals[1], vals[mid], vals[mid + 1], vals[-2], vals[-1]]
     accs = rng.integers(0, Q, size=(len(b0), 2, N), dtype=np.uint64)
     for k, b in enumerate(b0):
         rot = vals[k % len(vals):] + vals[:k % len(vals)]
@@ -504,6 +517,30 @@ def _tail_accumulators(o, rng):
             accs[k, 0, N - i] = (Q - rot[i]) % Q       # a'_i = -a_{N-i}
         accs[k, 1, 0] = b
     return accs
+
+
+def _rotated_tail_targets(o, rng, pairs):
+    """[(pair word, target, A2)] for a pair's SECOND tail, one per accumulator of _tail_accumulators, the ordered pairs of
+    `pairs` in turn: A2 is the boundary accumulator of the default tail with, in component 0, 0 at the wrap index e mod N (the
+    word the rotation reads from coefficient 0) and Q - 1 at its neighbour below (read from coefficient N - 1), and 0 and
+    Q - 1 at two positions in the middle of the range the rotation negates; the target is X^(2N - e) A2, so that the second
+    tail of a pair whose shared accumulator is the target reads A2 itself (and the first tail the target)."""
+    Q, N = o.params["Q"], o.N
+    out = []
+    for k, A2 in enumerate(_tail_accumulators(o, rng)):
+        op, op2 = pairs[k % len(pairs)]
+        e = pm.exponent(o.params, op, op2)
+        lo, hi = (0, e % N) if e < N else (e % N, N)          # positions i of X^e p whose source word is negated
+        A2 = A2.copy()
+        A2[0, e % N], A2[0, (e - 1) % N] = 0, Q - 1
+        A2[0, (lo + hi) // 2], A2[0, (lo + hi) // 2 + 1] = 0, Q - 1
+        target = np.stack([pm.rotate(A2[j], (2 * N - e) % (2 * N), Q) for j in range(2)])
+        out.append((wc.pair_word(op, op2), target, A2))
+    return out
+
+
+# one ordered pair per distinct rotation exponent N/2, N, 3N/2
+EXPONENT_PAIRS = ((wc.AND, wc.OR), (wc.OR, wc.NOR), (wc.OR, wc.AND))
 
 
 TAIL_ROWS = [pytest.param(r, id=r.id) for r in ROWS if (r.cls, r.selector, r.method) in

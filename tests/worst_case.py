@@ -4,10 +4,16 @@ Honest keys and ciphertexts are close to uniform, so they sit in the middle of e
 speak about.  What is built here sits at the ends:
 
   * edge ciphertexts: every rotation exponent 0, N, odd, 2 mod 4, 0 mod 4 at once; b on the edges of every gate's window;
+  * two-operand cases (two_operand_cases): a chosen prepared word vector split into two real inputs under all four
+    negation combinations (the second a fixed cycle through 0, 1, q/4, q/2 +- 1, q/2, 3q/4, q - 1, the first solved, so
+    that most sums wrap mod q), for BCE_XOR (b on both sides of the four boundaries of its three-level polynomial), all
+    12 ordered pairs (b on the window edges of both gates; a = 0: the rotation works on the polynomial itself) and the
+    plain gates;
   * extreme keys: every bootstrapping / key-switching key word 0, 1 or the modulus minus one;
   * steered accumulators: the key of the first executed step is SOLVED so that the accumulator after that step is a
     polynomial pair the test chose (digits at -B/2 and B/2 - 1 in every row, residues round floor(Q/2), evaluation-form
-    words at (Q +- 1)/2 and Q - 1); the second step then decomposes, transforms and multiplies exactly that pair.
+    words at (Q +- 1)/2 and Q - 1); the second step then decomposes, transforms and multiplies exactly that pair.  The
+    polynomial the blind rotation starts from is the caller's (steered_keys' `poly`): the plain gates' by default.
 
 Crafted keys encrypt nothing.  Both sides (the oracle through import_keys_eval, the engine through import_keys_eval)
 evaluate the same function of the same words, and the tests compare them word for word.  All key words are reduced.
@@ -255,6 +261,118 @@ def test_vector(o, gate, b):
     return m
 
 
+# ---- two real operands: BCE_XOR, pairs, the preparation itself -------------------------------------------------------------
+XOR = 0x10006                                         # BCE_XOR (include/bce_gpu.h)
+PLAIN = (OR, AND, NOR, NAND)
+ORDERED_PAIRS = [(a, b) for a in PLAIN for b in PLAIN if a != b]
+NEGATIONS = ((0, 0), (1, 0), (0, 1), (1, 1))
+SWEEP = "sweep: "                                    # name prefix of the per-boundary b sweep (left out of the subset)
+
+
+def pair_word(op, op2):
+    """the descriptor word of a pair (the macro BCE_PAIR)"""
+    return op | ((op2 + 1) << 8)
+
+
+def is_pair(op):
+    return op != XOR and (op >> 8) != 0
+
+
+def op_name(op):
+    if op == XOR:
+        return "XOR"
+    return "PAIR(%s,%s)" % (GATE_NAMES[op & 0xFF], GATE_NAMES[(op >> 8) - 1]) if is_pair(op) else GATE_NAMES[op]
+
+
+def xor_b_values(q):
+    """prepared b of BCE_XOR on the ends of Z_q and on both sides of its four window boundaries k q/8, k = 1, 3, 5, 7"""
+    e = q // 8
+    return [0, q - 1] + [k * e - d for k in (1, 3, 5, 7) for d in (1, 0)]
+
+
+def op_b_values(q, op):
+    """the window-edge b values of any descriptor word (a pair rotates its first gate's polynomial)"""
+    return xor_b_values(q) if op == XOR else b_patterns(q, op & 0xFF)
+
+
+def lwe_not(q, ct):
+    """EvalNOT: (-a, q/4 - b); its own inverse"""
+    ct = np.asarray(ct, dtype=np.uint64)
+    out = (np.uint64(q) - ct) % np.uint64(q)
+    out[-1] = (q // 4 + q - int(ct[-1])) % q
+    return out
+
+
+def second_operand(q, n):
+    """the fixed second input: a cycle through 0, 1, q/4, q/2 - 1, q/2, q/2 + 1, 3q/4, q - 1, the b word >= q/2"""
+    cyc = (0, 1, q // 4, q // 2 - 1, q // 2, q // 2 + 1, 3 * q // 4, q - 1)
+    ct2 = np.array([cyc[(i + 1) % 8] for i in range(n + 1)], dtype=np.uint64)
+    ct2[n] = cyc[4 + n % 4]
+    return ct2
+
+
+def split_operands(q, prep, neg0, neg1):
+    """(ct1, ct2) with ct1' + ct2' = prep mod q word for word, x' = EvalNOT(x) where the flag is set: ct2 is second_operand,
+    ct1 is solved"""
+    prep = np.asarray(prep, dtype=np.uint64)
+    ct2 = second_operand(q, prep.size - 1)
+    eff2 = lwe_not(q, ct2) if neg1 else ct2
+    eff1 = (prep + np.uint64(q) - eff2) % np.uint64(q)
+    return (lwe_not(q, eff1) if neg0 else eff1), ct2
+
+
+def wrapped_sums(q, ct1, ct2, neg0, neg1):
+    """how many of the n + 1 word sums ct1' + ct2' reach q (and are reduced)"""
+    a = lwe_not(q, ct1) if neg0 else np.asarray(ct1, dtype=np.uint64)
+    b = lwe_not(q, ct2) if neg1 else np.asarray(ct2, dtype=np.uint64)
+    return int(((a + b) >= np.uint64(q)).sum())
+
+
+def two_operand_cases(o):
+    """[(name, op, ct1, ct2, neg0, neg1, prep)]: op is BCE_XOR, a pair word or a plain gate; prep is the sum of the (negated)
+    operands, chosen first and split by split_operands; the four (neg0, neg1) combinations rotate over the cases.
+      * BCE_XOR: every a pattern with one of the ten b values of xor_b_values in turn, and (SWEEP) with the one five further;
+        then (SWEEP) all ten under a=cycle;
+      * pairs: all 12 ordered pairs, a=0 (no step: the rotation works on the first gate's polynomial itself) with b next to an
+        edge, a=cycle with b on the first edge of op, then (SWEEP) on every other window edge of op and of op2;
+      * the four plain gates under every negation combination, b on a window edge, a=cycle: the preparation alone."""
+    q, n = o.params["q"], o.n
+    pats = a_patterns(o)
+    cyc = dict((nm, a) for nm, a, _ in pats)["a=cycle"]
+    out = []
+
+    def add(name, op, a, b):
+        neg0, neg1 = NEGATIONS[len(out) % 4]
+        prep = np.array(list(a) + [b], dtype=np.uint64)
+        ct1, ct2 = split_operands(q, prep, neg0, neg1)
+        out.append(("%s%s b=%d %s neg=%d%d" % (name[0], name[1], b, op_name(op), neg0, neg1), op, ct1, ct2, neg0, neg1, prep))
+
+    xb = xor_b_values(q)
+    for k, (name, a, _) in enumerate(pats):
+        add(("", name), XOR, a, xb[k % 10])
+        add((SWEEP, name), XOR, a, xb[(k + 5) % 10])
+    for b in xb:
+        add((SWEEP, "a=cycle"), XOR, cyc, b)
+    for k, (op, op2) in enumerate(ORDERED_PAIRS):
+        w = pair_word(op, op2)
+        edges = []
+        for e in gate_window(q, op) + gate_window(q, op2):
+            if e not in edges:
+                edges.append(e)
+        add(("", "a=0"), w, [0] * n, (edges[k % len(edges)] - 1) % q)
+        for t, b in enumerate(edges):
+            add((SWEEP if t else "", "a=cycle"), w, cyc, b)
+    for gate in PLAIN:
+        for t in range(4):
+            add(("", "a=cycle"), gate, cyc, b_patterns(q, gate)[2 + (gate + t) % 4])
+    return out
+
+
+def operand_subset(cases):
+    """the cases without the per-boundary b sweeps"""
+    return [x for x in cases if not x[0].startswith(SWEEP)]
+
+
 # ---- extreme keys ----------------------------------------------------------------------------------------------------
 BSK_PATTERNS = ("Q-1", "1", "0", "rows 0/Q-1", "uniform+forced")
 KSK_PATTERNS = ("qKS-1", "0", "uniform")
@@ -391,9 +509,11 @@ def _solve_rows(o, m, E, mono):
     return rows
 
 
-def steered_keys(o, targets, second, rng, gates=(AND, OR, NAND, NOR)):
+def steered_keys(o, targets, second, rng, gates=(AND, OR, NAND, NOR), poly=None):
     """One key set steering one ciphertext per target.  Returns (bsk, cases): cases = [(name, gate, prepared ciphertext,
     first-step-only prepared ciphertext, expected coefficient-form accumulator after the first step)].
+    `poly` (o, op, b) -> m makes the test polynomial the blind rotation of `op` starts from (default: test_vector, the plain
+    gates' own); `gates` may then hold any descriptor word: target t is steered under gates[t % len(gates)].
     GINX: ciphertext t has a[2t] and a[2t+1] non-zero only; the keys of coefficient 2t are solved (ek+; ek- = 0), those of
     2t+1 are the `second` pattern ('Q-1' or 'uniform').  AP: -a[2t] has two non-zero digits; the key of its low digit is
     solved, the key of its next digit is the `second` pattern.  The first-step-only ciphertext drops the second step."""
@@ -420,8 +540,9 @@ def steered_keys(o, targets, second, rng, gates=(AND, OR, NAND, NOR)):
             a1 |= 1                              # odd exponents where the context has them
         rows, tries = None, 0
         while rows is None:
-            b = (b_patterns(q, gate)[(t + tries) % 6] + tries // 6) % q
-            m = test_vector(o, gate, b)
+            cand = op_b_values(q, gate)
+            b = (cand[(t + tries) % len(cand)] + tries // len(cand)) % q
+            m = (poly or test_vector)(o, gate, b)
             if ginx:
                 e1 = ((q - a1) % q) * (2 * N // q)
                 x = np.zeros(N, dtype=np.uint64)
@@ -431,7 +552,7 @@ def steered_keys(o, targets, second, rng, gates=(AND, OR, NAND, NOR)):
             else:
                 rows = _solve_rows(o, m, E, None)
             tries += 1
-            assert tries < 6 * q, "no b gives a first step that can be steered (%s)" % name
+            assert tries < len(cand) * q, "no b gives a first step that can be steered (%s)" % name
         prep = np.zeros(n + 1, dtype=np.uint64)
         prep[n] = b
         first_only = prep.copy()

@@ -89,10 +89,7 @@ def _digits(o, acc):
 
 def _times(dct, ek, Q):
     """digits x one RGSW ciphertext ([2 dG][2][N]): [2][N], reduced"""
-    out = np.zeros(ek.shape[1:], dtype=np.uint64)
-    for l in range(ek.shape[0]):
-        out = (out + mulmod(dct[l][None, :], ek[l], Q)) % np.uint64(Q)
-    return out
+    return mulmod(dct[:, None, :], ek, Q).sum(axis=0, dtype=np.uint64) % np.uint64(Q)     # 2 dG <= 16 terms below Q < 2^41: no overflow
 
 
 def blind_rotate(o, m, prep):
@@ -105,6 +102,8 @@ def blind_rotate(o, m, prep):
     for i in range(o.n):
         a = (q - int(prep[i])) % q
         if p["method"] == GINX:   # acc += (dct x ek1) mono[a] + (dct x ek2) mono[-a]
+            if a == 0:
+                continue          # mono[0] = X^0 - 1 = 0: the step adds nothing, word for word
             dct, ipos = _digits(o, acc), (a * f) % (2 * N)
             r1, r2 = _times(dct, K.rgsw(i, 0), Q), _times(dct, K.rgsw(i, 1), Q)
             acc = (mulmod(r1, K.mono(ipos)[None, :], Q) + mulmod(r2, K.mono((2 * N - ipos) % (2 * N))[None, :], Q) + acc) % np.uint64(Q)
