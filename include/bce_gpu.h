@@ -407,6 +407,9 @@ int bce_debug_eval_stages(bce_ctx*, uint32_t n_desc, const bce_gate_desc* descs,
  * tools/openfhe_export/compare.py to replay OpenFHE's own tail records (kind BCE_GATEVEC_TAIL of bce_keyfile.h). */
 int bce_debug_tail(bce_ctx*, uint32_t count, const uint64_t* acc, const uint32_t* out_slots, uint64_t* lweN,
                    uint64_t* ks);
+/* Workgroups the separate tail kernels spread ONE bootstrap's key-switch rows over in a launch of `count` bootstraps
+ * (16, 8, 4, 2 or 1: the rule launch_tail itself applies).  Read-only; for tests that must know which split a launch ran. */
+uint32_t bce_debug_tail_split(const bce_ctx*, uint32_t count);
 /* forward (inverse=0) / inverse negacyclic NTT of `count` polys, in place, u64 [count][N];
  * forward output is in the engine's internal evaluation order. */
 int bce_debug_ntt(bce_ctx*, uint64_t* polys, uint32_t count, int inverse);

@@ -91,7 +91,7 @@ ENGINE_SYMBOLS = [
     "bce_export_ksk", "bce_pool_reserve", "bce_pool_slots", "bce_lwe_write", "bce_lwe_read",
     "bce_encrypt_bits", "bce_set_encrypt_seed", "bce_decrypt_bits", "bce_eval_gates", "bce_eval_gates_strided", "bce_synchronize",
     "bce_timing_reset", "bce_timing_get", "bce_timing_set_events", "bce_bytes_per_bootstrap", "bce_bytes_per_bootstrap_parts", "bce_forward_transforms_per_step", "bce_forward_units", "bce_forward_mfma", "bce_lazy_arithmetic", "bce_forward_mfma_tables", "bce_launch_capacity", "bce_rccl_available", "bce_rccl_version", "bce_rccl_unique_id", "bce_rccl_init", "bce_rccl_allgather", "bce_rccl_comm_info",
-    "bce_rccl_shutdown", "bce_debug_eval_stages", "bce_debug_ntt", "bce_debug_tail",
+    "bce_rccl_shutdown", "bce_debug_eval_stages", "bce_debug_ntt", "bce_debug_tail", "bce_debug_tail_split",
     "bce_dag_supported", "bce_dag_create", "bce_dag_create_pairs", "bce_dag_run", "bce_dag_destroy", "bce_dag_set_limits", "bce_dag_last_run", "bce_dag_debug_block_task",
     "bce_dag_set_checks", "bce_dag_set_expected",
     "bce_plan_create", "bce_plan_run_step", "bce_plan_run", "bce_plan_destroy",
@@ -187,6 +187,8 @@ def lib():
     L.bce_debug_eval_stages.argtypes = [vp, u32, vp, vp, vp, vp]
     L.bce_debug_ntt.argtypes = [vp, vp, u32, i32]
     L.bce_debug_tail.argtypes = [vp, u32, vp, vp, vp, vp]
+    L.bce_debug_tail_split.argtypes = [vp, u32]
+    L.bce_debug_tail_split.restype = C.c_uint32
     L.bce_dag_supported.argtypes = [vp]
     L.bce_dag_create.argtypes = [vp, u32, vp, vp, C.POINTER(vp)]
     L.bce_dag_create_pairs.argtypes = [vp, u32, vp, vp, C.POINTER(vp)]
@@ -578,6 +580,10 @@ class BinFHEContext:
         ks = np.zeros((slots.size, self.n + 1), dtype=np.uint64)
         self._ck(self._L.bce_debug_tail(self.h, slots.size, _p(acc), _p(slots), _p(lweN), _p(ks)))
         return lweN, ks
+
+    def debug_tail_split(self, count):
+        """workgroups the separate tail kernels spread one bootstrap over in a launch of `count` bootstraps (launch_tail's rule)"""
+        return int(self._L.bce_debug_tail_split(self.h, int(count)))
 
     def debug_ntt(self, polys, inverse=False):
         polys = np.array(polys, dtype=np.uint64, order="C")

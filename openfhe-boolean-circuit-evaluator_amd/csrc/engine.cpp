@@ -247,6 +247,10 @@ int derive_ctx(bce_ctx* c, u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 
         if (P.fwd_units && !env_off("BCE_FWD_MFMA")) {
             T.fwd = build_fwd_mfma_tables(Q, N, c->gBits, c->dG, c->psi);
             if (T.fwd.ok) { P.fwd_mfma = 1; P.w14 = T.fwd.w14; P.w14s = T.fwd.w14s; }
+            // The body is a two-workgroups-per-CU build and its byte matrices cost 6 KiB of LDS in front of the (n + 1)-word
+            // ciphertext region: where two such workgroups no longer fit a CU (n >= 896) the quarter-unit body stays, which
+            // fits up to n = 2431 (beyond that kernel_class reports one workgroup per CU)
+            if (P.fwd_mfma && 2 * kernel_class(P).lds_bytes > kLdsBytesPerCu) P.fwd_mfma = P.w14 = P.w14s = 0;
         }
     }
     P.pool_stride = n + 1;
@@ -1159,6 +1163,8 @@ int bce_debug_tail(bce_ctx* c, uint32_t count, const uint64_t* acc, const uint32
     if (ks && (rc = words_from_device(c, ks, d_ks.get(), (size_t)count * (c->n + 1), false))) return rc;
     return BCE_OK;
 }
+
+uint32_t bce_debug_tail_split(const bce_ctx* c, uint32_t count) { return c && count ? tail_split(c->P, count) : 0; }
 
 static int pool_pack(bce_ctx* c, const uint32_t* slots, uint32_t count, void* dev, int to_pool) {
     if (!c || !slots || !dev) return BCE_ERR_ARG;

@@ -187,7 +187,10 @@ int bce_dag_run(bce_ctx* c, bce_dag* g, uint32_t instances, uint32_t slot_stride
         wps = t1 <= t2 ? 2 : 4;
     }
     if (const char* e = std::getenv("BCE_DAG_WPS")) { if (e[0] == '2') wps = 2; else if (e[0] == '4') wps = 4; }
-    if (kernel_class(c->P).wg_per_cu_full == 1) wps = 2;   // the config-5 kernel: one 1,024-thread workgroup is all a CU's LDS holds
+    if (kernel_class(c->P).wg_per_cu_full == 1) wps = 2;   // a CU's LDS holds one workgroup (the config-5 kernel; the split-transform kernel at n >= 2432)
+    // the persistent kernel's own LDS (mailbox in front of the layout): where two such workgroups do not fit a CU although two
+    // of the per-frontier kernel do (n = 888..895 on the matrix-pipe build, 2424..2431 on the quarter-unit build), one per CU
+    if (wps == 4 && !c->P.is64 && 2 * bootstrap_dag_lds_bytes(c->P, 4) > kLdsBytesPerCu) wps = 2;
     if (const char* e = std::getenv("BCE_DAG_PLACE")) D.policy = e[0] == '0' ? 0u : 1u;
     const char* dbg = std::getenv("BCE_DAG_DEBUG");   // development: 'r' = re-arm only, 'd' = dry run (no bootstraps)
     if (dbg && dbg[0] == 'd') D.policy |= 2u;

@@ -1640,8 +1640,9 @@ KernelClass kernel_class(const DevParams& P) {
         k.fold_build = std::any_of(std::begin(kLatBuilds), std::end(kLatBuilds), [ap](const LatBuild& b) { return b.ap == ap && b.fwd != Fwd::Rows; });
         k.dag = fused_tail_fits(P);
         k.wg_per_cu_lone = lat_variant(P, true).wps / 2;     // LatBuild::wps counts waves per SIMD; a workgroup brings two
-        k.wg_per_cu_full = lat_variant(P, false).wps / 2;
         k.lds_bytes = blind_rotate_lat_lds_bytes(P, lat_variant(P, false));
+        // LDS-bound like kernel_class64: the layout ends in n + 1 words, so a large LWE dimension leaves a CU one workgroup
+        k.wg_per_cu_full = std::min<u32>(lat_variant(P, false).wps / 2, (u32)std::max<size_t>(1, kLdsBytesPerCu / k.lds_bytes));
     } else {
         k.wg_per_cu_lone = 1;
         k.wg_per_cu_full = k.occupancy_target;
@@ -1710,6 +1711,11 @@ hipError_t launch_dag_rearm(const DagRearm& D, hipStream_t s) {
     return hipGetLastError();
 }
 
+// dynamic LDS of one workgroup of the 32-bit persistent kernel: the worker's mailbox in front of the layout of lat_bootstrap
+size_t bootstrap_dag_lds_bytes(const DevParams& P, int wps) {
+    return blind_rotate_lat_lds_bytes(P, lat_variant(P, wps <= 2)) + kDagMailboxWords * 4;
+}
+
 hipError_t launch_bootstrap_dag(const DevParams& P, const DevParams* d_P, const DagParams* d_params, int wps, u32 grid, hipStream_t s) {
     if (!dag_kernel_available(P)) return hipErrorInvalidValue;
     if (P.is64) return launch_bootstrap_dag64(P, d_P, d_params, grid, s);
@@ -1720,7 +1726,7 @@ hipError_t launch_bootstrap_dag(const DevParams& P, const DevParams* d_P, const 
         return k_bootstrap_dag<LatVariant<b.wps, b.ap, true, b.fwd>>;
     });
     if (!k) return hipErrorInvalidValue;
-    const size_t lds = blind_rotate_lat_lds_bytes(P, v) + kDagMailboxWords * 4;   // + the worker's mailbox in front
+    const size_t lds = bootstrap_dag_lds_bytes(P, wps);
     return launch_kernel_lds(k, dim3(grid), dim3(512), lds, s, LaunchEvents{}, d_P, d_params);
 }
 
@@ -1757,6 +1763,7 @@ hipError_t launch_blind_rotate(const DevParams& P, const bce_gate_desc* d, u32 n
         if (tail_fused) *tail_fused = fuse;
         DevParams Pl = P;
         if (x1 || grid.x <= 2 * P.cu_count) Pl.xcd_gate = nullptr;            // one round: every workgroup starts at once anyway
+        if (kc.wg_per_cu_full != 2) Pl.xcd_gate = nullptr;                     // the gate counts two resident workgroups per CU
         if (Pl.xcd_gate) {
             const hipError_t e = hipMemsetAsync(Pl.xcd_gate, 0, 16 * 32 * sizeof(u32), s);
             if (e != hipSuccess) return e;

@@ -177,6 +177,9 @@ hipError_t launch_dag_rearm(const DagRearm& D, hipStream_t s);
 hipError_t launch_bootstrap_dag(const DevParams& P, const DevParams* d_P, const DagParams* d_params, int wps, u32 grid,
                                 hipStream_t s);
 inline bool dag_kernel_available(const DevParams& P) { return kernel_class(P).dag; }
+// dynamic LDS of one workgroup of the 32-bit persistent kernel (split-transform family; the mailbox included): what
+// bce_dag_run sizes its grid by, so that it never launches more workgroups than are resident
+size_t bootstrap_dag_lds_bytes(const DevParams& P, int wps);
 
 // Timestamps of a launch without event packets of their own in the queue: start / stop are attached to the kernel's
 // dispatch (hipExtLaunchKernel) -- what hipEventRecord before and after a kernel costs on the device timeline (5-10 us of
@@ -224,6 +227,7 @@ hipError_t launch_blind_rotate(const DevParams& P, const bce_gate_desc* d_descs,
 // the debug buffers then have 2 n_boot rows, the second outputs in the second half).  A blind-rotation kernel that fuses
 // the tail runs the second pass itself.
 size_t tail_partial_words(const DevParams& P, u32 boots);
+u32 tail_split(const DevParams& P, u32 boots);   // workgroups launch_tail spreads one bootstrap's rows over (16 .. 1)
 hipError_t launch_tail(const DevParams& P, const bce_gate_desc* d_descs, u32 n_desc, u32 instances, u32 slot_stride,
                        const void* acc_in /* u32 or u64 words by P.is64 */, u64* partial, u32* dbg_lweN, u32* dbg_ks,
                        hipStream_t s, LaunchEvents ev = {}, bool pairs = false);   // ev.start on the first kernel, ev.stop on the last
