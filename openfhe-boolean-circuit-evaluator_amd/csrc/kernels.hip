@@ -37,6 +37,7 @@
 namespace bce {
 
 #include "phase_prof.hpp"
+#include "gate_front.hpp"
 #include "fused_tail.hpp"
 #include "dag_sched.hpp"
 #ifdef BCE_PHASE_PROF
@@ -107,7 +108,6 @@ __device__ __forceinline__ u32 barrett_fold(u64 x, u32 c32, u32 Q, u32 shift, u3
 // ---------------------------------------------------------------------------------------
 // LDS polynomial layout and register passes
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ u32 phys(u32 j) { return j + ((j >> 6) << 2); }
 
 template <int LOGN>
 struct Cfg {
@@ -810,56 +810,18 @@ __device__ __forceinline__ void ginx_mac_tail_redc(const PT& P, __amdgpu_buffer_
     *reinterpret_cast<uint4*>(accw) = make_uint4(a[0], a[1], a[2], a[3]);
 }
 
-// Common start of a gate bootstrap: twiddles into LDS, EvalBinGate's LWE preparation (ct1 + ct2 with the
-// folded EvalNOTs, or ct + q/4 for a refresh) into av[0..n], BootstrapGateCore's test vector into acc
-// (evaluation form).  Ends with a workgroup barrier.
+// Common start of a 32-bit gate bootstrap: twiddles into LDS, the LWE preparation into av[0..n] and the test polynomial
+// into acc (gate_front.hpp), then its forward transform: acc in evaluation form.  Ends with a workgroup barrier.
 template <int LOGN, bool LAZY, u32 T, typename PT>
 __device__ __forceinline__ void bootstrap_prologue(const PT& P, const bce_gate_desc& g, u32 soff, uint2* twf, u32* acc,
                                                    u32* av, u32 tid, u32 lane, u32 wave) {
     using C = Cfg<LOGN>;
     constexpr int N = C::N, NP = C::NP;
-    const u32 Q = P.Q, q = P.q, qm = q - 1, n = P.n;
+    const u32 Q = P.Q, q = P.q;
     for (u32 i = tid; i < (u32)N; i += T) twf[i] = P.tw_f[i];
-    const u32 op = g.op & 0xFFu;   // bits 8..15: the second gate of a pair (BCE_PAIR), the tail's business
-    {   // EvalBinGate LWE prep with folded EvalNOT: (-a, q/4 - b)
-        const u32* in0 = P.pool + (size_t)(g.in0 + soff) * P.pool_stride;
-        const u32* in1 = P.pool + (size_t)(g.in1 + soff) * P.pool_stride;
-        const bool two = op <= kXorGate;
-        for (u32 i = tid; i <= n; i += T) {
-            u32 v0 = in0[i];
-            if (g.neg0) v0 = ((i == n ? (q >> 2) : 0u) - v0) & qm;
-            u32 v = v0;
-            if (two) {
-                u32 v1 = in1[i];
-                if (g.neg1) v1 = ((i == n ? (q >> 2) : 0u) - v1) & qm;
-                v = (op == BCE_XOR_FAST || op == BCE_XNOR_FAST) ? (2u * (v0 - v1)) & qm : (v0 + v1) & qm;
-            } else if (i == n) {
-                v = (v0 + (q >> 2)) & qm;  // Bootstrap(): ct + q/4
-            }
-            av[i] = v;
-        }
-    }
+    lwe_prepare<T>(P, g, soff, q, av, tid);
     __syncthreads();
-    {   // BootstrapGateCore: acc = (0, m(X)), m sparse with +-(Q/8+1); BCE_XOR: 0 and +-2(Q/8+1) (xor_level)
-        const u32 b = av[n];
-        const u32 q1 = gate_const(op, q), q2 = (q1 + (q >> 1)) & qm;
-        const u32 pos = P.Q8p1, neg = Q - P.Q8p1;
-        for (u32 j = tid; j < (u32)N; j += T) {
-            u32 v = 0;
-            if (j % P.factor == 0) {
-                u32 t = (b - j / P.factor) & qm;
-                if (op == kXorGate) {
-                    const int lv = xor_level(t, q);
-                    v = lv > 0 ? 2 * pos : lv < 0 ? Q - 2 * pos : 0u;
-                } else {
-                    bool in = (q1 < q2) ? (t >= q1 && t < q2) : !(t >= q2 && t < q1);
-                    v = in ? neg : pos;
-                }
-            }
-            acc[phys(j)] = 0;
-            acc[NP + phys(j)] = v;
-        }
-    }
+    test_polynomial<T, (u32)N>(P, g.op & 0xFFu, q, av[P.n], Q, acc, acc + NP, tid);
     __syncthreads();
     if (wave == 0) ntt_forward_wave<LOGN, LAZY>(acc + NP, twf, lane, Q, P.mu32);
     __syncthreads();
@@ -888,7 +850,7 @@ __global__ __launch_bounds__(128 * DG, (OCC * 2 * DG + 3) / 4) void k_blind_rota
     const u32 tid = threadIdx.x;
     const u32 lane = tid & 63;
     const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: keep it (and wave*NP) in SGPRs
-    const u32 Q = P.Q, q = P.q, qm = q - 1, n = P.n;
+    const u32 Q = P.Q, q = P.q, n = P.n;
 
     const bce_gate_desc g = descs[blockIdx.x % n_desc];
     const u32 soff = (blockIdx.x / n_desc) * slot_stride;
@@ -908,16 +870,14 @@ __global__ __launch_bounds__(128 * DG, (OCC * 2 * DG + 3) / 4) void k_blind_rota
         u32 ap = 0, rowb = 0;
         const u32* bk;
         if constexpr (!AP) {
-            ap = ((q - av[step]) & qm) * P.factor;  // exponent of the monomial, in [0, 2N)
-            if (ap == 0) continue;                   // X^0 - 1 = 0: AddToAcc adds nothing
+            ap = ginx_exponent(P, q, av[step]);
+            if (ap == 0) continue;
             bk = P.bsk + (size_t)step * 2 * rgsw;
             rowb = step * (2 * rgsw * 4);
         } else {
             const u32 i = step / P.dR, k = step - i * P.dR;
-            u32 aI = (q - av[i]) & qm;
-            for (u32 t = 0; t < k; ++t) aI /= P.baseR;
-            const u32 a0 = aI % P.baseR;
-            if (a0 == 0) continue;                   // rgsw-acc-dm.cpp EvalAcc: digit 0 is skipped
+            const u32 a0 = ap_digit(P, q, av[i], k);
+            if (a0 == 0) continue;
             bk = P.bsk + (((size_t)i * P.baseR + a0) * P.dR + k) * rgsw;
         }
         // (1) two waves: INTT of acc[c], SignedDigitDecompose -> dct[2l + c] (coefficient form)
@@ -1293,7 +1253,7 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
     const u32 tid = tid_;
     const u32 lane = tid & 63;
     const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const u32 Q = P.Q, q = P.q, qm = q - 1, n = P.n;
+    const u32 Q = P.Q, q = P.q, n = P.n;
     if constexpr (WPS >= 4 && !PERSIST) {
         // XCD start gate of a multi-round launch (round 4): the workgroups that take over an XCD's slots as the previous round
         // retires start their bootstraps together, so that they walk the key in lock-step (one L2 fill per row and XCD) like
@@ -1364,15 +1324,13 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
     for (u32 step = 0; step < nsteps; ++step) {
         u32 ap = 0, rowb;
         if constexpr (!AP) {
-            ap = ((q - av[step]) & qm) * P.factor;
+            ap = ginx_exponent(P, q, av[step]);
             if (ap == 0) continue;  // acc unchanged: xa still holds its pass 0
             rowb = step * (2 * rgsw * 4);
         } else {
             const u32 i = step / P.dR, kd = step - i * P.dR;
-            u32 aI = (q - av[i]) & qm;
-            for (u32 t = 0; t < kd; ++t) aI /= P.baseR;
-            const u32 a0 = aI % P.baseR;
-            if (a0 == 0) continue;      // rgsw-acc-dm.cpp EvalAcc: digit 0 is skipped
+            const u32 a0 = ap_digit(P, q, av[i], kd);
+            if (a0 == 0) continue;
             rowb = (((i * P.baseR + a0) * P.dR + kd) * rgsw) * 4u;
         }
         // key rows of this step, requested during phase 1 (a quarter at the start of each inverse pass),
@@ -1521,23 +1479,7 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
         if constexpr (WPS >= 4) __builtin_amdgcn_s_setprio(0);
         __syncthreads();
         // rowidx and the partial sums live in the digit rows + exchange buffers (LatLds::tail_bytes = 54 KiB, all dead now)
-        u32* rowidx = dct;
-        u64* red = reinterpret_cast<u64*>(dct + ((N * P.dKS + 3) & ~3u));
-        u32* outp = P.pool + (size_t)(g.out + soff) * P.pool_stride;
-        const u64 off = tail_offset<u32>(P, g.op);
-        if (P.ksk_u16) fused_tail<uint16_t, T>(P, acc, rowidx, red, outp, boot, dbg_lweN, dbg_ks, off);
-        else fused_tail<u32, T>(P, acc, rowidx, red, outp, boot, dbg_lweN, dbg_ks, off);
-        // a pair descriptor (BCE_PAIR) runs the tail a second time, on X^e * acc, into slot out + 1 (debug rows: a second block
-        // of gridDim.x rows); the branch is workgroup-uniform, the barrier frees rowidx / red.  The dataflow kernel runs the
-        // same pass (bce_dag_create_pairs): g came from D.tasks[t] through the constant address space, so the test is scalar,
-        // and both rows are stored before the worker's drain / barrier / release (dag_worker).  Its debug pointers are null:
-        // the row index stays `boot`.
-        if ((g.op >> 8) & 0xFFu) {   // (bit 16 is BCE_XOR's, not a pair's)
-            __syncthreads();
-            const u32 e = pair_rotation(P, g.op), row = PERSIST ? boot : boot + gridDim.x;
-            if (P.ksk_u16) fused_tail<uint16_t, T>(P, acc, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, off, e);
-            else fused_tail<u32, T>(P, acc, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, off, e);
-        }
+        fused_tail_outputs<T, PERSIST>(P, g, soff, acc, dct, reinterpret_cast<u64*>(dct + ((N * P.dKS + 3) & ~3u)), boot, dbg_lweN, dbg_ks);
     }
 }
 
@@ -1549,13 +1491,12 @@ __global__ __launch_bounds__(V::T, V::WPS) void k_blind_rotate_lat(DevParams P, 
     lat_bootstrap<V, false>(P, descs[blockIdx.x % n_desc], (blockIdx.x / n_desc) * slot_stride, blockIdx.x, smem, acc_out, dbg_lweN, dbg_ks);
 }
 
-// LDS the fused tail needs inside the digit rows + exchange buffers of k_blind_rotate_lat (T = 512 threads)
+// the fused tail's scratch inside the digit rows + exchange buffers of lat_bootstrap (512 threads)
 bool fused_tail_fits(const DevParams& P) {
-    const size_t N = P.N;
-    const size_t VW = P.ksk_u16 ? 8 : 4, G = (P.n + VW) / VW, Gv = G < 512 ? G : 512, RW = (Gv + 63) / 64, SL = 8 / RW;
-    const size_t need = ((N * P.dKS + 3) & ~(size_t)3) * 4 + SL * Gv * VW * 8;
-    return (size_t)P.n + 1 <= 512 * VW && RW <= 8 && need <= LatLds::tail_bytes;
+    return TailGeom::fused_fits(P.n, P.ksk_u16, 64 * LatLds::R, (size_t)P.N * P.dKS, LatLds::tail_bytes);
 }
+static_assert(!TailGeom::fused_fits(511, true, 512, 1024 * 7, LatLds::tail_bytes), "n = 511, u16 rows: dKS = 7 does not fit");
+static_assert(TailGeom::fused_fits(511, true, 512, 1024 * 5, LatLds::tail_bytes), "n = 511, u16 rows: dKS = 5 (53,248 bytes) fits");
 
 // ---- which build a launch runs ---------------------------------------------------------------------------------------
 // The builds that exist, as (waves per SIMD, AP, forward body); k_bootstrap_dag has each with the tail fused,
@@ -1800,94 +1741,28 @@ __global__ __launch_bounds__(256) void k_tail_gather(DevParams P, u32 S, const A
                                                      const bce_gate_desc* __restrict__ descs, u32 n_desc) {
     extern __shared__ __align__(16) u32 smem[];
     constexpr u32 VW = 16 / sizeof(KT);  // elements per 16-byte load
-    const u32 N = P.N, n = P.n, qKS = P.qKS, B = P.baseKS, D = P.dKS;
-    const u64 Q = sizeof(AW) == 8 ? P.Q64 : (u64)P.Q;
-    const u32 tid = threadIdx.x, lane = tid & 63;
+    const u32 N = P.N, n = P.n, tid = threadIdx.x, lane = tid & 63;
     const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const u32 boot = blockIdx.x / S, s = blockIdx.x - boot * S;
     u32 rot = 0, dbg_row = boot;
     if constexpr (PAIR) {
         const u32 op = descs[boot % n_desc].op;
-        if (!((op >> 8) & 0xFFu)) return;
+        if (!pair_second(op)) return;
         rot = pair_rotation(P, op);
         dbg_row = boot + gridDim.x / S;
     }
-    const u32 ni = N / S, i0 = s * ni, LR = ni * D;  // coefficients / rows of this workgroup
-    u32* rowidx = smem;                                   // [LR] row number (i*B + digit)*D + j
+    const u32 ni = N / S, LR = ni * P.dKS;  // coefficients / rows of this workgroup
+    u32* rowidx = smem;                                   // [LR] row numbers
     u64* red = reinterpret_cast<u64*>(smem + ((LR + 3) & ~3u));  // [slices][Gv*VW] or [256] (scalar pass)
-    const AW* a0 = acc_in + (size_t)boot * 2 * N;
-
-    // Transpose (X -> X^-1) of acc[0]: a'_0 = a_0, a'_{N-i} = -a_i ; then ModSwitch(Q -> qKS)
-    for (u32 ii = tid; ii < ni; ii += 256) {
-        const u32 i = i0 + ii;
-        const u64 v = rotated_coef(a0, i == 0 ? 0 : N - i, rot, N, Q, i != 0);
-        u32 at = round_qQ(v, qKS, Q);
-        if (dbg_lweN) dbg_lweN[(size_t)dbg_row * (N + 1) + i] = at;
-        for (u32 j = 0; j < D; ++j) {
-            rowidx[ii * D + j] = (i * B + at % B) * D + j;
-            at /= B;
-        }
-    }
+    tail_row_numbers(P, acc_in + (size_t)boot * 2 * N, rot, s * ni, ni, tid, 256u, rowidx, dbg_lweN, dbg_row);
     __syncthreads();
-
+    const TailGeom tg(n, VW == 8, 256);                   // one group per lane of up to 4 waves
+    tail_gather_rows<KT, 8>(P, tg, wave, lane, rowidx, LR, red);
+    __syncthreads();
     const KT* __restrict__ ksk = reinterpret_cast<const KT*>(P.ksk);
-    const u32 G = (n + VW) / VW;                 // 16-byte groups holding elements 0..n
-    const u32 Gv = G < 256 ? G : 256;            // groups of the vector pass (one per lane of up to 4 waves)
-    const u32 RW = (Gv + 63) / 64, SL = 4 / RW;  // waves per row, row slices per workgroup
-    const u32 slice = wave / RW, group = (wave - slice * RW) * 64 + lane;
-    u64 tot[VW];
-#pragma unroll
-    for (u32 e = 0; e < VW; ++e) tot[e] = 0;
-    if (slice < SL && group < Gv) {
-        // u32 running sums are folded into the u64 totals every CH rows (CH * qKS <= 2^32: no wrap)
-        const u32 CH = P.ks_chunk;
-        constexpr u32 U = 8;  // rows in flight per lane
-        u32 r = slice;
-        while (r < LR) {
-            u32 run[VW];
-#pragma unroll
-            for (u32 e = 0; e < VW; ++e) run[e] = 0;
-            const u32 rend = (LR - r > CH * SL) ? r + CH * SL : LR;
-            for (; r + (U - 1) * SL < rend; r += U * SL) {
-                uint4 v[U];
-#pragma unroll
-                for (u32 u = 0; u < U; ++u) {
-                    const u32 row = __builtin_amdgcn_readfirstlane(rowidx[r + u * SL]);
-                    v[u] = reinterpret_cast<const uint4*>(ksk + (size_t)row * P.ksk_stride)[group];
-                }
-#pragma unroll
-                for (u32 u = 0; u < U; ++u) {
-                    if constexpr (sizeof(KT) == 2) {
-                        run[0] += v[u].x & 0xFFFFu; run[1] += v[u].x >> 16; run[2] += v[u].y & 0xFFFFu; run[3] += v[u].y >> 16;
-                        run[4] += v[u].z & 0xFFFFu; run[5] += v[u].z >> 16; run[6] += v[u].w & 0xFFFFu; run[7] += v[u].w >> 16;
-                    } else {
-                        run[0] += v[u].x; run[1] += v[u].y; run[2] += v[u].z; run[3] += v[u].w;
-                    }
-                }
-            }
-            for (; r < rend; r += SL) {
-                const u32 row = __builtin_amdgcn_readfirstlane(rowidx[r]);
-                const uint4 v = reinterpret_cast<const uint4*>(ksk + (size_t)row * P.ksk_stride)[group];
-                if constexpr (sizeof(KT) == 2) {
-                    run[0] += v.x & 0xFFFFu; run[1] += v.x >> 16; run[2] += v.y & 0xFFFFu; run[3] += v.y >> 16;
-                    run[4] += v.z & 0xFFFFu; run[5] += v.z >> 16; run[6] += v.w & 0xFFFFu; run[7] += v.w >> 16;
-                } else {
-                    run[0] += v.x; run[1] += v.y; run[2] += v.z; run[3] += v.w;
-                }
-            }
-#pragma unroll
-            for (u32 e = 0; e < VW; ++e) tot[e] += run[e];
-        }
-#pragma unroll
-        for (u32 e = 0; e < VW; ++e) red[(size_t)slice * Gv * VW + group * VW + e] = tot[e];
-    }
-    __syncthreads();
+    const u32 Gv = tg.Gv;
     u64* out = partial + ((size_t)boot * S + s) * (n + 1);
-    for (u32 k = tid; k < Gv * VW && k <= n; k += 256) {
-        u64 sum = 0;
-        for (u32 sl = 0; sl < SL; ++sl) sum += red[(size_t)sl * Gv * VW + k];
-        out[k] = sum;
-    }
+    for (u32 k = tid; k < Gv * VW && k <= n; k += 256) out[k] = tail_slice_sum(tg, red, k);
     // elements beyond the vector pass (n + 1 > 256 groups, e.g. the single b column of n = 1024 with u32 rows):
     // all threads split the rows, one element at a time
     for (u32 k = Gv * VW; k <= n; ++k) {
@@ -1908,34 +1783,21 @@ template <typename AW, bool PAIR>
 __global__ __launch_bounds__(256) void k_tail_finish(DevParams P, const bce_gate_desc* __restrict__ descs, u32 n_desc, u32 slot_stride,
                                                      u32 S, const AW* __restrict__ acc_in, const u64* __restrict__ partial,
                                                      u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks) {
-    const u32 N = P.N, n = P.n, qKS = P.qKS;
-    const u64 Q = sizeof(AW) == 8 ? P.Q64 : (u64)P.Q;
-    const u32 boot = blockIdx.x;
+    const u32 N = P.N, n = P.n, boot = blockIdx.x;
     const bce_gate_desc g = descs[boot % n_desc];
     const u64 off = tail_offset<AW>(P, g.op);
     u32 rot = 0, dbg_row = boot;
     if constexpr (PAIR) {
-        if (!((g.op >> 8) & 0xFFu)) return;
+        if (!pair_second(g.op)) return;
         rot = pair_rotation(P, g.op);
         dbg_row = boot + gridDim.x;
     }
     u32* out = P.pool + (size_t)(g.out + (PAIR ? 1u : 0u) + (boot / n_desc) * slot_stride) * P.pool_stride;
     const u64* part = partial + (size_t)boot * S * (n + 1);
-    // KeySwitch: a' = -sum_rows A[row], b' = b - sum_rows B[row]   (mod qKS), b = acc[1][0] + off (Q/8 + 1; BCE_XOR: 0) mod-switched
     for (u32 k = threadIdx.x; k <= n; k += 256) {
         u64 sum = 0;
         for (u32 s = 0; s < S; ++s) sum += part[(size_t)s * (n + 1) + k];
-        const u32 sm = (u32)(sum % qKS);
-        u32 base = 0;
-        if (k == n) {
-            u64 b = rotated_coef(acc_in + (size_t)boot * 2 * N + N, 0, rot, N, Q, false) + off;
-            b = b >= Q ? b - Q : b;
-            base = round_qQ(b, qKS, Q);
-            if (dbg_lweN) dbg_lweN[(size_t)dbg_row * (N + 1) + N] = base;
-        }
-        const u32 v = base >= sm ? base - sm : base + qKS - sm;
-        if (dbg_ks) dbg_ks[(size_t)dbg_row * (n + 1) + k] = v;
-        out[k] = round_qQ(v, P.q, qKS);  // ModSwitch(qKS -> q)
+        out[k] = tail_finish_word(P, sum, k, acc_in + (size_t)boot * 2 * N, rot, off, dbg_lweN, dbg_ks, dbg_row);
     }
 }
 
@@ -1951,10 +1813,7 @@ hipError_t launch_tail(const DevParams& P, const bce_gate_desc* d, u32 n_desc, u
                        const void* acc_in, u64* partial, u32* dbg_lweN, u32* dbg_ks, hipStream_t s, LaunchEvents ev, bool pairs) {
     const u32 boots = n_desc * instances, S = tail_split(P, boots);
     const dim3 grid(boots * S), block(256);
-    const u32 VW = P.ksk_u16 ? 8 : 4, G = (P.n + VW) / VW, Gv = G < 256 ? G : 256, RW = (Gv + 63) / 64, SL = 4 / RW;
-    const size_t LR = (size_t)P.N / S * P.dKS;
-    const size_t red_words = std::max<size_t>((size_t)SL * Gv * VW, 256);
-    const size_t lds = ((LR + 3) & ~(size_t)3) * sizeof(u32) + red_words * sizeof(u64);
+    const size_t lds = TailGeom(P.n, P.ksk_u16, 256).lds_bytes((size_t)P.N / S * P.dKS, 256);   // 256: the scalar pass's reduction
     // the first gather carries the start timestamp, the last finish the stop (plain launches when none was asked for)
     const LaunchEvents none{}, first{ev.start, nullptr}, last{nullptr, ev.stop};
     auto go = [&](auto kern, dim3 g, size_t l, LaunchEvents e, auto... args) { return launch_kernel(kern, g, block, l, s, e, args...); };

@@ -20,6 +20,7 @@
 #include "phase_prof.hpp"
 
 namespace bce {
+#include "gate_front.hpp"
 #include "fused_tail.hpp"
 #include "dag_sched.hpp"
 #ifdef BCE_PHASE_PROF
@@ -57,7 +58,6 @@ __device__ __forceinline__ u64 reduce128(U128 a, u64 Q, u64 c64, u64 mu64) {
     return csub(r, Q);
 }
 
-__device__ __forceinline__ u32 phys(u32 j) { return j + ((j >> 6) << 2); }
 constexpr u32 padded_words(u32 logn) { return (1u << logn) + ((1u << logn) >> 6) * 4; }   // of a polynomial: phys(N)
 
 template <int LOGN>
@@ -261,49 +261,12 @@ __global__ __launch_bounds__(128 * DG) void k_blind_rotate64(DevParams P, const 
 
     const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const u64 Q = P.Q64;
-    const u32 q = P.q, qm = q - 1, n = P.n;
+    const u32 q = P.q, n = P.n;
     const bce_gate_desc g = descs[blockIdx.x % n_desc];
     const u32 soff = (blockIdx.x / n_desc) * slot_stride;
-    const u32 op = g.op & 0xFFu;   // bits 8..15: the second gate of a pair (BCE_PAIR), the tail's business
-    {
-        const u32* in0 = P.pool + (size_t)(g.in0 + soff) * P.pool_stride;
-        const u32* in1 = P.pool + (size_t)(g.in1 + soff) * P.pool_stride;
-        const bool two = op <= kXorGate;
-        for (u32 i = tid; i <= n; i += T) {
-            u32 v0 = in0[i];
-            if (g.neg0) v0 = ((i == n ? (q >> 2) : 0u) - v0) & qm;
-            u32 v = v0;
-            if (two) {
-                u32 v1 = in1[i];
-                if (g.neg1) v1 = ((i == n ? (q >> 2) : 0u) - v1) & qm;
-                v = (op == BCE_XOR_FAST || op == BCE_XNOR_FAST) ? (2u * (v0 - v1)) & qm : (v0 + v1) & qm;
-            } else if (i == n) {
-                v = (v0 + (q >> 2)) & qm;
-            }
-            av[i] = v;
-        }
-    }
+    lwe_prepare<T>(P, g, soff, q, av, tid);
     __syncthreads();
-    {
-        const u32 b = av[n];
-        const u32 q1 = gate_const(op, q), q2 = (q1 + (q >> 1)) & qm;
-        const u64 pos = P.Q8p1_64, neg = Q - P.Q8p1_64;
-        for (u32 j = tid; j < (u32)N; j += T) {
-            u64 v = 0;
-            if (j % P.factor == 0) {
-                u32 t = (b - j / P.factor) & qm;
-                if (op == kXorGate) {   // three levels, 0 and +-2(Q/8+1) (xor_level, fused_tail.hpp)
-                    const int lv = xor_level(t, q);
-                    v = lv > 0 ? 2 * pos : lv < 0 ? Q - 2 * pos : (u64)0;
-                } else {
-                    bool in = (q1 < q2) ? (t >= q1 && t < q2) : !(t >= q2 && t < q1);
-                    v = in ? neg : pos;
-                }
-            }
-            acc[phys(j)] = 0;
-            acc[NP + phys(j)] = v;
-        }
-    }
+    test_polynomial<T, (u32)N>(P, g.op & 0xFFu, q, av[n], Q, acc, acc + NP, tid);
     __syncthreads();
     if (wave == 0) ntt_forward_wave<LOGN, true>(acc + NP, tw, lane, Q, P.mu64);
     __syncthreads();
@@ -317,14 +280,12 @@ __global__ __launch_bounds__(128 * DG) void k_blind_rotate64(DevParams P, const 
         u32 ap = 0;
         const u64* bk;
         if constexpr (!AP) {
-            ap = ((q - av[step]) & qm) * P.factor;
+            ap = ginx_exponent(P, q, av[step]);
             if (ap == 0) continue;
             bk = bsk + (size_t)step * 2 * rgsw;
         } else {
             const u32 i = step / P.dR, k = step - i * P.dR;
-            u32 aI = (q - av[i]) & qm;
-            for (u32 t = 0; t < k; ++t) aI /= P.baseR;
-            const u32 a0 = aI % P.baseR;
+            const u32 a0 = ap_digit(P, q, av[i], k);
             if (a0 == 0) continue;
             bk = bsk + (((size_t)i * P.baseR + a0) * P.dR + k) * rgsw;
         }
@@ -525,7 +486,6 @@ __global__ void k_pointwise_mac64(DevParams P, u64* __restrict__ b, const u64* _
 // except where fma() is written.
 namespace wd {
 using w64::Cfg;
-using w64::phys;
 using w64::elem_j;
 using w64::wave_sync;
 using w64::block_sync_lds;
@@ -1124,46 +1084,10 @@ __device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g,
     const double Q = P.Qd, invQ = P.invQd;
     const Tw twa{tw, twl, twl1, invQ};
 
-    const u32 q = P.q, qm = q - 1, n = P.n;
-    const u32 op = g.op & 0xFFu;   // bits 8..15: the second gate of a pair (BCE_PAIR), the tail's business
-    {
-        const u32* in0 = P.pool + (size_t)(g.in0 + soff) * P.pool_stride;
-        const u32* in1 = P.pool + (size_t)(g.in1 + soff) * P.pool_stride;
-        const bool two = op <= kXorGate;
-        for (u32 i = tid; i <= n; i += T) {
-            u32 v0 = in0[i];
-            if (g.neg0) v0 = ((i == n ? (q >> 2) : 0u) - v0) & qm;
-            u32 v = v0;
-            if (two) {
-                u32 v1 = in1[i];
-                if (g.neg1) v1 = ((i == n ? (q >> 2) : 0u) - v1) & qm;
-                v = (op == BCE_XOR_FAST || op == BCE_XNOR_FAST) ? (2u * (v0 - v1)) & qm : (v0 + v1) & qm;
-            } else if (i == n) {
-                v = (v0 + (q >> 2)) & qm;
-            }
-            av[i] = v;
-        }
-    }
+    const u32 q = P.q, n = P.n;
+    lwe_prepare<T>(P, g, soff, q, av, tid);
     __syncthreads();
-    {
-        const u32 b = av[n];
-        const u32 q1 = gate_const(op, q), q2 = (q1 + (q >> 1)) & qm;
-        const double pos = (double)P.Q8p1_64, neg = -pos;
-        for (u32 j = tid; j < (u32)N; j += T) {
-            double v = 0.0;
-            if (j % P.factor == 0) {
-                u32 t = (b - j / P.factor) & qm;
-                if (op == kXorGate) {   // three levels, 0 and +-2(Q/8+1) (xor_level, fused_tail.hpp)
-                    v = (double)xor_level(t, q) * (2.0 * pos);
-                } else {
-                    bool in = (q1 < q2) ? (t >= q1 && t < q2) : !(t >= q2 && t < q1);
-                    v = in ? neg : pos;
-                }
-            }
-            acc[phys(j)] = 0.0;
-            acc[NP + phys(j)] = v;
-        }
-    }
+    test_polynomial<T, (u32)N>(P, g.op & 0xFFu, q, av[n], 0.0, acc, acc + NP, tid);   // signed levels: +-(Q/8 + 1), +-2(Q/8 + 1)
     __syncthreads();
     if (wave == 0) ntt_forward_wave<LOGN>(acc + NP, Tw{tw, nullptr}, lane, Q);
     __syncthreads();
@@ -1192,14 +1116,12 @@ __device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g,
         u32 ap = 0;
         const double* bk;
         if constexpr (!AP) {
-            ap = ((q - av[step]) & qm) * P.factor;
+            ap = ginx_exponent(P, q, av[step]);
             if (ap == 0) continue;
             bk = bsk + (size_t)step * 2 * rgsw;
         } else {
             const u32 i = step / P.dR, k = step - i * P.dR;
-            u32 aI = (q - av[i]) & qm;
-            for (u32 t = 0; t < k; ++t) aI /= P.baseR;
-            const u32 a0 = aI % P.baseR;
+            const u32 a0 = ap_digit(P, q, av[i], k);
             if (a0 == 0) continue;
             bk = bsk + (((size_t)i * P.baseR + a0) * P.dR + k) * rgsw;
         }
@@ -1429,19 +1351,7 @@ __device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g,
         __syncthreads();
         u32* rowidx = reinterpret_cast<u32*>(dct);                                      // digit rows + exchange buffers: all dead
         u64* red = reinterpret_cast<u64*>(rowidx + ((N * P.dKS + 3) & ~3u));
-        u32* outp = P.pool + (size_t)(g.out + soff) * P.pool_stride;
-        const u64* coef = reinterpret_cast<const u64*>(acc);
-        const u64 off = tail_offset<u64>(P, g.op);
-        if (P.ksk_u16) fused_tail<uint16_t, T>(P, coef, rowidx, red, outp, boot, dbg_lweN, dbg_ks, off);
-        else fused_tail<u32, T>(P, coef, rowidx, red, outp, boot, dbg_lweN, dbg_ks, off);
-        // a pair descriptor (BCE_PAIR): second tail pass on X^e * acc into slot out + 1, as in lat_bootstrap (kernels.hip);
-        // in the dataflow kernel too (scalar test of the task's word, debug pointers null: the row index stays `boot`)
-        if ((g.op >> 8) & 0xFFu) {   // (bit 16 is BCE_XOR's, not a pair's)
-            __syncthreads();
-            const u32 e = pair_rotation(P, g.op), row = PERSIST ? boot : boot + gridDim.x;
-            if (P.ksk_u16) fused_tail<uint16_t, T>(P, coef, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, off, e);
-            else fused_tail<u32, T>(P, coef, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, off, e);
-        }
+        fused_tail_outputs<T, PERSIST>(P, g, soff, reinterpret_cast<const u64*>(acc), rowidx, red, boot, dbg_lweN, dbg_ks);
     }
 }
 
@@ -1468,10 +1378,8 @@ __global__ __launch_bounds__(V::T) void k_bootstrap_dag64(const DevParams* Pp, c
 
 // LDS the fused tail needs inside the digit rows of the Split16 kernel
 bool fused_tail64_fits(const DevParams& P) {
-    const size_t N = P.N, T = wd_threads(Body::Split16, P.dG);
-    const size_t VW = P.ksk_u16 ? 8 : 4, G = (P.n + VW) / VW, Gv = G < T ? G : T, RW = (Gv + 63) / 64, SL = (T / 64) / RW;
-    const size_t need = ((N * P.dKS + 3) & ~(size_t)3) * 4 + SL * Gv * VW * 8;
-    return P.logN == 11 && (size_t)P.n + 1 <= T * VW && RW <= T / 64 && SL >= 1 && need <= WdLds(P.logN, P.dG, Body::Split16).tail_bytes();
+    return P.logN == 11 && TailGeom::fused_fits(P.n, P.ksk_u16, wd_threads(Body::Split16, P.dG), (size_t)P.N * P.dKS,
+                                                WdLds(P.logN, P.dG, Body::Split16).tail_bytes());
 }
 
 // ---- which build a launch runs ---------------------------------------------------------------------------------------

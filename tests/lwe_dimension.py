@@ -2,8 +2,8 @@
 
 n decides the row geometry of the key-switch tail -- how many 16-byte groups a key row has, how many waves share a row, how
 many row slices a workgroup walks, whether a scalar pass follows -- and the size of the last LDS region of the blind-rotation
-kernels.  This module restates those rules in a few lines (launch_tail, fused_tail and fused_tail_fits of csrc/kernels.hip and
-csrc/fused_tail.hpp, LatLds::bytes, tail_split), names the classes and in-class edges they produce for n = 1 .. N_MAX, and
+kernels.  This module restates those rules in a few lines (TailGeom and its fused_fits of csrc/fused_tail.hpp, as launch_tail,
+fused_tail and fused_tail_fits use them, LatLds::bytes, tail_split), names the classes and in-class edges they produce for n = 1 .. N_MAX, and
 lists the n the GPU sweep (tests/test_gpu_lwe_dimension.py) runs.  Its CPU half asserts that the lists hit every class and
 edge, so a shortened list fails on any machine.
 

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Development aid (GPU box): rows in flight per lane in the fused tail (kernels.hip fused_tail) vs saturated launch time.
+# Development aid (GPU box): rows in flight per lane in the fused tail (csrc/fused_tail.hpp fused_tail) vs saturated launch time.
 set -eo pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R"
