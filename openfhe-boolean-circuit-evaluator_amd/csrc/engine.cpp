@@ -300,7 +300,11 @@ int build_ctx(u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 baseG, u32 ba
     if ((q & (q - 1)) || q > 2 * (u64)N || q < 8) { g_create_error = "LWE modulus q must be a power of two dividing 2N"; return BCE_ERR_ARG; }
     if (!is_prime_u64(Q) || (Q - 1) % (2ull * N)) { g_create_error = "Q must be a prime = 1 mod 2N"; return BCE_ERR_ARG; }
     if (Q >= (1ull << 40)) { g_create_error = "ring modulus Q must be below 2^40"; return BCE_ERR_UNSUPPORTED; }
-    if (baseG & (baseG - 1)) { g_create_error = "gadget base must be a power of two"; return BCE_ERR_ARG; }
+    if (baseG < 2 || (baseG & (baseG - 1))) { g_create_error = "gadget base baseG must be a power of two, at least 2"; return BCE_ERR_ARG; }
+    // digit_count divides by log(base), and a base of 0 gives a loop of no digits that "succeeds"
+    if (n == 0) { g_create_error = "LWE dimension n must be at least 1"; return BCE_ERR_ARG; }
+    if (baseKS < 2) { g_create_error = "key-switching base baseKS must be at least 2"; return BCE_ERR_ARG; }
+    if (method == BCE_AP && baseR < 2) { g_create_error = "refreshing base baseR must be at least 2 (AP)"; return BCE_ERR_ARG; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         g_create_error = "no HIP device visible: the engine has no CPU fallback";

@@ -1283,7 +1283,8 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
 
     const uint2 ninv = make_uint2(P.Ninv, P.Ninv_s), wlast = make_uint2(P.Winv_last, P.Winv_last_s);
     constexpr u32 rgsw = R * 2 * N;
-    // GINX key: n * 2 RGSW ciphertexts; AP key: n * baseR * dR of them (< 2^31 bytes for every 32-bit parameter set)
+    // GINX key: n * 2 RGSW ciphertexts; AP key: n * baseR * dR of them, below 2^31 bytes: kernel_class grants this family to
+    // an AP context on that condition (kSplitApKeyBytes), since rowb below is 32 bits wide and is range-checked with the rest
     const __amdgpu_buffer_rsrc_t rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<u32*>(P.bsk), 0, AP ? 0x7FFFFFFF : (int)(n * 2 * rgsw * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t psi_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32*>(P.psi_tab_r2), 0, N * 4, 0x00020000);
@@ -1575,7 +1576,13 @@ KernelClass kernel_class(const DevParams& P) {
     if (P.dG < 3 || P.dG > 4 || (P.logN == 11 && P.dG != 3)) k.error = kDigitCountError;
     const bool ap = P.method_ap != 0;
     // N = 1024, dG = 4 with the lazy bounds (STD128 class): the split-transform kernels, unless BCE_VARIANT=1 pins the other family
-    const bool split = P.variant != 1 && P.logN == 10 && P.dG == 4 && P.lazy;
+    // An AP context gets them only while its key stays below 2^31 bytes: lat_bootstrap reads the AP key through one buffer
+    // resource of 0x7FFFFFFF records with a 32-bit wave-uniform row offset, and that offset takes part in the range check (at
+    // exactly 2^31 bytes the last 16 bytes of the key read as zeros; past 2^32 the offset wraps onto another coefficient's rows:
+    // tests/test_gpu_ap_key_size.py).  A larger key runs on the one-wave-per-transform family, which adds the index to a
+    // 64-bit pointer.  STD128_OPT / AP (n = 503, 4 MiB per coefficient) is 42 MB below the bound.
+    const u64 ap_key_bytes = (u64)P.n * P.baseR * P.dR * (2ull * P.dG * 2 * P.N) * sizeof(u32);
+    const bool split = P.variant != 1 && P.logN == 10 && P.dG == 4 && P.lazy && (!ap || ap_key_bytes < kSplitApKeyBytes);
     k.family = split ? KernelFamily::SplitTransform : KernelFamily::WavePerTransform;
     if (split) {
         k.fold_build = std::any_of(std::begin(kLatBuilds), std::end(kLatBuilds), [ap](const LatBuild& b) { return b.ap == ap && b.fwd != Fwd::Rows; });

@@ -92,9 +92,12 @@ struct DevParams {
 // The one place that knows it.  The 32-bit part (shape rule of the split-transform family, read off kLatBuilds) lives in
 // kernels.hip, the 64-bit part (shape rule of the integer / fp64 families, read off kWdBuilds) in kernels64.hip.
 constexpr size_t kLdsBytesPerCu = 160 * 1024;
+// An AP key of the split-transform family must be smaller than this (one buffer resource, 32-bit row offsets: kernel_class)
+constexpr unsigned long long kSplitApKeyBytes = 1ull << 31;
 enum class KernelFamily {
     WavePerTransform,   // k_blind_rotate (kernels.hip): one wave per transform, every 32-bit shape the split family does not take
-    SplitTransform,     // k_blind_rotate_lat / k_bootstrap_dag (kernels.hip): N = 1024, four gadget digits, lazy bounds hold
+    SplitTransform,     // k_blind_rotate_lat / k_bootstrap_dag (kernels.hip): N = 1024, four gadget digits, lazy bounds hold,
+                        // an AP key below kSplitApKeyBytes
     Int64,              // w64::k_blind_rotate64 (kernels64.hip), with its narrow build (four digits, N >= 1024, Q < 2^31)
     Fp64,               // wd::k_blind_rotate64d / k_bootstrap_dag64 (kernels64.hip): Q < 2^39 in doubles
 };

@@ -50,6 +50,33 @@ def test_argument_errors_are_status_codes(bce):
     assert L.bce_ctx_create(bce.TOY, 7, 0, C.byref(h)) == bce.ERR_ARG
     assert b"method" in L.bce_last_error(None)
     assert L.bce_eval_gates(None, 0, None) == bce.ERR_ARG
+    # bases and dimension of a custom context: refused with a message before any device call (this host may have no device:
+    # a set that passes these checks gets as far as BCE_ERR_NO_DEVICE or creates a context, never BCE_ERR_ARG)
+    Q = 134215681                                     # TOY's 27-bit prime, 1 mod 1024
+    assert Q % 1024 == 1 and all(Q % p for p in range(3, 11587, 2))
+    #      n   N    q    Q  qKS      baseKS baseG baseR
+    good = (16, 512, 512, Q, 1 << 14, 32, 1 << 9, 23)
+
+    def create(method, **change):
+        names = ("n", "N", "q", "Q", "qKS", "baseKS", "baseG", "baseR")
+        args = [change.get(k, v) for k, v in zip(names, good)]
+        hh = C.c_void_p()
+        rc = L.bce_ctx_create_custom(*args, method, 0, C.byref(hh))
+        msg = L.bce_last_error(None).decode()
+        if hh.value:
+            L.bce_ctx_destroy(hh)
+        return rc, msg
+
+    for method, change, word in ((bce.AP, {"baseR": 0}, "baseR"), (bce.AP, {"baseR": 1}, "baseR"),
+                                 (bce.AP, {"baseKS": 0}, "baseKS"), (bce.GINX, {"baseKS": 1}, "baseKS"),
+                                 (bce.GINX, {"baseG": 0}, "baseG"), (bce.AP, {"baseG": 1}, "baseG"),
+                                 (bce.GINX, {"n": 0}, "LWE dimension"), (bce.AP, {"n": 0}, "LWE dimension")):
+        rc, msg = create(method, **change)
+        assert rc == bce.ERR_ARG and word in msg, (method, change, rc, msg)
+    for method, change in ((bce.AP, {}), (bce.GINX, {}), (bce.GINX, {"baseR": 0}), (bce.AP, {"baseR": 2}), (bce.AP, {"baseKS": 2}),
+                           (bce.GINX, {"baseG": 2})):
+        rc, msg = create(method, **change)
+        assert rc != bce.ERR_ARG, (method, change, rc, msg)
 
 
 def test_product_does_not_reference_the_oracle():

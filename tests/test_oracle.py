@@ -215,15 +215,28 @@ def _rotate_minus_one(p, k, N, Q):
     return (sign * r - p) % Q
 
 
-@pytest.mark.parametrize("method", ["GINX", "AP"])
-def test_blind_rotation_equals_its_coefficient_domain_definition(orc, method):
+# AP digit geometries beside TOY's dR = 2 (tests/ap_digits.py names the classes): (n, N, q, baseR, log2 baseG) at the 27-bit prime
+_AP_GEOMETRIES = {"dR1_baseR_eq_q": (4, 512, 512, 512, 9), "dR1_baseR_gt_q": (4, 512, 256, 300, 9), "dR3_exact_power": (4, 512, 512, 8, 9),
+                  "dR3_top_digit_0_or_1": (4, 512, 1024, 23, 9), "dR3_factor_1_N1024": (3, 1024, 2048, 45, 7), "dR7": (3, 512, 1024, 3, 9),
+                  "dR10": (3, 512, 1024, 2, 9)}
+
+
+@pytest.mark.parametrize("method,geometry", [pytest.param("GINX", None, id="GINX"), pytest.param("AP", None, id="AP")]
+                         + [pytest.param("AP", g, id="AP-" + g) for g in _AP_GEOMETRIES])
+def test_blind_rotation_equals_its_coefficient_domain_definition(orc, method, geometry):
     """An independent restatement of BootstrapGateCore + EvalAcc with NO number-theoretic transform anywhere: the
     accumulator stays in coefficient form, SignedDigitDecompose is re-implemented here in numpy, every RGSW product is a
     negacyclic convolution by definition (np.convolve) against the COEFFICIENT-form key the oracle exports, the GINX
     monomials are coefficient rotations.  It must reproduce the oracle's accumulator word for word (TOY, a few gates) --
     this pins the oracle's transform-domain machinery (CT/GS order, twiddles, evaluation-form keys and monomials, Barrett
     folds) to the ring arithmetic it stands for.  It does not pin the oracle to OpenFHE (still unpinned: see the header)."""
-    o = orc.Oracle(orc.TOY, getattr(orc, method))
+    if geometry is None:
+        o = orc.Oracle(orc.TOY, getattr(orc, method))
+    else:                         # the oracle at dR = 1, 3, 7 and 10: what the AP digit-geometry sweep compares the engine with
+        n_, N_, q_, baseR_, gb_ = _AP_GEOMETRIES[geometry]
+        Q_ = int(orc.lib().bo_previous_prime(orc.lib().bo_first_prime(27, 2 * N_), 2 * N_))
+        o = orc.Oracle(method=orc.AP, custom=(n_, N_, q_, Q_, 1 << 14, 32, 1 << gb_, baseR_))
+        assert o.params["dR"] == {"dR1": 1, "dR3": 3, "dR7": 7, "dR10": 10}[geometry.split("_")[0]]
     o.keygen(424242)
     P = o.params
     n, N, q, Q, B, dG = P["n"], o.N, P["q"], P["Q"], P["baseG"], P["dG"]
