@@ -200,6 +200,14 @@ int bce_circuit_device_verify_active(const bce_circuit*);
 /* The device's report of the last Clock() on that path (all zero otherwise): checks, mismatches, repairs and the phase
  * error statistics of every checked gate output (noise margin = q/8 - max_abs_err). */
 int bce_circuit_get_check_report(const bce_circuit*, bce_check_report* out);
+/* Read-only, no circuit, no device: the rule that decides what a Clock() runs (resolve_mode of csrc/run_mode.hpp), as bits.
+ * inputs:  bit 0 plaintext, 1 encrypted, 2 verify, 3 batched, 4 relevel, 5 graph, 6 device verify, 7 dataflow,
+ *          8 dataflow shared, 9-10 the XOR choice (0 none, 1 fast, 2 shared, 3 single), 11 the circuit has an engine,
+ *          12 bce_dag_supported, 13 gate sharded, 14 a dataflow task list exists.
+ * returns: bits 0-1 the path of Clock() (0 gate-level rounds, 1 step schedule, 2 dataflow kernel), 2-3 the XOR mode of the
+ *          units (0 reference, 1 fast, 2 shared, 3 single; 2 = bce_circuit_xor_shared_active), 4 bce_circuit_device_verify_active,
+ *          5 bce_circuit_graph_active, 6 bce_circuit_dataflow_active.  For tests that hold the rule to a recorded table. */
+uint32_t bce_circuit_resolve_mode(uint32_t inputs);
 /* The task list of the dataflow schedule (what bce_dag_create receives; bce_dag_create_pairs under
  * bce_circuit_set_dataflow_shared, `op` then holds the pair words): gates in topological order with SSA slots for
  * ONE instance (slot < slot_stride of bce_circuit_get_info) and their priority classes.  Writes min(*n_tasks, cap)

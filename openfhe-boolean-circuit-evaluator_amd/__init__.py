@@ -615,7 +615,7 @@ CIRCUIT_SYMBOLS = [
     "bce_circuit_create", "bce_circuit_destroy", "bce_circuit_last_error", "bce_circuit_read_file",
     "bce_circuit_read_bristol", "bce_circuit_get_info", "bce_circuit_reset", "bce_circuit_rearm", "bce_circuit_set_plaintext",
     "bce_circuit_set_encrypted", "bce_circuit_set_verify", "bce_circuit_get_flags", "bce_circuit_set_batched",
-    "bce_circuit_set_encrypt_mode", "bce_circuit_get_encrypt_mode", "bce_circuit_plan_hash", "bce_circuit_set_shard_locality", "bce_circuit_set_xor_fast", "bce_circuit_set_xor_shared", "bce_circuit_xor_shared_active", "bce_circuit_set_xor_single", "bce_circuit_get_xor_single", "bce_circuit_set_relevel", "bce_circuit_get_relevel", "bce_circuit_set_dataflow", "bce_circuit_set_dataflow_shared", "bce_circuit_dataflow_active", "bce_circuit_set_graph", "bce_circuit_graph_active", "bce_circuit_set_device_verify", "bce_circuit_device_verify_active", "bce_circuit_get_check_report", "bce_circuit_dataflow_plan", "bce_circuit_set_balance", "bce_circuit_relevel_steps", "bce_circuit_relevel_descs", "bce_circuit_relevel_publications", "bce_circuit_check_relevel", "bce_circuit_set_instances", "bce_circuit_set_input", "bce_circuit_clock",
+    "bce_circuit_set_encrypt_mode", "bce_circuit_get_encrypt_mode", "bce_circuit_plan_hash", "bce_circuit_set_shard_locality", "bce_circuit_set_xor_fast", "bce_circuit_set_xor_shared", "bce_circuit_xor_shared_active", "bce_circuit_set_xor_single", "bce_circuit_get_xor_single", "bce_circuit_set_relevel", "bce_circuit_get_relevel", "bce_circuit_set_dataflow", "bce_circuit_set_dataflow_shared", "bce_circuit_dataflow_active", "bce_circuit_set_graph", "bce_circuit_graph_active", "bce_circuit_set_device_verify", "bce_circuit_device_verify_active", "bce_circuit_get_check_report", "bce_circuit_resolve_mode", "bce_circuit_dataflow_plan", "bce_circuit_set_balance", "bce_circuit_relevel_steps", "bce_circuit_relevel_descs", "bce_circuit_relevel_publications", "bce_circuit_check_relevel", "bce_circuit_set_instances", "bce_circuit_set_input", "bce_circuit_clock",
     "bce_circuit_get_output", "bce_circuit_get_buses", "bce_circuit_get_counts", "bce_circuit_get_stats", "bce_circuit_dump",
     "bce_circuit_set_exchange", "bce_circuit_enable_rccl", "bce_circuit_exchange_capacity", "bce_assemble_bristol", "bce_pool_gather",
     "bce_pool_scatter",
@@ -652,6 +652,8 @@ def _bind_circuit():
     L.bce_circuit_set_device_verify.argtypes = [vp, i32]
     L.bce_circuit_device_verify_active.argtypes = [vp]
     L.bce_circuit_get_check_report.argtypes = [vp, C.POINTER(CheckReport)]
+    L.bce_circuit_resolve_mode.argtypes = [u32]
+    L.bce_circuit_resolve_mode.restype = u32
     L.bce_circuit_get_encrypt_mode.argtypes = [vp]
     L.bce_circuit_get_relevel.argtypes = [vp]
     L.bce_circuit_set_shard_locality.argtypes = [vp, i32]
@@ -689,6 +691,11 @@ def assemble_bristol(in_path, out_path=None, new_flag=False, gen_fan_flag=False,
                                 out_path.encode() if out_path else None, err, 512)
     if rc != OK:
         raise BceError(rc, err.value.decode())
+
+
+def circuit_resolve_mode(inputs):
+    """the rule that decides what a Clock() runs, as bits (bce_circuit_resolve_mode of bce_circuit.h); no circuit, no GPU"""
+    return int(_bind_circuit().bce_circuit_resolve_mode(int(inputs)))
 
 
 # bit-order helpers of the reference harnesses (src/utils.cpp:49-89)

@@ -158,17 +158,9 @@ Circuit::Circuit(int set, int method) {
         throw std::runtime_error("BTKeyGen: " + m);
     }
     std::cout << "Done" << std::endl;
-    gep.cc = cc;
-    gep.enc_counter = &enc_counter_;
-    gep.fixes = &stats_.verify_fixes;
 }
 
-Circuit::Circuit(bce_ctx* engine) : cc(engine) {
-    gep.cc = cc;
-    gep.enc_counter = &enc_counter_;
-    gep.fixes = &stats_.verify_fixes;
-    quiet_ = true;
-}
+Circuit::Circuit(bce_ctx* engine) : cc(engine) { quiet_ = true; }
 
 Circuit::~Circuit() {
     dropDag();
@@ -392,10 +384,10 @@ void Circuit::finalizeNetlist() {
 
 void Circuit::Reset() {
     n_input_gates = n_output_gates = n_and_gates = n_or_gates = n_xor_gates = n_not_gates = 0;
-    plaintext_flag = encrypted_flag = verify_flag = false;  // gep's copies are left alone, like the reference
+    opt_.plaintext = opt_.encrypted = opt_.verify = false;
     done = false;
     inputs_set_ = false;
-    syncXorMode();   // verify_flag is one of the things xorSharedActive() reads
+    syncXorMode();   // verify is one of the things xorMode() reads
     ++epoch_;
     plain_.assign(instances_, std::vector<uint8_t>(wire_names_.size(), 0));
     circuitOut.assign(instances_, std::vector<uint8_t>(n_output_bits.empty() ? 0 : n_output_bits[0], 0));
@@ -409,9 +401,17 @@ void Circuit::Rearm() {
     stats_ = bce_circuit_stats{};
 }
 
+RunMode Circuit::runMode() const {
+    ModeInputs m = opt_;
+    m.engine = cc != nullptr;
+    m.dag_supported = cc && bce_dag_supported(cc);
+    m.gate_sharded = gateSharded();
+    m.tasks = !tasks_.tasks.empty();
+    return resolve_mode(m);
+}
+
 void Circuit::setVerify(bool b) {
-    setModeFlag(verify_flag, b, "setVerify");   // one of the things xorSharedActive() reads
-    gep.verify_flag = b;
+    setModeFlag(opt_.verify, b, "setVerify");   // one of the things xorMode() reads
     if (b) { setPlaintext(true); setEncrypted(true); }
 }
 
@@ -458,7 +458,7 @@ void Circuit::SetInput(unsigned inst, const Inputs& input, bool verbose) {
         std::cerr << "error: total_inputs: " << total_bits << " #used: " << inputGates.size() << std::endl;
     else if (verbose)
         std::cout << "input confirmed" << std::endl;
-    if (encrypted_flag && mine) {  // encrypted mode must be on at call time (src/circuit.cpp:505-507)
+    if (opt_.encrypted && mine) {  // encrypted mode must be on at call time (src/circuit.cpp:505-507)
         requireEngine("SetInput");
         ck(bce_pool_reserve(cc, instances_ * stride_), "SetInput(pool)");
         // stream index = (evaluation epoch, instance, input position): every rank draws the same ciphertexts
@@ -483,7 +483,7 @@ void Circuit::SetInput(unsigned inst, const Inputs& input, bool verbose) {
 
 // ---- sharding plan --------------------------------------------------------------------------
 void Circuit::buildShardPlan() {
-    shard_ = gateSharded() ? sched::shard_levels(net_, world_, xor_single_ ? sched::XorMode::Single : sched::xor_mode(xor_fast_)) : sched::LevelShard{};
+    shard_ = gateSharded() ? sched::shard_levels(net_, world_, xorMode()) : sched::LevelShard{};
 }
 
 uint64_t Circuit::exchangeCapacity(uint32_t world, int shard_mode, bool encrypted) const {
@@ -521,8 +521,8 @@ void Circuit::setExchange(uint32_t rank, uint32_t world, int shard_mode, bce_all
 uint64_t Circuit::planHash() const {
     uint64_t h = 0xcbf29ce484222325ull;   // FNV-1a over 64-bit words
     auto mix = [&](uint64_t v) { h = (h ^ v) * 0x100000001b3ull; };
-    mix(world_); mix((uint64_t)shard_mode_); mix(stride_); mix(instances_); mix(relevel_ ? 1 : 0); mix((uint64_t)xorMode());
-    if (dataflow_shared_) mix(0x6466736872ull);   // "dfshr"; mixed only when set: the hashes without the flag are pinned (tests/golden)
+    mix(world_); mix((uint64_t)shard_mode_); mix(stride_); mix(instances_); mix(opt_.relevel ? 1 : 0); mix((uint64_t)xorMode());
+    if (opt_.dataflow_shared) mix(0x6466736872ull);   // "dfshr"; mixed only when set: the hashes without the flag are pinned (tests/golden)
     for (const auto& lv : shard_.owner) { mix(lv.size()); for (uint8_t o : lv) mix(o); }
     for (const auto& lv : shard_.publish) for (const auto& r : lv) { mix(r.size()); for (int w : r) mix((uint64_t)w); }
     for (const auto& st : steps_.publish) for (const auto& r : st) { mix(r.size()); for (int w : r) mix((uint64_t)w); }
@@ -537,7 +537,7 @@ void Circuit::exchangeWires(const std::vector<std::vector<int>>& pub) {
     if (widest == 0) return;
     const auto& mine = pub[rank_];
     const unsigned K = instances_;
-    if (plaintext_flag) {
+    if (opt_.plaintext) {
         const uint64_t bytes = (uint64_t)widest * K;
         if (bytes > xcap_ || !host_send_ || !host_recv_) throw std::runtime_error("exchange: host buffers too small");
         uint8_t* s = (uint8_t*)host_send_;
@@ -552,7 +552,7 @@ void Circuit::exchangeWires(const std::vector<std::vector<int>>& pub) {
         }
         ++stats_.exchanges;
     }
-    if (encrypted_flag) {
+    if (opt_.encrypted) {
         uint64_t p[BCE_P_COUNT];
         bce_get_params(cc, p);
         const uint64_t W = 4 * (p[BCE_P_n] + 1);
@@ -621,7 +621,7 @@ void Circuit::rebuildRelevel() {
     const auto [lo, hi] = instanceRange();
     const uint64_t K = std::max(1u, hi - lo);
     const uint32_t world = gateSharded() ? world_ : 1;   // gate sharding: every step's units are split over the ranks
-    const bool want_tasks = dataflow_ && tasksExist();   // shared XORs: pair tasks, with setDataflowShared only
+    const bool want_tasks = opt_.dataflow && tasksExist();   // shared XORs: pair tasks, with setDataflowShared only
     if (!want_tasks || tasks_.tasks.empty()) tasks_ = want_tasks ? lowerTasks() : sched::TaskList{};   // a function of the units
     auto plan = [&](bool by_slack) {   // returns the slot stride the schedules need
         if (by_slack && !units_.units.empty()) {
@@ -655,27 +655,17 @@ std::vector<uint32_t> Circuit::relevelPublications() const {
     return v;
 }
 
-void Circuit::setXorFast(bool b) {
-    if (b && xor_shared_) throw std::invalid_argument("setXorFast: not together with setXorShared");
-    if (b && xor_single_) throw std::invalid_argument("setXorFast: not together with setXorSingle");
-    xor_fast_ = gep.xor_fast = b;
-    buildUnits();
-    buildShardPlan();
-    rebuildRelevel();
-}
-
-void Circuit::setXorShared(bool b) {
-    if (b && xor_fast_) throw std::invalid_argument("setXorShared: not together with setXorFast");
-    if (b && xor_single_) throw std::invalid_argument("setXorShared: not together with setXorSingle");
-    if (inputs_set_ && b != xor_shared_) throw std::logic_error("setXorShared: choose the XOR lowering before SetInput");
-    xor_shared_ = b;
-    syncXorMode();
-}
-
-void Circuit::setXorSingle(bool b) {
-    if (b && (xor_fast_ || xor_shared_)) throw std::invalid_argument("setXorSingle: not together with setXorFast or setXorShared");
-    if (inputs_set_ && b != xor_single_) throw std::logic_error("setXorSingle: choose the XOR lowering before SetInput");
-    xor_single_ = gep.xor_single = b;
+// the one XOR choice behind setXorFast / setXorShared / setXorSingle (circuit.hpp)
+void Circuit::chooseXor(XorChoice which, bool b, bool before_input) {
+    static const char* const setter[] = {"", "setXorFast", "setXorShared", "setXorSingle"};
+    const std::string who = setter[(int)which];
+    const XorChoice cur = opt_.xor_choice;
+    if (b && cur != XorChoice::None && cur != which)
+        throw std::invalid_argument(who + ": not together with " + (which == XorChoice::Single ? "setXorFast or setXorShared" : setter[(int)cur]));
+    if (before_input && inputs_set_ && b != (cur == which)) throw std::logic_error(who + ": choose the XOR lowering before SetInput");
+    if (b) opt_.xor_choice = which;
+    else if (cur == which) opt_.xor_choice = XorChoice::None;
+    if (which == XorChoice::Shared) return syncXorMode();
     buildUnits();
     buildShardPlan();
     rebuildRelevel();
@@ -719,73 +709,58 @@ void Circuit::ensurePlan(bce_plan*& plan, unsigned lo, uint32_t K) {
     }
 }
 
-void Circuit::clockReleveled() {
-    if (verify_flag) throw std::logic_error("re-levelled schedule is not available in verify mode");
+// ---- the bootstrap-depth schedule on the resident plan, step by step or as one hipGraph -----------------------------
+// verify: verify mode's checks on the device (bce_plan_set_checks).  The reference checks every gate as it evaluates it
+// (src/gate.cpp:113-120,153-160,174-181,206-213).  Here the plaintext pass runs first for all levels, its bits become the
+// expected values of the plan's per-step check lists, and the report is read once, after the last step.
+void Circuit::clockSteps(bool verify) {
+    if (!verify && opt_.verify) throw std::logic_error("re-levelled schedule is not available in verify mode");
     const auto [lo, hi] = instanceRange();
     const uint32_t K = hi - lo;
-    ensurePlan(plan_, lo, K);
-    if (plan_ && graphActive()) {
-        ck(bce_plan_run(cc, plan_), "Clock(schedule graph)");
-        for (const auto& st : steps_.steps) if (!st.empty()) ++stats_.sublaunches;
-    } else {
-        uint32_t ps = 0;
-        for (size_t s = 0; s < steps_.steps.size(); ++s) {
-            if (plan_ && !steps_.steps[s].empty()) {
-                ck(bce_plan_run_step(cc, plan_, ps++), "Clock(re-levelled step)");
-                ++stats_.sublaunches;
+    if (verify) for (size_t l = 0; l < levels_.size(); ++l) plainRound(l);
+    bce_plan*& plan = verify ? vplan_ : plan_;   // a plan of its own: the verify-off runs keep theirs (and its captured graph)
+    ensurePlan(plan, lo, K);
+    if (verify) check_report_ = bce_check_report{};
+    if (verify && plan) {
+        if (!vplan_checks_) {
+            const sched::CheckLists all = sched::check_lists(steps_, net_);
+            check_gates_.clear();
+            check_wires_.clear();
+            std::vector<uint32_t> sizes;
+            for (size_t s = 0; s < steps_.steps.size(); ++s) {
+                if (steps_.steps[s].empty()) continue;   // the plan holds the non-empty steps
+                check_gates_.push_back(all.gates[s]);
+                sizes.push_back((uint32_t)all.wires[s].size());
+                check_wires_.insert(check_wires_.end(), all.wires[s].begin(), all.wires[s].end());
             }
-            if (gateSharded()) exchangeWires(steps_.publish[s]);   // outputs of this step whose consumers sit on other ranks
+            ck(bce_plan_set_checks(cc, plan, sizes.data(), check_wires_.data(), 1), "Clock(check lists)");
+            vplan_checks_ = true;
         }
+        const std::vector<uint8_t> expect = armChecks(lo, hi, check_wires_);
+        if (!expect.empty()) ck(bce_plan_set_expected(cc, plan, expect.data()), "Clock(expected bits)");
     }
-    finishReleveled(lo, hi);
+    const bool graph = plan && runMode().graph;
+    if (graph) ck(bce_plan_run(cc, plan), "Clock(schedule graph)");
+    uint32_t ps = 0;
+    for (size_t s = 0; s < steps_.steps.size(); ++s) {
+        if (plan && !steps_.steps[s].empty()) {
+            if (!graph) ck(bce_plan_run_step(cc, plan, ps++), "Clock(re-levelled step)");
+            ++stats_.sublaunches;
+        }
+        if (!graph && gateSharded()) exchangeWires(steps_.publish[s]);   // outputs of this step whose consumers sit on other ranks
+    }
+    if (verify && plan) reportChecks(&check_gates_, nullptr);
+    finishReleveled(lo, hi, verify);
     stats_.levels = (uint32_t)steps_.steps.size();
 }
 
-// ---- verify mode on the bootstrap-depth schedule: decrypt, compare, repair on the device (bce_plan_set_checks) -------
-// The reference checks every gate as it evaluates it (src/gate.cpp:113-120,153-160,174-181,206-213).  Here the plaintext
-// pass runs first for all levels, its bits become the expected values of the plan's per-step check lists, and the encrypted
-// pass stays on the resident plan (step by step or as one hipGraph); the report is read once, after the last step.
-void Circuit::clockDeviceVerify() {
-    const auto [lo, hi] = instanceRange();
-    const uint32_t K = hi - lo;
-    for (size_t l = 0; l < levels_.size(); ++l) plainRound(l);
-    ensurePlan(vplan_, lo, K);   // a plan of its own: the verify-off runs keep theirs (and its captured graph)
-    check_report_ = bce_check_report{};
-    if (vplan_) {
-        if (!vplan_checks_) {
-            const sched::CheckLists all = sched::check_lists(steps_, net_);
-            checks_ = {};
-            std::vector<uint32_t> sizes, slots;
-            for (size_t s = 0; s < steps_.steps.size(); ++s) {
-                if (steps_.steps[s].empty()) continue;   // the plan holds the non-empty steps
-                checks_.wires.push_back(all.wires[s]);
-                checks_.gates.push_back(all.gates[s]);
-                sizes.push_back((uint32_t)all.wires[s].size());
-                slots.insert(slots.end(), all.wires[s].begin(), all.wires[s].end());
-            }
-            ck(bce_plan_set_checks(cc, vplan_, sizes.data(), slots.data(), 1), "Clock(check lists)");
-            vplan_checks_ = true;
-        }
-        std::vector<uint8_t> expect;
-        for (unsigned i = lo; i < hi; ++i)
-            for (const auto& st : checks_.wires)
-                for (uint32_t w : st) expect.push_back(plain_[i][w]);
-        ck(bce_check_reset(cc), "Clock(check reset)");
-        if (!expect.empty()) ck(bce_plan_set_expected(cc, vplan_, expect.data()), "Clock(expected bits)");
-        if (graphActive()) {
-            ck(bce_plan_run(cc, vplan_), "Clock(schedule graph)");
-            stats_.sublaunches += (uint32_t)checks_.wires.size();
-        } else {
-            for (uint32_t ps = 0; ps < checks_.wires.size(); ++ps) {
-                ck(bce_plan_run_step(cc, vplan_, ps), "Clock(re-levelled step)");
-                ++stats_.sublaunches;
-            }
-        }
-        reportChecks(&checks_.gates, nullptr);
-    }
-    finishReleveled(lo, hi);
-    compareOutputs(lo, hi);
-    stats_.levels = (uint32_t)steps_.steps.size();
+// verify prologue once the plan / DAG exists: the plaintext pass's bits of `wires`, instance after instance, and a fresh report
+std::vector<uint8_t> Circuit::armChecks(unsigned lo, unsigned hi, const std::vector<uint32_t>& wires) {
+    std::vector<uint8_t> expect;
+    for (unsigned i = lo; i < hi; ++i)
+        for (uint32_t w : wires) expect.push_back(plain_[i][w]);
+    ck(bce_check_reset(cc), "Clock(check reset)");
+    return expect;
 }
 
 // the report of the run, read once: one "Bad <OP> fixing" line per logged mismatch, all mismatches into verify_fixes.  The
@@ -836,19 +811,19 @@ void Circuit::setDataflow(bool b) {
             if (t.stride > stride_) throw std::logic_error("setDataflow: choose the dataflow schedule before SetInput (it lays the pool out with its own temporaries)");
             tasks_ = std::move(t);
         }
-        dataflow_ = b;
+        opt_.dataflow = b;
         return;
     }
-    dataflow_ = b;
+    opt_.dataflow = b;
     rebuildRelevel();
 }
 
 // Opt-in: shared XORs on the dataflow schedule.  The task list is then lowered in XorMode::Shared -- a pair task and an AND
 // per XOR -- and goes to the engine through bce_dag_create_pairs.  Part of the pool layout and of the lowering: before SetInput.
 void Circuit::setDataflowShared(bool b) {
-    if (inputs_set_ && b != dataflow_shared_) throw std::logic_error("setDataflowShared: choose the dataflow schedule of the shared XOR lowering before SetInput");
-    if (b == dataflow_shared_) return;
-    dataflow_shared_ = b;
+    if (inputs_set_ && b != opt_.dataflow_shared) throw std::logic_error("setDataflowShared: choose the dataflow schedule of the shared XOR lowering before SetInput");
+    if (b == opt_.dataflow_shared) return;
+    opt_.dataflow_shared = b;
     tasks_ = {};          // the list depends on the flag where the units are shared
     rebuildRelevel();
 }
@@ -858,57 +833,45 @@ void Circuit::createDag(bce_dag** g) {
     ck(create(cc, (uint32_t)tasks_.tasks.size(), tasks_.tasks.data(), tasks_.prio.data(), g), "Clock(dataflow DAG)");
 }
 
-void Circuit::clockDataflow() {
-    const auto [lo, hi] = instanceRange();
-    if (tasks_.stride > stride_) throw std::logic_error("dataflow schedule needs more scratch slots than the pool stride");
-    if (steps_.steps.empty()) rebuildRelevel();
-    if (!dag_) createDag(&dag_);
-    if (hi > lo) {
-        ck(bce_dag_run(cc, dag_, hi - lo, stride_, lo * stride_), "Clock(dataflow run)");
-        ++stats_.sublaunches;
-    }
-    finishReleveled(lo, hi);
-    stats_.levels = 1;
-}
-
-// ---- verify mode on the dataflow schedule: the checks of clockDeviceVerify inside the persistent kernel ---------------
-// setDataflow + setDeviceVerify + setVerify.  The plaintext pass runs first for all levels, its bits become the expected
-// values of the DAG's checks (sched::task_checks: the same (register, gate) pairs as the step plan's lists), ONE
-// bce_dag_run follows in which every workgroup checks and repairs its task's output before it releases the consumers --
-// where Gate::Evaluate does it, src/gate.cpp:153-160 -- and the report is read once.
-void Circuit::clockDataflowVerify() {
+// verify: the checks of clockSteps inside the persistent kernel (setDataflow + setDeviceVerify + setVerify).  The plaintext
+// pass's bits become the expected values of the DAG's checks (sched::task_checks: the same (register, gate) pairs as the
+// step plan's lists), ONE bce_dag_run follows in which every workgroup checks and repairs its task's output before it
+// releases the consumers -- where Gate::Evaluate does it, src/gate.cpp:153-160 -- and the report is read once.
+void Circuit::clockDag(bool verify) {
     const auto [lo, hi] = instanceRange();
     const uint32_t K = hi - lo;
     if (tasks_.stride > stride_) throw std::logic_error("dataflow schedule needs more scratch slots than the pool stride");
     if (steps_.steps.empty()) rebuildRelevel();
-    for (size_t l = 0; l < levels_.size(); ++l) plainRound(l);
-    check_report_ = bce_check_report{};
-    if (!vdag_) {   // a DAG of its own: the verify-off runs keep theirs
-        createDag(&vdag_);
-        task_checks_ = sched::task_checks(tasks_, units_, net_);
-        ck(bce_dag_set_checks(cc, vdag_, (uint32_t)task_checks_.tasks.size(), task_checks_.tasks.data(), 1), "Clock(check list)");
+    if (verify) for (size_t l = 0; l < levels_.size(); ++l) plainRound(l);
+    if (verify) check_report_ = bce_check_report{};
+    bce_dag*& dag = verify ? vdag_ : dag_;   // a DAG of its own: the verify-off runs keep theirs
+    if (!dag) {
+        createDag(&dag);
+        if (verify) {
+            task_checks_ = sched::task_checks(tasks_, units_, net_);
+            ck(bce_dag_set_checks(cc, dag, (uint32_t)task_checks_.tasks.size(), task_checks_.tasks.data(), 1), "Clock(check list)");
+        }
     }
     if (K) {
-        std::vector<uint8_t> expect;
-        expect.reserve((size_t)K * task_checks_.wires.size());
-        for (unsigned i = lo; i < hi; ++i)
-            for (uint32_t w : task_checks_.wires) expect.push_back(plain_[i][w]);
-        ck(bce_check_reset(cc), "Clock(check reset)");
-        if (!expect.empty()) ck(bce_dag_set_expected(cc, vdag_, K, expect.data()), "Clock(expected bits)");
-        ck(bce_dag_run(cc, vdag_, K, stride_, lo * stride_), "Clock(dataflow run)");
+        if (verify) {
+            const std::vector<uint8_t> expect = armChecks(lo, hi, task_checks_.wires);
+            if (!expect.empty()) ck(bce_dag_set_expected(cc, dag, K, expect.data()), "Clock(expected bits)");
+        }
+        ck(bce_dag_run(cc, dag, K, stride_, lo * stride_), "Clock(dataflow run)");
         ++stats_.sublaunches;
-        reportChecks(nullptr, &task_checks_.gates);
+        if (verify) reportChecks(nullptr, &task_checks_.gates);
     }
-    finishReleveled(lo, hi);
-    compareOutputs(lo, hi);
+    finishReleveled(lo, hi, verify);
     stats_.levels = 1;
 }
 
-// NOT wires the OUTPUT gates read, OUTPUT gates (decrypt), gate counts: common end of the two DAG-level schedules
-void Circuit::finishReleveled(unsigned lo, unsigned hi) {
+// NOT wires the OUTPUT gates read, OUTPUT gates (decrypt), gate counts, in verify mode the OUTPUT gates against the plaintext
+// pass: common end of the two DAG-level schedules
+void Circuit::finishReleveled(unsigned lo, unsigned hi, bool verify) {
     evalStrided(steps_.output_nots, lo, hi - lo, "Clock(output NOTs)");
     decryptOutputs(lo, hi, nullptr);
     countGates(nullptr);
+    if (verify) compareOutputs(lo, hi);
 }
 
 // descriptors address instance 0; a strided call replicates them K times from instance `lo` on
@@ -931,9 +894,9 @@ void Circuit::decryptOutputs(unsigned lo, unsigned hi, const std::vector<int>* g
     for (size_t k = 0; k < n; ++k) {
         const GateRec& g = allGates[gates ? (*gates)[k] : k];
         if (g.op != GateEnum::OUTPUT) continue;
-        if (!encrypted_flag && !plaintext_flag) std::cerr << "Error either encrypted or plaintext flag must be set" << std::endl;
+        if (!opt_.encrypted && !opt_.plaintext) std::cerr << "Error either encrypted or plaintext flag must be set" << std::endl;
         for (unsigned i = lo; i < hi; ++i) {
-            if (encrypted_flag) { oslots.push_back(i * stride_ + g.in[0]); obits.push_back({i, g.out_bit}); }
+            if (opt_.encrypted) { oslots.push_back(i * stride_ + g.in[0]); obits.push_back({i, g.out_bit}); }
             else circuitOut[i][g.out_bit] = plain_[i][g.in[0]];
         }
     }
@@ -991,19 +954,21 @@ void Circuit::executeRound(size_t level) {
     const auto [lo, hi] = instanceRange();
     auto mine = [&](size_t k) { return !gateSharded() || shard_.owner[level][k] == 0xFF || shard_.owner[level][k] == rank_; };
 
-    if (plaintext_flag) plainRound(level);
-    if (encrypted_flag) {
+    const sched::XorMode xm = xorMode();   // the rounds spell a Shared XOR as the reference does
+    const bool xor_one = xm == sched::XorMode::Fast || xm == sched::XorMode::Single, xor_single = xm == sched::XorMode::Single;
+    if (opt_.plaintext) plainRound(level);
+    if (opt_.encrypted) {
         requireEngine("Clock");
         const uint32_t tmp0 = (uint32_t)wire_names_.size();
-        if (batched_) {
+        if (opt_.batched) {
             // stage A: AND / OR gates and the two ANDs of every XOR; stage B: the OR of every XOR
             std::vector<bce_gate_desc> A, B;
             uint32_t x = 0;
             for (size_t k = 0; k < L.gates.size(); ++k) {
                 const GateRec& g = allGates[L.gates[k]];
                 const bool me = mine(k);
-                if (g.op == GateEnum::XOR && (xor_fast_ || xor_single_)) {
-                    if (me) A.push_back({(uint32_t)(xor_single_ ? BCE_XOR : BCE_XOR_FAST), (uint32_t)g.in[0], (uint32_t)g.in[1], (uint32_t)g.out, 0, 0});
+                if (g.op == GateEnum::XOR && xor_one) {
+                    if (me) A.push_back({(uint32_t)(xor_single ? BCE_XOR : BCE_XOR_FAST), (uint32_t)g.in[0], (uint32_t)g.in[1], (uint32_t)g.out, 0, 0});
                 } else if (g.op == GateEnum::XOR) {
                     const uint32_t t1 = tmp0 + 2 * x, t2 = t1 + 1;
                     ++x;
@@ -1024,9 +989,9 @@ void Circuit::executeRound(size_t level) {
             evalStrided(B, lo, hi - lo, "Clock(stage B)");
         } else {
             // reference shape: one Gate::Evaluate per gate (src/circuit.cpp:698-710)
-            GateEvalParams p = gep;
-            p.plaintext_flag = false;  // plaintext was done above for every instance
-            p.verify_flag = false;
+            // plaintext was done above for every instance and the level's checks follow below: encrypted only
+            GateEvalParams p;
+            p.encrypted_flag = true; p.cc = cc; p.xor_fast = xm == sched::XorMode::Fast; p.xor_single = xor_single;
             for (unsigned i = lo; i < hi; ++i) {
                 uint32_t x = 0;
                 for (size_t k = 0; k < L.gates.size(); ++k) {
@@ -1042,7 +1007,7 @@ void Circuit::executeRound(size_t level) {
                 }
             }
         }
-        if (verify_flag) {
+        if (opt_.verify) {
             // decrypt every output of the level, compare with the plaintext pass, repair mismatches
             std::vector<uint32_t> slots;
             std::vector<uint8_t> expect;
@@ -1076,11 +1041,11 @@ void Circuit::executeRound(size_t level) {
 Outputs Circuit::Clock() {
     if (done) throw std::logic_error("done ckt clocked! should reset");  // the reference exits (src/circuit.cpp:538-541)
     if (!inputs_set_) throw std::logic_error("Clock: SetInput has not been called (no active wires)");
-    if (!plaintext_flag && !encrypted_flag) throw std::logic_error("Error either encrypted or plaintext flag must be set");
+    if (!opt_.plaintext && !opt_.encrypted) throw std::logic_error("Error either encrypted or plaintext flag must be set");
     auto t_total = Clock_t::now();
     double management = 0, execution = 0;
     uint64_t boots0 = 0;
-    if (encrypted_flag) {
+    if (opt_.encrypted) {
         requireEngine("Clock");
         ck(bce_pool_reserve(cc, instances_ * stride_), "Clock(pool)");
         bce_timing t;
@@ -1088,15 +1053,13 @@ Outputs Circuit::Clock() {
         boots0 = t.bootstraps;
     }
     size_t done_gates = 0;
-    // gate-level rounds (the reference's Clock loop) whenever a plaintext pass rides along (verify mode) or the caller asked for
-    // one Gate::Evaluate per gate (setBatched(false)); otherwise the bootstrap-depth schedule, unless setRelevel(false)
-    // (or its checks run on the device: setDeviceVerify)
-    const bool releveled = ((relevel_ || dataflow_) && encrypted_flag && !plaintext_flag && batched_) || deviceVerifyActive();
+    // gate-level rounds (the reference's Clock loop), the bootstrap-depth step schedule or the dataflow kernel: run_mode.hpp
+    const RunMode mode = runMode();
+    const bool releveled = mode.path != RunPath::Rounds;
     if (releveled) {
         auto t0 = Clock_t::now();
-        if (deviceVerifyActive()) { if (dataflowActive()) clockDataflowVerify(); else clockDeviceVerify(); }
-        else if (dataflowActive()) clockDataflow();
-        else clockReleveled();
+        if (mode.path == RunPath::Dag) clockDag(mode.device_checks);
+        else clockSteps(mode.device_checks);
         execution += ms_since(t0);
         done_gates = allGates.size();
     }
@@ -1111,7 +1074,7 @@ Outputs Circuit::Clock() {
         ++stats_.levels;
         if (!quiet_) std::cout << "\rProcessing: " << done_gates << " of " << allGates.size() << std::flush;
     }
-    if (encrypted_flag) {
+    if (opt_.encrypted) {
         auto t0 = Clock_t::now();
         bce_timing t;
         ck(bce_timing_get(cc, &t), "Clock");  // synchronizes

@@ -17,6 +17,7 @@
 
 #include "../../include/bce_circuit.h"
 #include "../../include/bce_gpu.h"
+#include "run_mode.hpp"
 #include "schedule.hpp"
 
 namespace bce {
@@ -104,12 +105,12 @@ public:
     void Reset();                                              // src/circuit.cpp:368-419
     void SetInput(const Inputs& input, bool verbose = false);  // src/circuit.cpp:455-530
     void SetInput(unsigned instance, const Inputs& input, bool verbose = false);
-    void setPlaintext(bool b) { plaintext_flag = gep.plaintext_flag = b; }
-    bool getPlaintext() const { return plaintext_flag; }
-    void setEncrypted(bool b) { encrypted_flag = gep.encrypted_flag = b; }
-    bool getEncrypted() const { return encrypted_flag; }
+    void setPlaintext(bool b) { opt_.plaintext = b; }
+    bool getPlaintext() const { return opt_.plaintext; }
+    void setEncrypted(bool b) { opt_.encrypted = b; }
+    bool getEncrypted() const { return opt_.encrypted; }
     void setVerify(bool b);                                    // src/circuit.cpp:833-840
-    bool getVerify() const { return verify_flag; }
+    bool getVerify() const { return opt_.verify; }
     Outputs Clock();                                           // src/circuit.cpp:532-573
     void dumpNetList() const;
     void dumpGates() const;
@@ -118,80 +119,67 @@ public:
     // ---- extensions --------------------------------------------------------------
     void setInstances(unsigned k);            // K lock-step input sets (before SetInput)
     unsigned getInstances() const { return instances_; }
-    void setBatched(bool b) { setModeFlag(batched_, b, "setBatched"); }
+    // ---- what a Clock() runs.  The setters below record choices; which path, XOR lowering, device checks and graph
+    // replay result from them is decided in ONE place, resolve_mode() in run_mode.hpp (table: DESIGN.md 5.1), and the
+    // four ...Active() predicates report its answer for the next Clock().
+    void setBatched(bool b) { setModeFlag(opt_.batched, b, "setBatched"); }   // false: one Gate::Evaluate per gate
     // cc.Encrypt(sk, bit) of SetInput (src/circuit.cpp:506) and of the verify-mode repairs (src/gate.cpp:118,139,143,158,179,211):
     // BCE_BOOTSTRAPPED by default, as OpenFHE v1.0.x's Encrypt defaults to BOOTSTRAPPED (one Bootstrap per fresh ciphertext);
     // BCE_FRESH is the opt-in that skips it
-    void setEncryptMode(int mode) { encrypt_mode_ = gep.encrypt_mode = mode; }
+    void setEncryptMode(int mode) { encrypt_mode_ = mode; }
     int getEncryptMode() const { return encrypt_mode_; }
-    // opt-in, NOT the reference's semantics: evaluate XOR natively with OpenFHE's XOR_FAST gate
-    // (src/gate.cpp:194-196 disables it "for now" because of its higher failure rate)
-    void setXorFast(bool b);
-    // opt-in: XOR as AND(OR(a, b), NAND(a, b)) with the OR and the NAND from ONE blind rotation (a BCE_PAIR descriptor,
-    // bce_gpu.h): two blind rotations per XOR instead of three, in the same two steps, and every gate input is still the sum
-    // of two refreshed ciphertexts.  The XOR's two temporaries hold other ciphertexts than the reference lowering's; every
-    // netlist wire holds the same BIT.  Before SetInput; not together with setXorFast.  Active with batched launches on the
-    // bootstrap-depth schedule, without gate sharding and without a host-side verify pass (setVerify without
-    // setDeviceVerify); otherwise the reference lowering runs exactly as without it.  With setDataflow on top the step
-    // schedule runs (dataflowActive() is false) unless setDataflowShared is on too: then the dataflow kernel runs pair tasks.
-    // The lowering is fixed at SetInput, and so is whether it is active: setBatched, setRelevel, setDeviceVerify and
-    // setVerify rebuild the units and the schedule when they change xorSharedActive() before SetInput, and are refused
-    // (std::logic_error, BCE_ERR_STATE; the flag keeps its value) when they would change it after.  The pool is laid out
-    // for the schedule of one lowering: slack filling spreads the 2-rotation XORs over other steps than the 3-rotation
-    // ones, so the other lowering can need more temporaries per step than the stride has (adder_64bit, K = 64: 899
-    // slots laid out, 923 needed).  With the option off these calls behave as they always did.  Reset() lifts it.
-    void setXorShared(bool b);
-    // opt-in, not an OpenFHE gate: XOR as ONE BCE_XOR bootstrap of ct1 + ct2 (three-level test polynomial, bce_gpu.h): the
-    // bootstrap count and depth of XOR_FAST at a plain gate's noise (every level q/8 from both boundaries).  On every path
-    // XOR_FAST runs on.  Before SetInput (the slot stride depends on it: std::logic_error after); not together with
-    // setXorFast or setXorShared (std::invalid_argument).
-    void setXorSingle(bool b);
-    bool getXorSingle() const { return xor_single_; }
-    bool getXorShared() const { return xor_shared_; }
-    bool xorSharedActive() const { return xor_shared_ && batched_ && relevel_ && !gateSharded() && !(verify_flag && !device_verify_); }
+    // The XOR lowering: ONE choice, three opt-in setters (std::invalid_argument when another one is on).
+    //   setXorFast:   OpenFHE's XOR_FAST gate, one bootstrap of 2 (ct1 - ct2); NOT the reference's semantics
+    //                 (src/gate.cpp:194-196 disables it "for now" because of its higher failure rate).
+    //   setXorShared: AND(OR(a, b), NAND(a, b)) with the OR and the NAND from one blind rotation (a BCE_PAIR descriptor):
+    //                 two rotations per XOR instead of three, the same two steps, the same BIT on every netlist wire.
+    //                 Before SetInput (std::logic_error after).  Where it is not active (xorSharedActive()) the reference
+    //                 lowering runs.  The lowering and the pool layout are fixed at SetInput: setBatched, setRelevel,
+    //                 setDeviceVerify and setVerify are refused after it (std::logic_error, the flag keeps its value)
+    //                 where they would change xorSharedActive().  Reset() lifts that.
+    //   setXorSingle: one BCE_XOR bootstrap of ct1 + ct2 (three-level test polynomial, bce_gpu.h): XOR_FAST's count and
+    //                 depth at a plain gate's noise, on every path XOR_FAST runs on.  Before SetInput (std::logic_error after).
+    void setXorFast(bool b) { chooseXor(XorChoice::Fast, b, false); }
+    void setXorShared(bool b) { chooseXor(XorChoice::Shared, b, true); }
+    void setXorSingle(bool b) { chooseXor(XorChoice::Single, b, true); }
+    XorChoice getXorChoice() const { return opt_.xor_choice; }
+    bool xorSharedActive() const { return xorMode() == sched::XorMode::Shared; }
     // opt-in: schedule by BOOTSTRAP depth instead of gate level -- NOT gates are folded into their
     // consumers' prep (neg flags) and an XOR's OR shares a launch with the next level's ANDs.  Same
     // ciphertexts as the level schedule (EvalNOT is deterministic), fewer dependent launches.
-    void setRelevel(bool b) { setModeFlag(relevel_, b, "setRelevel"); }
-    bool getRelevel() const { return relevel_; }
+    void setRelevel(bool b) { setModeFlag(opt_.relevel, b, "setRelevel"); }
+    bool getRelevel() const { return opt_.relevel; }
     // the bootstrap-depth schedule fills its steps by slack up to the launch staircase of the engine (default on; see
     // sched::place_by_slack).  lone / full = 0: ask the engine (bce_launch_capacity), else use these capacities (tests).
     void setBalance(bool on, uint32_t lone = 0, uint32_t full = 0) { balance_ = on; cap_lone_ = lone; cap_full_ = full; rebuildRelevel(); }
     // opt-in: hand the engine the whole bootstrap DAG (bce_dag_*): ONE persistent launch per Clock() in which a finished
     // bootstrap releases its consumers on the device -- the ready-gate rule of the reference's manager
     // (src/circuit.cpp:575-683) applied per gate instead of per frontier.  Same ciphertexts in every register as the
-    // other schedules.  XOR temporaries get slots of their own (SSA), so it must be chosen before SetInput (switching it off and
-    // on again later keeps that layout); it is
-    // ignored (the bootstrap-depth schedule runs) under gate sharding, for parameter classes without the persistent
-    // kernel, and in verify mode unless setDeviceVerify is on too: then the checks run inside the persistent kernel
-    // (bce_dag_set_checks), between a bootstrap and the release of its consumers.
+    // other schedules.  XOR temporaries get slots of their own (SSA), so choose it before SetInput (switching it off and
+    // on again later keeps that layout).  Where it is not available (dataflowActive()) the step schedule runs.
     void setDataflow(bool b);
-    bool getDataflow() const { return dataflow_; }
-    // opt-in on top of setDataflow and setXorShared: keep the shared lowering on the dataflow schedule.  The task list is
-    // then lowered in XorMode::Shared (per XOR a pair task writing the XOR's own two temporaries and an AND of the two: two
-    // tasks instead of three, the same slot stride) and goes to the engine through bce_dag_create_pairs; dataflowActive()
-    // and xorSharedActive() are both true.  Verify mode on the device checks the AND tasks.  Without it the two options
-    // together run the step schedule, as they always did.  Before SetInput (std::logic_error after, if it would change).
+    bool getDataflow() const { return opt_.dataflow; }
+    // opt-in on top of setDataflow and setXorShared: keep the shared lowering on the dataflow schedule, as pair tasks
+    // (bce_dag_create_pairs: per XOR a pair task and an AND, the same slot stride).  Without it the two options together
+    // run the step schedule.  Before SetInput (std::logic_error after, if it would change).
     void setDataflowShared(bool b);
-    bool getDataflowShared() const { return dataflow_shared_; }
+    bool getDataflowShared() const { return opt_.dataflow_shared; }
     // opt-in: replay the bootstrap-depth schedule's launches as ONE hipGraph per Clock() (bce_plan_run) instead of one
-    // host call per step.  Same ciphertexts.  Not with gate sharding (the per-step exchange is a host call) or verify mode on
-    // the host path (setDeviceVerify: the checks are captured with the steps).
-    void setGraph(bool b) { graph_ = b; }
-    bool getGraph() const { return graph_; }
-    bool graphActive() const { return graph_ && cc && relevel_ && !dataflowActive() && (!verify_flag || deviceVerifyActive()) && !gateSharded(); }
+    // host call per step.  Same ciphertexts.
+    void setGraph(bool b) { opt_.graph = b; }
+    bool getGraph() const { return opt_.graph; }
+    bool graphActive() const { return runMode().graph; }
     // opt-in: verify mode (src/gate.cpp:153-160: decrypt every gate output, compare with the plaintext pass, "Bad <OP> fixing",
-    // replace) checked ON THE DEVICE between the steps of the bootstrap-depth schedule (bce_plan_set_checks) instead of the
-    // gate-level rounds with one host decryption per level.  Active with verify on, batched launches, the bootstrap-depth
-    // schedule and no gate sharding; otherwise the host path runs as before.  Differences to the host path: a repaired
-    // register holds the trivial ciphertext of the right bit (bce_gpu.h), and NOT gates have no register on this schedule, so
-    // a wrong NOT input is caught at its consumer -- fix counts can differ from the gate-level path for that reason.
-    // Together with setDataflow the same checks run on the dataflow schedule instead: one persistent launch per Clock().
-    void setDeviceVerify(bool b) { setModeFlag(device_verify_, b, "setDeviceVerify"); }
-    bool getDeviceVerify() const { return device_verify_; }
-    bool deviceVerifyActive() const { return device_verify_ && verify_flag && encrypted_flag && cc && batched_ && relevel_ && !gateSharded(); }
+    // replace) checked ON THE DEVICE between the steps of the bootstrap-depth schedule (bce_plan_set_checks), or inside the
+    // persistent kernel with setDataflow, instead of the gate-level rounds with one host decryption per level.  Differences
+    // to the host path: a repaired register holds the trivial ciphertext of the right bit (bce_gpu.h), and NOT gates have no
+    // register on these schedules, so a wrong NOT input is caught at its consumer -- fix counts can differ for that reason.
+    void setDeviceVerify(bool b) { setModeFlag(opt_.device_verify, b, "setDeviceVerify"); }
+    bool getDeviceVerify() const { return opt_.device_verify; }
+    bool deviceVerifyActive() const { return runMode().device_checks; }
     const bce_check_report& checkReport() const { return check_report_; }   // of the last Clock() on the device path
-    bool dataflowActive() const { return dataflow_ && (!xorSharedActive() || dataflow_shared_) && cc && (!verify_flag || deviceVerifyActive()) && !gateSharded() && bce_dag_supported(cc) && !tasks_.tasks.empty(); }
+    bool dataflowActive() const { return runMode().dataflow; }
+    RunMode runMode() const;                  // resolve_mode() of the choices and this circuit's facts
     const std::vector<bce_gate_desc>& dataflowTasks() const { return tasks_.tasks; }
     const std::vector<uint8_t>& dataflowPriorities() const { return tasks_.prio; }
     bool getBalance() const { return balance_; }
@@ -199,7 +187,6 @@ public:
     const std::vector<std::vector<bce_gate_desc>>& relevelStepDescs() const { return steps_.steps; }   // this rank's descriptors, instance 0
     std::vector<uint32_t> relevelPublications() const;       // registers this rank publishes per step (gate sharding)
     bool checkRelevelPlan(std::string* why = nullptr) const { return sched::check(steps_, net_, rank_, gateSharded() ? world_ : 1, why); }
-    bool getXorFast() const { return xor_fast_; }
     void setQuiet(bool q) { quiet_ = q; }
     // re-arm for another Clock() on the SAME inputs: keeps mode flags and the input ciphertexts
     // already resident in the device pool (registers are SSA, inputs are never overwritten)
@@ -242,10 +229,9 @@ private:
 
     bce_ctx* cc = nullptr;
     bool owns_engine_ = false;
-    bool plaintext_flag = false, encrypted_flag = false, verify_flag = false;
-    bool done = false, inputs_set_ = false, quiet_ = false, batched_ = true, xor_fast_ = false, xor_shared_ = false, xor_single_ = false;
+    ModeInputs opt_;   // the caller's choices; the facts are filled in by runMode()
+    bool done = false, inputs_set_ = false, quiet_ = false;
     int encrypt_mode_ = BCE_BOOTSTRAPPED;
-    GateEvalParams gep;
 
     std::vector<LoadRec> inputGates;  // LOADs
     std::vector<ConstRec> constWires_; // constants (live from the start, like inputs)
@@ -286,14 +272,13 @@ private:
     void finalizeNetlist();
     void buildShardPlan();
     std::pair<unsigned, unsigned> instanceRange() const;   // [lo, hi): the instances this rank evaluates
-    bool relevel_ = true;   // the bootstrap-depth schedule is the default since round 4 (identical registers, 416 instead of 496
-                            // dependent launches on AES-expanded); setRelevel(false) = the reference's gate-level rounds, src/circuit.cpp:532-573
     sched::Dag net_;          // the levelised netlist as the schedule module reads it
     sched::Units units_;      // rebuilt when the netlist or the XOR mode changes
     sched::XorMode units_mode_ = sched::XorMode::Reference;   // the mode units_ were built for
-    sched::XorMode xorMode() const { return xor_fast_ ? sched::XorMode::Fast : xor_single_ ? sched::XorMode::Single : xorSharedActive() ? sched::XorMode::Shared : sched::XorMode::Reference; }
+    sched::XorMode xorMode() const { return runMode().xor_mode; }
     void buildUnits() { units_mode_ = xorMode(); units_ = sched::build_units(net_, units_mode_); tasks_ = {}; }
-    void syncXorMode();       // after a change of anything xorSharedActive() reads: units and schedules for the mode that now holds
+    void syncXorMode();       // after a change of anything xorMode() reads: units and schedules for the mode that now holds
+    void chooseXor(XorChoice which, bool on, bool before_input);
     void setModeFlag(bool& flag, bool b, const char* who);   // sets one of those flags; refused after SetInput where it would switch the lowering
     sched::StepPlan steps_;   // bootstrap-depth schedule: redone when K, capacities, world, locality or balance change
     sched::TaskList tasks_;   // dataflow schedule: held only while it is chosen
@@ -301,13 +286,11 @@ private:
     bool balance_ = true;
     uint32_t cap_lone_ = 0, cap_full_ = 0;
     std::pair<uint32_t, uint32_t> launchCapacity() const;   // (lone, full) of the launch staircase: set by the caller, else the engine's
-    bool dataflow_ = false, dataflow_shared_ = false;
     bool tasksHavePairs() const { return units_mode_ == sched::XorMode::Shared; }          // of a task list lowered from units_
-    bool tasksExist() const { return !tasksHavePairs() || dataflow_shared_; }              // the dataflow schedule has a list for units_
+    bool tasksExist() const { return !tasksHavePairs() || opt_.dataflow_shared; }              // the dataflow schedule has a list for units_
     sched::TaskList lowerTasks() const { return sched::lower_tasks(units_, net_.n_wires, tasksHavePairs()); }
     void createDag(bce_dag** g);               // bce_dag_create, or bce_dag_create_pairs for a list with pairs
     bce_dag* dag_ = nullptr;
-    bool graph_ = false;
     bce_plan* plan_ = nullptr;                 // the schedule's descriptors resident on the device (and its captured graph)
     uint32_t plan_lo_ = 0, plan_K_ = 0, plan_stride_ = 0;
     bce_plan* vplan_ = nullptr;                // the same schedule with the check lists of device verify mode attached (its own capture)
@@ -316,22 +299,21 @@ private:
     bce_dag* vdag_ = nullptr;                  // the same DAG with the checks of device verify mode attached
     sched::TaskChecks task_checks_;            // of vdag_
     void dropDag() { for (bce_dag** g : {&dag_, &vdag_}) if (*g) { bce_dag_destroy(cc, *g); *g = nullptr; } }
-    void clockDataflow();
-    void clockDataflowVerify();
+    void clockDag(bool verify);
     void reportChecks(const std::vector<std::vector<uint32_t>>* by_tag, const std::vector<uint32_t>* by_index);   // read the report, print and count the mismatches
     void compareOutputs(unsigned lo, unsigned hi);   // verify mode: OUTPUT gates against the plaintext pass
-    void finishReleveled(unsigned lo, unsigned hi);
+    std::vector<uint8_t> armChecks(unsigned lo, unsigned hi, const std::vector<uint32_t>& wires);   // expected bits per instance; check reset
+    void finishReleveled(unsigned lo, unsigned hi, bool verify);
     void rebuildRelevel();
     std::vector<bce_gate_desc> rebased(std::vector<bce_gate_desc> descs, unsigned lo) const;   // descriptors of instance 0 -> instance lo
     void evalStrided(const std::vector<bce_gate_desc>& descs, unsigned lo, uint32_t K, const char* what);   // one launch, if any
     void decryptOutputs(unsigned lo, unsigned hi, const std::vector<int>* gates);   // OUTPUT gates among `gates` (nullptr: all) -> circuitOut
     void countGates(const std::vector<int>* gates);
-    void clockReleveled();
-    bool device_verify_ = false;
-    sched::CheckLists checks_;                 // of vplan_: per NON-EMPTY step of steps_ (= per step of the plan)
+    void clockSteps(bool verify);
+    std::vector<std::vector<uint32_t>> check_gates_;   // of vplan_: per NON-EMPTY step of steps_ (= per step of the plan), the owning gates
+    std::vector<uint32_t> check_wires_;                // ... and the registers checked, step after step
     bce_check_report check_report_{};
     void ensurePlan(bce_plan*& plan, unsigned lo, uint32_t K);  // the schedule's descriptors resident on the device
-    void clockDeviceVerify();
     void plainRound(size_t level);             // the plaintext pass of one gate level
     void managerRound(size_t level);
     void executeRound(size_t level);

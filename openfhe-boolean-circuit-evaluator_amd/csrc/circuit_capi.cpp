@@ -83,7 +83,7 @@ int bce_circuit_set_encrypt_mode(bce_circuit* h, int mode) {
 int bce_circuit_set_xor_fast(bce_circuit* h, int on) { return guarded(h, [&] { h->c.setXorFast(on != 0); }); }
 int bce_circuit_set_xor_shared(bce_circuit* h, int on) { return guarded(h, [&] { h->c.setXorShared(on != 0); }); }
 int bce_circuit_set_xor_single(bce_circuit* h, int on) { return guarded(h, [&] { h->c.setXorSingle(on != 0); }); }
-int bce_circuit_get_xor_single(const bce_circuit* h) { return h && h->c.getXorSingle() ? 1 : 0; }
+int bce_circuit_get_xor_single(const bce_circuit* h) { return h && h->c.getXorChoice() == bce::XorChoice::Single ? 1 : 0; }
 int bce_circuit_xor_shared_active(const bce_circuit* h) { return h && h->c.xorSharedActive() ? 1 : 0; }
 int bce_circuit_set_relevel(bce_circuit* h, int on) { return guarded(h, [&] { h->c.setRelevel(on != 0); }); }
 int bce_circuit_get_relevel(bce_circuit* h) { return h && h->c.getRelevel() ? 1 : 0; }
@@ -102,6 +102,16 @@ int bce_circuit_get_check_report(const bce_circuit* h, bce_check_report* out) {
     if (!h || !out) return BCE_ERR_ARG;
     *out = h->c.checkReport();
     return BCE_OK;
+}
+uint32_t bce_circuit_resolve_mode(uint32_t in) {
+    auto bit = [&](int k) { return ((in >> k) & 1u) != 0; };
+    bce::ModeInputs m;
+    m.plaintext = bit(0); m.encrypted = bit(1); m.verify = bit(2); m.batched = bit(3); m.relevel = bit(4); m.graph = bit(5);
+    m.device_verify = bit(6); m.dataflow = bit(7); m.dataflow_shared = bit(8);
+    m.xor_choice = (bce::XorChoice)((in >> 9) & 3u);
+    m.engine = bit(11); m.dag_supported = bit(12); m.gate_sharded = bit(13); m.tasks = bit(14);
+    const bce::RunMode r = bce::resolve_mode(m);
+    return (uint32_t)r.path | (uint32_t)r.xor_mode << 2 | (uint32_t)r.device_checks << 4 | (uint32_t)r.graph << 5 | (uint32_t)r.dataflow << 6;
 }
 int bce_circuit_dataflow_plan(const bce_circuit* h, bce_gate_desc* tasks, uint8_t* prio, uint32_t cap, uint32_t* n_tasks) {
     if (!h || !n_tasks) return BCE_ERR_ARG;
