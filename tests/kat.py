@@ -63,6 +63,12 @@ def parity_case(test_ix):
     return [bits], [1 - odd, odd]
 
 
+def parity_cascade_case(test_ix):
+    """second run of every loop: the even-parity bit goes into bit 8, the word is now odd (src/test_parity.cpp:291-297)"""
+    (bits,), (even, _) = parity_case(test_ix)
+    return [bits[:8] + [even]], [0, 1]
+
+
 def hash_vectors(test_file):
     """(inhex, outhex) pairs of md5-test.txt / sha-256-test.txt"""
     ins, outs = [], []

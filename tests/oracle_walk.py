@@ -99,8 +99,9 @@ def rounds(nl):
     return out
 
 
-def evaluate(O, o, nl, inputs, enc_index=0, nthreads=0, fresh=False):
-    """Encrypted evaluation on oracle context `o` (module `O` = oracle.oracle); returns (output bits, bootstraps)."""
+def evaluate(O, o, nl, inputs, enc_index=0, nthreads=0, fresh=False, pool_out=None):
+    """Encrypted evaluation on oracle context `o` (module `O` = oracle.oracle); returns (output bits, bootstraps).
+    A list passed as `pool_out` receives the final register file (rows [0, n_regs): the netlists are SSA)."""
     W = o.n + 1
     ready = rounds(nl)
     widest = max(sum(1 for g in r if g[0] == "XOR") for r in ready) if ready else 0
@@ -132,4 +133,6 @@ def evaluate(O, o, nl, inputs, enc_index=0, nthreads=0, fresh=False):
             if stage:
                 boots += o.eval_gates(pool, stage, nthreads)
     n_out = 1 + max(nl.stores)
+    if pool_out is not None:
+        pool_out.append(pool[:T].copy())
     return [o.decrypt(pool[nl.stores[k]]) for k in range(n_out)], boots
