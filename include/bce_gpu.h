@@ -353,7 +353,7 @@ uint32_t bce_forward_units(const bce_ctx*);
  * csrc/fwd_mfma.hpp for this Q); 0: the quarter-unit body, in other contexts or with BCE_FWD_MFMA=0 at context creation. */
 uint32_t bce_forward_mfma(const bce_ctx*);
 /* 1 when the context was granted the lazy arithmetic of the 32-bit kernels (forward transforms without corrections, 64-bit
- * MAC sums, Montgomery MAC tail: the bounds ok1..ok5 of derive_ctx, csrc/engine.cpp, hold for this Q, N and digit count);
+ * MAC sums, Montgomery MAC tail: the bounds ok1..ok5 of derive_params, csrc/ctx_params.cpp, hold for this Q, N and digit count);
  * 0: the corrected forms.  Always 1 for Q >= 2^28 (the 64-bit kernels have one form).  Read-only; for tests that look for the
  * largest modulus of a class. */
 uint32_t bce_lazy_arithmetic(const bce_ctx*);
@@ -370,6 +370,41 @@ int bce_forward_mfma_tables(uint64_t Q, uint32_t N, uint32_t gBits, uint32_t dG,
  * *lone = bootstraps up to which every workgroup has a compute unit to itself (one bootstrap latency per call),
  * *full = bootstraps resident at once when the device is saturated (each further multiple costs one more round). */
 int bce_launch_capacity(const bce_ctx*, uint32_t* lone, uint32_t* full);
+
+/* ---- what a context would decide, without a context or a device --------- */
+/* The derivation bce_ctx_create* runs (csrc/ctx_params.cpp), for `cu_count` compute units and the context knobs of the
+ * environment: one 64-bit value per item.  BCE_D_n .. BCE_D_w14s are the scalar fields of the kernels'
+ * parameter block under their own names (doubles as their bit patterns), then: the per-XCD counters are wanted, the 2N-th
+ * root, the granted kernel class (family: 0 one wave per transform, 1 split transform, 2 64-bit integer, 3 doubles), what
+ * bce_launch_capacity, bce_bytes_per_bootstrap_parts and bce_forward_transforms_per_step would answer, FNV-1a-64 digests of
+ * the host tables' bytes, and the LDS bytes of one workgroup of the persistent kernel's two-per-CU build (0 for Q >= 2^28).
+ * Returns the status bce_ctx_create* would return on a machine with a device (never BCE_ERR_NO_DEVICE); *message (may be
+ * NULL) receives the text bce_last_error would hold, "" for BCE_OK; `out` is all zero unless BCE_OK. */
+enum { BCE_D_n = 0, BCE_D_N, BCE_D_logN, BCE_D_q, BCE_D_Q, BCE_D_qKS, BCE_D_baseKS, BCE_D_dKS, BCE_D_ksk_stride, BCE_D_ksk_u16,
+       BCE_D_ks_chunk, BCE_D_gBits, BCE_D_dG, BCE_D_baseR, BCE_D_dR, BCE_D_method_ap, BCE_D_factor, BCE_D_Q8p1, BCE_D_red_shift,
+       BCE_D_red_mu, BCE_D_Ninv, BCE_D_Ninv_s, BCE_D_Winv_last, BCE_D_Winv_last_s, BCE_D_mu32, BCE_D_lazy, BCE_D_c32,
+       BCE_D_occupancy_target, BCE_D_variant, BCE_D_cu_count, BCE_D_xcd_gate_ticks, BCE_D_fuse_tail, BCE_D_fold_ninv, BCE_D_fold,
+       BCE_D_fwd_units, BCE_D_factor_even, BCE_D_I4_0, BCE_D_I4_1, BCE_D_I4_2, BCE_D_I4_3, BCE_D_I4s_0, BCE_D_I4s_1, BCE_D_I4s_2,
+       BCE_D_I4s_3, BCE_D_qinv_neg, BCE_D_r2_off, BCE_D_is64, BCE_D_Q64, BCE_D_Q8p1_64, BCE_D_mu64, BCE_D_c64, BCE_D_Ninv64,
+       BCE_D_Ninv64_s, BCE_D_fp64, BCE_D_Qd, BCE_D_invQd, BCE_D_Ninvd, BCE_D_Ninvd_q, BCE_D_pool_stride, BCE_D_fwd_mfma, BCE_D_w14,
+       BCE_D_w14s,
+       BCE_D_xcd_gate, BCE_D_psi,
+       BCE_D_family, BCE_D_fold_build, BCE_D_dag, BCE_D_wg_per_cu_lone, BCE_D_wg_per_cu_full, BCE_D_lds_bytes,
+       BCE_D_capacity_lone, BCE_D_capacity_full, BCE_D_bytes_bsk, BCE_D_bytes_ksk, BCE_D_bytes_ct, BCE_D_forward_transforms,
+       BCE_D_fnv_twf, BCE_D_fnv_psi, BCE_D_fnv_psi_r2, BCE_D_fnv_tw64, BCE_D_fnv_tw64d, BCE_D_fnv_fwd_mfma,
+       BCE_D_dag_lds_bytes, BCE_D_COUNT };
+int bce_params_derive(uint32_t n, uint32_t N, uint64_t q, uint64_t Q, uint64_t qKS, uint32_t baseKS, uint32_t baseG, uint32_t baseR,
+                      int method, uint32_t cu_count, uint64_t out[BCE_D_COUNT], const char** message);
+/* the same for a tabulated set (enum bce_paramset) */
+int bce_params_derive_set(int paramset, int method, uint32_t cu_count, uint64_t out[BCE_D_COUNT], const char** message);
+/* What bce_dag_run would launch for a context with the report `derived` (of the two entries above), the limits of
+ * bce_dag_set_limits, a DAG whose longest chain has `depth` tasks and `items` = tasks x instances bootstraps, under the DAG
+ * knobs of the environment: out[BCE_L_wps] 2 = one workgroup per compute unit, 4 = two (bce_dag_last_run's out[3] is half of
+ * it); the grid; the policy bits, gate and timeout words the device scheduler receives; re-arm only (development). */
+enum { BCE_L_wps = 0, BCE_L_grid, BCE_L_policy, BCE_L_gate_ticks, BCE_L_gate_backlog, BCE_L_lazy_ticks, BCE_L_stall_ticks,
+       BCE_L_rearm_only, BCE_L_COUNT };
+int bce_dag_launch_choice(const uint64_t derived[BCE_D_COUNT], int workgroups_per_cu, int placement, uint32_t lazy_us,
+                          uint32_t stall_ms, uint32_t depth, uint64_t items, uint64_t out[BCE_L_COUNT]);
 
 /* ---- in-library collective (multi-GPU, one process per GPU) ---------------------------------------------
  * RCCL all-gather issued on the engine's own stream, so that the exchange of boundary ciphertexts between two

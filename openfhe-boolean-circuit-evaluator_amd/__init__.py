@@ -94,6 +94,7 @@ ENGINE_SYMBOLS = [
     "bce_rccl_shutdown", "bce_debug_eval_stages", "bce_debug_ntt", "bce_debug_tail", "bce_debug_tail_split",
     "bce_dag_supported", "bce_dag_create", "bce_dag_create_pairs", "bce_dag_run", "bce_dag_destroy", "bce_dag_set_limits", "bce_dag_last_run", "bce_dag_debug_block_task",
     "bce_dag_set_checks", "bce_dag_set_expected",
+    "bce_params_derive", "bce_params_derive_set", "bce_dag_launch_choice",
     "bce_plan_create", "bce_plan_run_step", "bce_plan_run", "bce_plan_destroy",
     "bce_check_slots", "bce_plan_set_checks", "bce_plan_set_expected", "bce_check_reset", "bce_check_get",
 ]
@@ -210,8 +211,49 @@ def lib():
     L.bce_plan_set_expected.argtypes = [vp, vp, vp]
     L.bce_check_reset.argtypes = [vp]
     L.bce_check_get.argtypes = [vp, C.POINTER(CheckReport), C.POINTER(CheckEntry), u32]
+    L.bce_params_derive.argtypes = [u32, u32, u64, u64, u64, u32, u32, u32, i32, u32, C.POINTER(u64), C.POINTER(C.c_char_p)]
+    L.bce_params_derive_set.argtypes = [i32, i32, u32, C.POINTER(u64), C.POINTER(C.c_char_p)]
+    L.bce_dag_launch_choice.argtypes = [C.POINTER(u64), i32, i32, u32, u32, u32, u64, C.POINTER(u64)]
     _lib = L
     return L
+
+
+# enum BCE_D_* / BCE_L_* of include/bce_gpu.h
+D_NAMES = ["n", "N", "logN", "q", "Q", "qKS", "baseKS", "dKS", "ksk_stride", "ksk_u16", "ks_chunk", "gBits", "dG", "baseR", "dR",
+           "method_ap", "factor", "Q8p1", "red_shift", "red_mu", "Ninv", "Ninv_s", "Winv_last", "Winv_last_s", "mu32", "lazy", "c32",
+           "occupancy_target", "variant", "cu_count", "xcd_gate_ticks", "fuse_tail", "fold_ninv", "fold", "fwd_units", "factor_even",
+           "I4_0", "I4_1", "I4_2", "I4_3", "I4s_0", "I4s_1", "I4s_2", "I4s_3", "qinv_neg", "r2_off", "is64", "Q64", "Q8p1_64", "mu64",
+           "c64", "Ninv64", "Ninv64_s", "fp64", "Qd", "invQd", "Ninvd", "Ninvd_q", "pool_stride", "fwd_mfma", "w14", "w14s",
+           "xcd_gate", "psi", "family", "fold_build", "dag", "wg_per_cu_lone", "wg_per_cu_full", "lds_bytes",
+           "capacity_lone", "capacity_full", "bytes_bsk", "bytes_ksk", "bytes_ct", "forward_transforms",
+           "fnv_twf", "fnv_psi", "fnv_psi_r2", "fnv_tw64", "fnv_tw64d", "fnv_fwd_mfma", "dag_lds_bytes"]
+L_NAMES = ["wps", "grid", "policy", "gate_ticks", "gate_backlog", "lazy_ticks", "stall_ticks", "rearm_only"]
+
+
+def derive_params(paramset=None, method=GINX, cu_count=256, custom=None):
+    """What a context of this shape would decide about itself, for `cu_count` compute units and the context knobs of the
+    environment; no context, no GPU.  custom = (n, N, q, Q, qKS, baseKS, baseG, baseR) instead of a tabulated set.  Returns
+    {"status", "message"} and, for status OK, every value of enum BCE_D_* by name (doubles as bit patterns)."""
+    L = lib()
+    out, msg = (C.c_uint64 * len(D_NAMES))(), C.c_char_p()
+    if custom is not None:
+        rc = L.bce_params_derive(*[int(v) for v in custom], method, cu_count, out, C.byref(msg))
+    else:
+        rc = L.bce_params_derive_set(paramset, method, cu_count, out, C.byref(msg))
+    d = {"status": int(rc), "message": (msg.value or b"").decode()}
+    if rc == OK:
+        d.update(zip(D_NAMES, [int(v) for v in out]))
+    return d
+
+
+def dag_launch_choice(derived, depth, items, workgroups_per_cu=0, placement=1, lazy_us=20, stall_ms=4000):
+    """What bce_dag_run would launch for a context that derive_params() describes, under the DAG knobs of the environment."""
+    L = lib()
+    rep, out = (C.c_uint64 * len(D_NAMES))(*[derived[k] for k in D_NAMES]), (C.c_uint64 * len(L_NAMES))()
+    rc = L.bce_dag_launch_choice(rep, workgroups_per_cu, placement, lazy_us, stall_ms, depth, items, out)
+    if rc != OK:
+        raise BceError(rc, "bce_dag_launch_choice")
+    return dict(zip(L_NAMES, [int(v) for v in out]))
 
 
 def _p(a):

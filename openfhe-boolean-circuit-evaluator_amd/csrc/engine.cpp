@@ -5,8 +5,8 @@
 // (src/circuit.cpp:506,800) and the per-gate EvalBinGate / EvalNOT calls
 // (src/gate.cpp:112,133,172,198-202), the latter batched per ready frontier.
 // There is no CPU compute path here: without a HIP device every call fails loudly.
-// This file: the context (derivation, tables, keys, pool and LWE I/O), one frontier of gates, timing and the debug entry
-// points.  The schedules built on it live in engine_plan.cpp (bce_plan, bce_check_*) and engine_dag.cpp (bce_dag).
+// This file: the context (its tables on the device, keys, pool and LWE I/O; what it decides about itself is ctx_params.cpp),
+// one frontier of gates, timing and the debug entry points.  The schedules built on it live in engine_plan.cpp (bce_plan, bce_check_*) and engine_dag.cpp (bce_dag).
 #include <sys/random.h>
 
 #include <algorithm>
@@ -15,9 +15,9 @@
 #include <memory>
 
 #include "../../include/bce_circuit.h"
+#include "ctx_params.hpp"
 #include "desc.hpp"
 #include "engine_internal.hpp"
-#include "fwd_mfma.hpp"
 #include "host_math.hpp"
 #include "keygen.hpp"
 #include "prng.hpp"
@@ -32,21 +32,6 @@ static_assert(sizeof(bce_check_report) == 48 && sizeof(bce_check_entry) == 24, "
 namespace {
 
 thread_local std::string g_create_error;
-
-struct ParamRow { u32 bits, cyclo, n; u64 q, qKS; u32 baseKS, baseG, baseR; };
-// OpenFHE v1.0.x GenerateBinFHEContext table: {numberBits, cyclOrder, latticeParam, mod, modKS(0 = PRIME), baseKS, gadgetBase, baseRK}
-const ParamRow kParamTable[] = {
-    {27, 1024, 64, 512, 0, 25, 1u << 9, 23},              // TOY
-    {28, 2048, 422, 1024, 1u << 14, 1u << 7, 1u << 10, 32},  // MEDIUM
-    {27, 2048, 512, 1024, 1u << 14, 1u << 7, 1u << 9, 32},   // STD128_AP
-    {27, 2048, 502, 1024, 1u << 14, 1u << 7, 1u << 9, 32},   // STD128_APOPT
-    {27, 2048, 512, 1024, 1u << 14, 1u << 7, 1u << 7, 32},   // STD128
-    {27, 2048, 502, 1024, 1u << 14, 1u << 7, 1u << 7, 32},   // STD128_OPT
-    {37, 4096, 1024, 1024, 1u << 19, 28, 1u << 13, 32},      // STD192
-    {37, 4096, 805, 1024, 1u << 15, 32, 1u << 13, 32},       // STD192_OPT
-    {29, 4096, 1024, 2048, 1u << 14, 1u << 7, 1u << 8, 46},  // STD256
-    {29, 4096, 990, 2048, 1u << 14, 1u << 7, 1u << 8, 46},   // STD256_OPT
-};
 
 // 32 bytes from the operating system's entropy pool (getrandom, then /dev/urandom).  There is no fixed
 // fallback value: a context that cannot get entropy fails to draw keys / encryption randomness.
@@ -65,199 +50,7 @@ bool os_entropy(uint8_t out[32]) {
     return n == 32;
 }
 
-// development / parity knobs that default to on: NAME=0 switches the feature off
-bool env_off(const char* name) {
-    const char* e = std::getenv(name);
-    return e && e[0] == '0';
-}
-
-// What derive_ctx builds on the host for upload_ctx to put on the device
-struct HostTables {
-    std::vector<uint2> twf;         // [N] (psi^brv(i), Shoup companion) in the device layout of kernels.hip (tw_pos)
-    std::vector<u32> psi, psi_r2;   // [N] psi^e in natural exponent order, and psi^e R^2 (R = 2^32)
-    std::vector<ulonglong2> tw64;   // 64-bit path: [N] (psi^brv(i), floor(. 2^64 / Q)) ...
-    std::vector<double2> tw64d;     // ... and (psi^brv(i), psi^brv(i) / Q) for the double-precision formulation
-    FwdMfmaTables fwd;              // A operands of the matrix-pipe forward stages (used when P.fwd_mfma)
-    bool xcd_gate = false;          // the per-XCD arrival counters are wanted
-};
-
-// First half of build_ctx: the rest of the validation, every scalar field of c->P and the host tables.  No HIP call, so the
-// decisions can be checked on a machine without a device; cu_count is the one thing asked of the device beforehand.
-int derive_ctx(bce_ctx* c, u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 baseG, u32 baseR, int method, int device, u32 cu_count,
-               HostTables& T) {
-    c->n = n; c->N = N; c->q = q; c->Q = Q; c->qKS = qKS ? qKS : Q;
-    c->baseKS = baseKS; c->baseG = baseG; c->baseR = baseR; c->method = method; c->device = device;
-    while ((1u << c->logN) < N) ++c->logN;
-    while ((1u << c->gBits) < baseG) ++c->gBits;
-    c->dKS = digit_count((double)c->qKS, (double)baseKS);
-    c->dG = digit_count((double)Q, (double)baseG);
-    c->dR = digit_count((double)q, (double)baseR);
-    c->is64 = Q >= (1ull << 28);
-    c->wbytes = c->is64 ? 8 : 4;
-
-    DevParams& P = c->P;
-    P.n = n; P.N = N; P.logN = c->logN; P.q = (u32)q; P.Q = (u32)Q; P.qKS = (u32)c->qKS;
-    P.baseKS = baseKS; P.dKS = c->dKS;
-    P.ksk_stride = (n + 1 + 63) & ~63u;
-    P.ksk_u16 = c->qKS <= 65536 ? 1 : 0;
-    P.gBits = c->gBits; P.dG = c->dG; P.baseR = baseR; P.dR = c->dR;
-    P.method_ap = method == BCE_AP ? 1 : 0;
-    P.factor = (u32)(2 * N / q);
-    P.factor_even = (P.factor & 1u) ? 0 : 1;   // every STD128 set (q = N); the GINX MAC tail then needs no parity selects
-    P.Q8p1 = (u32)(Q / 8 + 1);
-    int bq = bit_length(Q);
-    P.red_shift = (u32)std::max(2 * bq + 3 - 32, 0);
-    P.red_mu = c->is64 ? 0 : (u32)((((u128)1) << (32 + P.red_shift)) / Q);
-    u64 ninv = pow_mod(N, Q - 2, Q);
-    P.Ninv = (u32)ninv;
-    P.Ninv_s = c->is64 ? 0 : (u32)(((u128)ninv << 32) / Q);
-    P.mu32 = (u32)((((u64)1) << 32) / Q);
-    P.c32 = (u32)((((u64)1) << 32) % Q);
-    {
-        // lazy forward NTT: inputs < 2Q, every stage adds < 2Q -> outputs < B*Q with B = 2*logN+2.
-        // needs (1) B*Q < 2^32, (2) R*B*Q*Q < 2^64 for the 64-bit MAC sums, (3) the folded sum
-        // (x>>32)*c32 + 2^32 below the Barrett input bound 2^(32+red_shift)
-        const u128 B = 2 * c->logN + 2, R = 2 * c->dG;
-        const u128 sum = R * B * Q * Q;
-        const bool ok1 = B * Q < ((u128)1 << 32);
-        const bool ok2 = sum < ((u128)1 << 64);
-        const u128 folded = (sum >> 32) * P.c32 + ((u128)1 << 32);
-        const bool ok3 = folded < ((u128)1 << (32 + P.red_shift));
-        // (4) MAC keeps rp, rn < 3Q and acc < 2Q: 3Q*Q + 3Q*Q + 2Q below the Barrett bound, 3Q < 2^32
-        const bool ok4 = (u128)6 * Q * Q + 2 * Q < ((u128)1 << (32 + P.red_shift)) && (u128)3 * Q < ((u128)1 << 32);
-        // (5) Montgomery form of the MAC tail (split-transform kernels): rp', rn' = REDC(sum) < sum / 2^32 + Q; the monomial
-        // factors are lazy in [0, 2Q); y = rp' M+ + rn' M- must fit 64 bits and REDC(y) < y / 2^32 + Q must stay <= 2Q, so that
-        // REDC(y) + acc (< 2Q) < 4Q < 2^32 and one conditional subtraction of 2Q returns it to [0, 2Q)
-        const u128 rmax = (sum >> 32) + 1 + Q, ymax = 2 * rmax * 2 * Q;
-        const bool ok5 = ymax < ((u128)1 << 64) && (ymax >> 32) + 1 + Q <= 2 * (u128)Q && (u128)4 * Q < ((u128)1 << 32);
-        P.lazy = (c->is64 || (ok1 && ok2 && ok3 && ok4 && ok5)) ? 1 : 0;   // (the 64-bit kernels have no other form)
-    }
-    P.is64 = c->is64 ? 1 : 0;
-    P.Q64 = Q;
-    {
-        const char* var = std::getenv("BCE_VARIANT");  // development knob, see DevParams::variant
-        P.variant = var ? (u32)std::atoi(var) : 0;
-        P.cu_count = cu_count;
-        P.fuse_tail = env_off("BCE_FUSE_TAIL") ? 0 : 1;  // development / parity knob: 0 keeps the separate tail kernels
-    }
-    // The kernel family and what follows from it (kernels.hpp, kernel_class).  Two requests go in and come back as granted:
-    // BCE_OCCUPANCY (development knob: 2 or 3 workgroups per CU of the one-wave-per-transform kernel) and the double-precision
-    // formulation of the 64-bit path (kernels64.hip, namespace wd): exact for Q < 2^39; BCE_FP64=0 keeps the integer kernel
-    // (development / parity knob)
-    const char* occ = std::getenv("BCE_OCCUPANCY");
-    P.occupancy_target = (occ && occ[0] == '2') ? 2 : 3;
-    P.fp64 = (c->is64 && Q < (1ull << 39) && !env_off("BCE_FP64")) ? 1 : 0;
-    const KernelClass kc = kernel_class(P);
-    P.occupancy_target = kc.occupancy_target;
-    P.fp64 = kc.fp64;
-    if (kc.error) { g_create_error = kc.error; return BCE_ERR_UNSUPPORTED; }
-    if (c->qKS > 0xFFFFFFFFull) { g_create_error = "qKS must fit 32 bits"; return BCE_ERR_UNSUPPORTED; }
-    c->psi = min_primitive_root(Q, 2ull * N);
-
-    // twiddle tables, OpenFHE ordering: tw[brv(i)] = psi^i
-    T.twf.resize(N);
-    T.psi.resize(N);
-    u64 p = 1;
-    for (u32 i = 0; i < N; ++i) {
-        T.psi[i] = c->is64 ? 0 : (u32)p;
-        u32 r = bit_reverse(i, (int)c->logN);
-        // device layout: blocks m >= 64 transposed to [slot][lane] (kernels.hip tw_pos)
-        u32 pos = r;
-        if (r >= 64) {
-            const u32 s = 31u - (u32)__builtin_clz(r), sh = s - 6, ii = r - (1u << s);
-            pos = (1u << s) + ((ii & ((1u << sh) - 1u)) << 6) + (ii >> sh);
-        }
-        T.twf[pos] = c->is64 ? make_uint2(0, 0) : make_uint2((u32)p, (u32)(((u128)p << 32) / Q));
-        p = mul_mod(p, c->psi, Q);
-    }
-    const u64 r2modq = c->is64 ? 0 : (u64)((((u128)1) << 64) % Q);     // R^2 mod Q, R = 2^32
-    T.psi_r2.resize(N);
-    for (u32 i = 0; i < N; ++i) T.psi_r2[i] = c->is64 ? 0 : (u32)mul_mod(T.psi[i], r2modq, Q);
-    {
-        const u64 ch = (((u64)1) << 32) / c->qKS;
-        if (ch < 8) { g_create_error = "qKS too large for the key-switch gather (needs qKS <= 2^29)"; return BCE_ERR_ARG; }
-        P.ks_chunk = (u32)std::min<u64>(ch & ~(u64)7, 1u << 20);
-    }
-    if (!c->is64) {
-        u32 inv = (u32)Q;                                  // Newton: inv = Q^-1 mod 2^32 (Q odd)
-        for (int i = 0; i < 5; ++i) inv *= 2u - (u32)Q * inv;
-        P.qinv_neg = 0u - inv;
-        P.r2_off = (u32)(Q - r2modq);
-    }
-    {
-        u64 I = pow_mod(c->psi, N / 2, Q), v = 1;
-        for (int k = 0; k < 4; ++k) {
-            P.I4[k] = (u32)v;
-            P.I4s[k] = c->is64 ? 0 : (u32)(((u128)v << 32) / Q);
-            v = mul_mod(v, I, Q);
-        }
-        const u64 wl = mul_mod(P.I4[3], ninv, Q);  // -I * N^-1 (I^3 = -I)
-        P.Winv_last = (u32)wl;
-        P.Winv_last_s = c->is64 ? 0 : (u32)(((u128)wl << 32) / Q);
-    }
-    P.xcd_gate_ticks = 10000;   // 100 us
-    T.xcd_gate = !c->is64 && !env_off("BCE_XCD_GATE");   // on by default (32-bit path); BCE_XCD_GATE=0: A/B runs
-    if (const char* t = std::getenv("BCE_XCD_GATE_US"); t && T.xcd_gate) P.xcd_gate_ticks = (u32)std::atoi(t) * 100u;
-    P.Q8p1_64 = Q / 8 + 1;
-    P.mu64 = (u64)((((u128)1) << 64) / Q);
-    P.c64 = (u64)((((u128)1) << 64) % Q);
-    P.Ninv64 = ninv;
-    P.Ninv64_s = (u64)(((u128)ninv << 64) / Q);
-    if (c->is64) {
-        T.tw64.resize(N);
-        u64 pw = 1;
-        for (u32 i = 0; i < N; ++i) {
-            T.tw64[bit_reverse(i, (int)c->logN)] = make_ulonglong2(pw, (u64)(((u128)pw << 64) / Q));
-            pw = mul_mod(pw, c->psi, Q);
-        }
-        if (kc.lds_error) { g_create_error = kc.lds_error; return BCE_ERR_UNSUPPORTED; }
-        P.Qd = (double)Q;
-        P.invQd = 1.0 / (double)Q;
-        P.Ninvd = (double)ninv;
-        P.Ninvd_q = (double)ninv / (double)Q;
-        T.tw64d.resize(N);
-        for (u32 i = 0; i < N; ++i) T.tw64d[i] = make_double2((double)T.tw64[i].x, (double)T.tw64[i].x / (double)Q);
-    }
-    // Lowest gadget digit folded into the key (kernels.hip, FOLD): needs a kernel that has the variant and an EXACT
-    // SignedDigitDecompose -- every centred residue d in [-(Q - Q/2), Q/2) must equal sum_l r_l B^l with dG digits
-    // r_l in [-B/2, B/2) (then the carry the reference drops after the last digit is always zero).  TOY (27-bit Q,
-    // B = 2^9, 3 digits) fails it for the top 0.1 % of residues; STD128* (B = 2^7, 4 digits) and STD192* (37-bit Q,
-    // B = 2^13, 3 digits) pass.  BCE_FOLD=0 keeps the plain key (development / parity knob).
-    {
-        const u128 Bg = (u128)1 << c->gBits;
-        u128 span = 0, pw = 1;
-        for (u32 l = 0; l < c->dG; ++l) { span += pw; pw *= Bg; }
-        const u128 hi = (Bg / 2 - 1) * span, lo = (Bg / 2) * span;       // largest / smallest (negated) representable value
-        const bool exact = (u128)(Q >> 1) <= hi + 1 && (u128)(Q - (Q >> 1)) <= lo;
-        // the folded fp64 kernels multiply a digit by a twiddle in one exact multiplication: |digit| Q <= (B / 2) Q < 2^53
-        const bool product_exact = kc.family != KernelFamily::Fp64 || (Bg / 2) * (u128)Q < ((u128)1 << 53);
-        P.fold = (exact && kc.fold_build && product_exact && !env_off("BCE_FOLD")) ? 1 : 0;
-        P.fold_ninv = (P.fold && kc.family == KernelFamily::Fp64) ? 1 : 0;
-        // forward transforms of the folded N = 1024 GINX kernel as quarter units (kernels.hip); that build is also compiled
-        // with the MAC tail of an even factor, so an odd factor keeps the whole-row + half-row bodies and the general tail.
-        // BCE_FWD_UNITS=0 keeps them everywhere (development / parity knob, same binary)
-        P.fwd_units = (P.fold && !c->is64 && c->method == BCE_GINX && P.factor_even && !env_off("BCE_FWD_UNITS")) ? 1 : 0;
-        // The stages on bits 9..4 of those transforms on the matrix pipe (kernels.hip, ntt_forward_quarter3<true>): a variant of
-        // the quarter units, so it needs everything they need (folded key, GINX, even factor, N = 1024, dG = 4) and the
-        // arithmetic conditions of fwd_mfma.hpp (gBits <= 7, four 7-bit limbs, exact limb sums, recombined word <= 13Q).
-        // Bound chain of the forward phase with this body: recombined words < 2Q + lo_max (< 4Q for STD128*), four lazy stages
-        // add < 2Q each -> MAC operands < 12Q, below the 22Q = (2 logN + 2) Q that ok1..ok5 above were checked with.
-        // Anything that fails keeps the quarter-unit body; BCE_FWD_MFMA=0 keeps it as well (development / parity knob).
-        P.fwd_mfma = 0; P.w14 = P.w14s = 0;
-        if (P.fwd_units && !env_off("BCE_FWD_MFMA")) {
-            T.fwd = build_fwd_mfma_tables(Q, N, c->gBits, c->dG, c->psi);
-            if (T.fwd.ok) { P.fwd_mfma = 1; P.w14 = T.fwd.w14; P.w14s = T.fwd.w14s; }
-            // The body is a two-workgroups-per-CU build and its byte matrices cost 6 KiB of LDS in front of the (n + 1)-word
-            // ciphertext region: where two such workgroups no longer fit a CU (n >= 896) the quarter-unit body stays, which
-            // fits up to n = 2431 (beyond that kernel_class reports one workgroup per CU)
-            if (P.fwd_mfma && 2 * kernel_class(P).lds_bytes > kLdsBytesPerCu) P.fwd_mfma = P.w14 = P.w14s = 0;
-        }
-    }
-    P.pool_stride = n + 1;
-    return BCE_OK;
-}
-
-// Second half: stream, and the tables of derive_ctx on the device
+// Stream, and the tables of derive_params on the device
 int upload_ctx(bce_ctx* c, const HostTables& T) {
     DevParams& P = c->P;
     if (hipSetDevice(c->device) != hipSuccess) { g_create_error = "hipSetDevice failed"; return BCE_ERR_HIP; }
@@ -291,20 +84,11 @@ int upload_ctx(bce_ctx* c, const HostTables& T) {
     return BCE_OK;
 }
 
-int build_ctx(u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 baseG, u32 baseR, int method, int device,
-              bce_ctx** out) {
+// validate; query the device; derive (ctx_params.cpp); copy the result into a context; upload
+int build_ctx(const Shape& s, int device, bce_ctx** out) {
     if (!out) return BCE_ERR_ARG;
     *out = nullptr;
-    if (method != BCE_AP && method != BCE_GINX) { g_create_error = "bad method (expect AP=1 or GINX=2)"; return BCE_ERR_ARG; }
-    if (N < 512 || N > 2048 || (N & (N - 1))) { g_create_error = "ring dimension N must be 512, 1024 or 2048"; return BCE_ERR_UNSUPPORTED; }
-    if ((q & (q - 1)) || q > 2 * (u64)N || q < 8) { g_create_error = "LWE modulus q must be a power of two dividing 2N"; return BCE_ERR_ARG; }
-    if (!is_prime_u64(Q) || (Q - 1) % (2ull * N)) { g_create_error = "Q must be a prime = 1 mod 2N"; return BCE_ERR_ARG; }
-    if (Q >= (1ull << 40)) { g_create_error = "ring modulus Q must be below 2^40"; return BCE_ERR_UNSUPPORTED; }
-    if (baseG < 2 || (baseG & (baseG - 1))) { g_create_error = "gadget base baseG must be a power of two, at least 2"; return BCE_ERR_ARG; }
-    // digit_count divides by log(base), and a base of 0 gives a loop of no digits that "succeeds"
-    if (n == 0) { g_create_error = "LWE dimension n must be at least 1"; return BCE_ERR_ARG; }
-    if (baseKS < 2) { g_create_error = "key-switching base baseKS must be at least 2"; return BCE_ERR_ARG; }
-    if (method == BCE_AP && baseR < 2) { g_create_error = "refreshing base baseR must be at least 2 (AP)"; return BCE_ERR_ARG; }
+    if (const CtxStatus st = validate_shape(s); st.code != BCE_OK) { g_create_error = st.message; return st.code; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         g_create_error = "no HIP device visible: the engine has no CPU fallback";
@@ -313,15 +97,20 @@ int build_ctx(u32 n, u32 N, u64 q, u64 Q, u64 qKS, u32 baseKS, u32 baseG, u32 ba
     if (device < 0 || device >= ndev) { g_create_error = "bad device ordinal"; return BCE_ERR_ARG; }
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
+    const CtxParams cp = derive_params(s, read_ctx_knobs(), (u32)cus);
+    if (cp.status.code != BCE_OK) { g_create_error = cp.status.message; return cp.status.code; }
 
     // partially built contexts are released through bce_ctx_destroy (frees whatever was allocated)
     struct CtxDeleter { void operator()(bce_ctx* p) const { bce_ctx_destroy(p); } };
     std::unique_ptr<bce_ctx, CtxDeleter> c(new bce_ctx);
     { std::lock_guard<std::mutex> lk(g_live_mu); g_live.insert(c.get()); }
-    HostTables T;
-    int rc = derive_ctx(c.get(), n, N, q, Q, qKS, baseKS, baseG, baseR, method, device, (u32)cus, T);
-    if (rc == BCE_OK) rc = upload_ctx(c.get(), T);
-    if (rc != BCE_OK) return rc;
+    const DevParams& P = c->P = cp.P;
+    c->n = P.n; c->N = P.N; c->logN = P.logN; c->q = s.q; c->Q = s.Q; c->qKS = P.qKS; c->psi = cp.psi;
+    c->baseKS = P.baseKS; c->dKS = P.dKS; c->baseG = s.baseG; c->gBits = P.gBits; c->dG = P.dG; c->baseR = P.baseR; c->dR = P.dR;
+    c->method = s.method; c->device = device;
+    c->is64 = P.is64 != 0;
+    c->wbytes = c->is64 ? 8 : 4;
+    if (const int rc = upload_ctx(c.get(), cp.T)) return rc;
     *out = c.release();
     return BCE_OK;
 }
@@ -698,15 +487,14 @@ int launch_bootstraps(bce_ctx* c, const bce_gate_desc* dd, u32 n, u32 instances,
 extern "C" {
 
 int bce_ctx_create(int paramset, int method, int device, bce_ctx** out) {
-    if (paramset < 0 || paramset > BCE_STD256_OPT) { g_create_error = "unknown parameter set"; if (out) *out = nullptr; return BCE_ERR_ARG; }
-    const ParamRow& r = kParamTable[paramset];
-    const u64 Q = previous_prime(first_prime(r.bits, r.cyclo), r.cyclo);
-    return build_ctx(r.n, r.cyclo / 2, r.q, Q, r.qKS, r.baseKS, r.baseG, r.baseR, method, device, out);
+    Shape s;
+    if (!tabulated_shape(paramset, method, s)) { g_create_error = "unknown parameter set"; if (out) *out = nullptr; return BCE_ERR_ARG; }
+    return build_ctx(s, device, out);
 }
 
 int bce_ctx_create_custom(uint32_t n, uint32_t N, uint64_t q, uint64_t Q, uint64_t qKS, uint32_t baseKS, uint32_t baseG,
                           uint32_t baseR, int method, int device, bce_ctx** out) {
-    return build_ctx(n, N, q, Q, qKS, baseKS, baseG, baseR, method, device, out);
+    return build_ctx(Shape{n, N, q, Q, qKS, baseKS, baseG, baseR, method}, device, out);
 }
 
 int bce_rccl_shutdown(bce_ctx* c);   // rccl_xchg.cpp
@@ -1083,7 +871,7 @@ int bce_timing_get(bce_ctx* c, bce_timing* out) {
     return rc;
 }
 
-uint32_t bce_forward_transforms_per_step(const bce_ctx* c) { return c ? 2 * c->dG - (c->P.fold ? 2 : 0) : 0; }
+uint32_t bce_forward_transforms_per_step(const bce_ctx* c) { return c ? forward_transforms_per_step(c->P) : 0; }
 uint32_t bce_forward_units(const bce_ctx* c) { return c ? c->P.fwd_units : 0; }
 uint32_t bce_forward_mfma(const bce_ctx* c) { return c ? c->P.fwd_mfma : 0; }
 uint32_t bce_lazy_arithmetic(const bce_ctx* c) { return c ? c->P.lazy : 0; }
@@ -1102,21 +890,34 @@ int bce_forward_mfma_tables(uint64_t Q, uint32_t N, uint32_t gBits, uint32_t dG,
 
 int bce_launch_capacity(const bce_ctx* c, uint32_t* lone, uint32_t* full) {
     if (!c || !lone || !full) return BCE_ERR_ARG;
-    const KernelClass k = kernel_class(c->P);
-    *lone = c->P.cu_count * k.wg_per_cu_lone;
-    *full = c->P.cu_count * k.wg_per_cu_full;
+    launch_capacity(c->P, lone, full);
     return BCE_OK;
+}
+
+static int report_derived(const CtxParams& cp, uint64_t* out, const char** message) {
+    if (message) *message = cp.status.message;
+    if (!out) return BCE_ERR_ARG;
+    std::fill(out, out + BCE_D_COUNT, 0);
+    if (cp.status.code != BCE_OK) return cp.status.code;
+    params_report(cp, out);
+    out[BCE_D_dag_lds_bytes] = cp.P.is64 ? 0 : bootstrap_dag_lds_bytes(cp.P, 4);
+    return BCE_OK;
+}
+
+int bce_params_derive(uint32_t n, uint32_t N, uint64_t q, uint64_t Q, uint64_t qKS, uint32_t baseKS, uint32_t baseG, uint32_t baseR,
+                      int method, uint32_t cu_count, uint64_t out[BCE_D_COUNT], const char** message) {
+    return report_derived(derive_params(Shape{n, N, q, Q, qKS, baseKS, baseG, baseR, method}, read_ctx_knobs(), cu_count), out, message);
+}
+
+int bce_params_derive_set(int paramset, int method, uint32_t cu_count, uint64_t out[BCE_D_COUNT], const char** message) {
+    Shape s;
+    if (!tabulated_shape(paramset, method, s)) { if (message) *message = "unknown parameter set"; return BCE_ERR_ARG; }
+    return report_derived(derive_params(s, read_ctx_knobs(), cu_count), out, message);
 }
 
 int bce_bytes_per_bootstrap_parts(const bce_ctx* c, uint64_t out[3]) {
     if (!c || !out) return BCE_ERR_ARG;
-    // w_bsk*[RGSWs touched * (2dG)*2*N] + w_ks*[N*dKS*(n+1)] + w_ct*[3(n+1)] at this build's widths.
-    // GINX touches 2 RGSW ciphertexts per LWE coefficient, AP one per non-zero base-baseR digit
-    // (dR * (baseR-1)/baseR on average).
-    const double rgsws = c->method == BCE_AP ? (double)c->n * c->dR * (c->baseR - 1) / c->baseR : 2.0 * c->n;
-    out[0] = (u64)((double)c->wbytes * rgsws * (2 * c->dG) * 2 * c->N);
-    out[1] = (c->P.ksk_u16 ? 2ull : 4ull) * c->N * c->dKS * (c->n + 1);
-    out[2] = 4ull * 3 * (c->n + 1);
+    bytes_per_bootstrap_parts(c->P, out);
     return BCE_OK;
 }
 

@@ -1,10 +1,10 @@
 // engine_dag.cpp -- dependency-driven evaluation (bce_dag; include/bce_gpu.h, "the hot path, dependency-driven"): the task
 // list analysed on the host (dag_build.cpp), resident on the device, and run by one persistent launch (dag_sched.hpp).
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <memory>
 
+#include "ctx_params.hpp"
 #include "dag_build.hpp"
 #include "engine_internal.hpp"
 
@@ -73,6 +73,20 @@ int bce_dag_set_limits(bce_ctx* c, int workgroups_per_cu, int placement, uint32_
 int bce_dag_last_run(bce_ctx* c, uint64_t out[7]) {
     if (!c || !out) return BCE_ERR_ARG;
     for (int i = 0; i < 7; ++i) out[i] = c->dag_last[i];
+    return BCE_OK;
+}
+
+int bce_dag_launch_choice(const uint64_t derived[BCE_D_COUNT], int workgroups_per_cu, int placement, uint32_t lazy_us, uint32_t stall_ms,
+                          uint32_t depth, uint64_t items, uint64_t out[BCE_L_COUNT]) {
+    if (!derived || !out) return BCE_ERR_ARG;
+    DevParams P{};
+    P.cu_count = (u32)derived[BCE_D_cu_count];
+    P.is64 = (u32)derived[BCE_D_is64];
+    const DagLaunchChoice L = dag_launch_choice(P, (u32)derived[BCE_D_wg_per_cu_full], (size_t)derived[BCE_D_dag_lds_bytes],
+                                                DagLimits{workgroups_per_cu, placement, lazy_us, stall_ms}, read_dag_knobs(), depth, items);
+    out[BCE_L_wps] = (u64)L.wps; out[BCE_L_grid] = L.grid; out[BCE_L_policy] = L.policy; out[BCE_L_gate_ticks] = L.gate_ticks;
+    out[BCE_L_gate_backlog] = L.gate_backlog; out[BCE_L_lazy_ticks] = L.lazy_ticks; out[BCE_L_stall_ticks] = L.stall_ticks;
+    out[BCE_L_rearm_only] = L.rearm_only ? 1 : 0;
     return BCE_OK;
 }
 
@@ -165,39 +179,10 @@ int bce_dag_run(bce_ctx* c, bce_dag* g, uint32_t instances, uint32_t slot_stride
         D.chk_of_task = g->d_chk_of_task.get(); D.expect = static_cast<const uint8_t*>(g->expect.device()); D.n_checks = g->n_checks; D.repair = (u32)g->chk_repair;
         D.s8 = c->d_s8.get(); D.report = c->d_check(); D.log = c->d_check_log();
     }
-    D.lazy_ticks = c->dag_lazy_us * 100u;                     // s_memrealtime: 100 MHz
-    D.stall_ticks = c->dag_stall_ms * 100000u;
-    D.policy = c->dag_placement ? 1u : 0u;
-    D.gate_ticks = 15000;        // 150 us: the finish times of bootstraps that started together spread less than that
-    D.gate_backlog = 8;          // (64 / 16 / 4 / 1: AES K = 8 at 150 / 153 / 154 / 155 k; with the classes below 157 k, profiles/r03_dataflow_vs_steps.jsonl)
-    if (const char* e = std::getenv("BCE_DAG_GATE_US")) D.gate_ticks = (u32)std::atoi(e) * 100u;
-    if (const char* e = std::getenv("BCE_DAG_GATE_BACKLOG")) D.gate_backlog = (u32)std::atoi(e);
-    // one or two workgroups per CU: two run 512 bootstraps per ~3.1 ms, one runs 256 per ~1.9 ms -- with less work per
-    // dependency level than the CUs can hold alone, the shorter bootstrap wins
-    int wps = c->dag_wg_per_cu == 1 ? 2 : 4;
-    if (c->dag_wg_per_cu == 0) {
-        // lower bound of the run under either residency, in units of one bootstrap with a CU to itself: the DAG's longest
-        // chain against the work over the chip's rate.  Two workgroups per CU take 1.6 x as long per bootstrap (3.1 vs
-        // 1.93 ms) and deliver 1.26 x the rate (165 vs 131 k/s); the cheaper bound wins (AES-expanded: K <= 2 one per CU,
-        // K >= 4 two; md5 K = 16 and adder_64 K = 64 one.  Against the earlier rule "work per level <= 3/4 of the CUs":
-        // adder_64 K = 64 97.9 -> 117.9 k/s, AES K = 2 115.7 -> 109.6 k, md5 K = 16 114.0 -> 110.1 k,
-        // profiles/r03_dataflow_vs_steps.jsonl)
-        const double D = (double)std::max<u32>(1, h.depth), W = (double)items, cus = (double)std::max<u32>(1, c->P.cu_count);
-        const double t1 = std::max(D, W / cus), t2 = std::max(1.6 * D, W / (1.26 * cus));
-        wps = t1 <= t2 ? 2 : 4;
-    }
-    if (const char* e = std::getenv("BCE_DAG_WPS")) { if (e[0] == '2') wps = 2; else if (e[0] == '4') wps = 4; }
-    if (kernel_class(c->P).wg_per_cu_full == 1) wps = 2;   // a CU's LDS holds one workgroup (the config-5 kernel; the split-transform kernel at n >= 2432)
-    // the persistent kernel's own LDS (mailbox in front of the layout): where two such workgroups do not fit a CU although two
-    // of the per-frontier kernel do (n = 888..895 on the matrix-pipe build, 2424..2431 on the quarter-unit build), one per CU
-    if (wps == 4 && !c->P.is64 && 2 * bootstrap_dag_lds_bytes(c->P, 4) > kLdsBytesPerCu) wps = 2;
-    if (const char* e = std::getenv("BCE_DAG_PLACE")) D.policy = e[0] == '0' ? 0u : 1u;
-    const char* dbg = std::getenv("BCE_DAG_DEBUG");   // development: 'r' = re-arm only, 'd' = dry run (no bootstraps)
-    if (dbg && dbg[0] == 'd') D.policy |= 2u;
-    // the XCD start gate pays where two workgroups per CU share the L2 in the saturated regime (development knob BCE_DAG_GATE=0 / 1)
-    { const char* e = std::getenv("BCE_DAG_GATE"); if (e ? e[0] != '0' : wps == 4) D.policy |= 4u; }
-    { const char* e = std::getenv("BCE_DAG_TICKETS"); if (e && e[0] == '1') D.policy |= 8u; }   // development: round 3's claim rule
-    const u32 grid = c->P.cu_count * (wps == 2 ? 1u : 2u);
+    // one or two workgroups per CU, the grid, the policy bits and the gate constants (ctx_params.cpp)
+    const DagLaunchChoice L = dag_launch_choice(c->P, kernel_class(c->P).wg_per_cu_full, c->P.is64 ? 0 : bootstrap_dag_lds_bytes(c->P, 4),
+                                                DagLimits{c->dag_wg_per_cu, c->dag_placement, c->dag_lazy_us, c->dag_stall_ms}, read_dag_knobs(), h.depth, items);
+    D.lazy_ticks = L.lazy_ticks; D.stall_ticks = L.stall_ticks; D.policy = L.policy; D.gate_ticks = L.gate_ticks; D.gate_backlog = L.gate_backlog;
     // parameter blocks reach the device in stream order (an earlier run may still be reading the previous ones) from
     // pinned staging entries that stay untouched until the next synchronisation
     const int slot = c->dag_pending++;
@@ -209,11 +194,11 @@ int bce_dag_run(bce_ctx* c, bce_dag* g, uint32_t instances, uint32_t slot_stride
     HIP_TRY(c, launch_dag_rearm(D, c->stream));
     EventPair e0 = get_events(c, BCE_BR_DAG);
     hipEventRecord(e0.a, c->stream);
-    if (!(dbg && dbg[0] == 'r')) HIP_TRY(c, launch_bootstrap_dag(c->P, c->d_P.get(), g->d_params.get(), wps, grid, c->stream));
+    if (!L.rearm_only) HIP_TRY(c, launch_bootstrap_dag(c->P, c->d_P.get(), g->d_params.get(), L.wps, L.grid, c->stream));
     hipEventRecord(e0.b, c->stream);
     c->pending.push_back(e0);
     c->dag_expected[slot] = items;
-    c->dag_wps_used[slot] = wps;
+    c->dag_wps_used[slot] = L.wps;
     HIP_TRY(c, hipMemcpyAsync(&c->h_dag_status.get()[slot], g->d_ctl.get() + kDagAbort, sizeof(bce_ctx::DagStatus), hipMemcpyDeviceToHost, c->stream));
     c->timing.br_launches[BCE_BR_DAG] += 1;
     c->timing.br_bootstraps[BCE_BR_DAG] += items;
