@@ -215,6 +215,15 @@ uint32_t bce_circuit_resolve_mode(uint32_t inputs);
 int bce_circuit_dataflow_plan(const bce_circuit*, bce_gate_desc* tasks, uint8_t* prio, uint32_t cap, uint32_t* n_tasks);
 /* K independent input sets evaluated in lock-step (call before SetInput) */
 int bce_circuit_set_instances(bce_circuit*, uint32_t k);
+/* Per-instance key sets (bce_gpu.h, "key sets"): instance k of the circuit belongs to the client whose keys are set ids[k] of
+ * the engine.  Call before SetInput with count == the instances (count 0 returns to the selected set; BCE_ERR_ARG otherwise,
+ * BCE_ERR_STATE after SetInput).  SetInput(instance k) then encrypts under set ids[k] (the selection is restored afterwards),
+ * Clock() runs the bootstrap-depth step schedule keyed (one launch per step for all clients; as one hipGraph with
+ * bce_circuit_set_graph), and the outputs of instance k are decrypted under set ids[k] (one gather, bce_decrypt_bits_keyed).
+ * BCE_ERR_UNSUPPORTED, with a message that names the combination: together with bce_circuit_set_dataflow,
+ * bce_circuit_set_verify, bce_circuit_set_device_verify or gate sharding (from either setter, and at SetInput), and at Clock()
+ * when the chosen options would not run the step schedule (plaintext pass, unbatched gates, relevel off). */
+int bce_circuit_set_instance_keysets(bce_circuit*, const uint32_t* ids, uint32_t count);
 /* Circuit::SetInput, src/circuit.cpp:455-530: bits = concatenation of the input buses,
  * LSB first (Inputs[k][bit]); widths[k] = number of bits of bus k */
 int bce_circuit_set_input(bce_circuit*, uint32_t instance, const uint32_t* widths, uint32_t n_buses,

@@ -175,6 +175,29 @@ int bce_export_sk(const bce_ctx*, int32_t* s, int32_t* z);
 int bce_export_bsk(bce_ctx*, uint64_t* bsk);
 int bce_export_ksk(bce_ctx*, uint32_t* ksk);
 
+/* ---- key sets ---------------------------------------------------------- */
+/* A server evaluates circuits for many clients, each with a bootstrapping and key-switching key of its own.  A context
+ * holds up to BCE_MAX_KEYSETS key sets: the secrets, the two evaluation keys and the device copy of the LWE secret of one
+ * client.  Everything derived from the parameters alone (tables, kernel choice, pool) stays per context.  Set 0 exists from
+ * creation and is what a caller that never touches this section uses.
+ *
+ * THE RULE: a call that takes no key-set map acts on the set that is SELECTED when it is called.  That covers bce_keygen,
+ * the three imports and every export, bce_bsk_words / bce_ksk_words, bce_encrypt_bits (its BOOTSTRAPPED refresh included),
+ * bce_decrypt_bits, bce_check_slots, bce_eval_gates[_strided], bce_debug_*, bce_dag_run, and bce_plan_run[_step] of a plan
+ * created without a map (a captured plan is captured again when the selection changed).  A selected set without keys gives
+ * BCE_ERR_NO_KEYS.
+ *
+ * bce_keyset_add    creates an empty set; *id = the lowest free id (>= 1).  BCE_ERR_ARG at the limit.
+ * bce_keyset_select chooses the selected set (default 0).  BCE_ERR_ARG for an id that does not exist.
+ * bce_keyset_drop   synchronises, then frees the set.  BCE_ERR_ARG for set 0, the selected set and an id that does not
+ *                   exist; BCE_ERR_STATE while a live plan was created with a map that names the set. */
+enum { BCE_MAX_KEYSETS = 256 };
+int bce_keyset_add(bce_ctx*, uint32_t* id);
+int bce_keyset_select(bce_ctx*, uint32_t id);
+int bce_keyset_drop(bce_ctx*, uint32_t id);
+uint32_t bce_keyset_count(const bce_ctx*);
+uint32_t bce_keyset_selected(const bce_ctx*);
+
 /* ---- device LWE pool --------------------------------------------------- */
 /* LWECiphertext objects (src/wire.h:46, src/gate.h:75-78) become slots. */
 int bce_pool_reserve(bce_ctx*, uint32_t slots);
@@ -202,6 +225,10 @@ int bce_encrypt_bits(bce_ctx*, const uint8_t* bits, const uint32_t* slots, uint3
 int bce_set_encrypt_seed(bce_ctx*, const uint8_t seed[32]);
 /* cc.Decrypt(sk, ct, &res): src/circuit.cpp:800, src/gate.cpp:72,97,115,... (res in 0..3) */
 int bce_decrypt_bits(bce_ctx*, const uint32_t* slots, uint32_t count, uint8_t* bits);
+/* The same with a key-set map per SLOT: slot i is decrypted under set keyset_of_slot[i] ("key sets" above), with the one
+ * device gather of the unkeyed call.  Errors as bce_eval_gates_keyed; NULL is bce_decrypt_bits. */
+int bce_decrypt_bits_keyed(bce_ctx*, const uint32_t* slots, uint32_t count, const uint32_t* keyset_of_slot /*[count]*/,
+                           uint8_t* bits);
 
 /* ---- the hot path ------------------------------------------------------ */
 /* Batched EvalBinGate / EvalNOT over one ready frontier:
@@ -215,6 +242,12 @@ int bce_eval_gates(bce_ctx*, uint32_t n_desc, const bce_gate_desc* descs);
  * the reference's sequential numTestLoops loop, src/test_aes.cpp:179-182). */
 int bce_eval_gates_strided(bce_ctx*, uint32_t n_desc, const bce_gate_desc* descs, uint32_t instances,
                            uint32_t slot_stride);
+/* The same with a key-set map: instance k runs entirely under key set keyset_of_instance[k] (LWE preparation, blind
+ * rotation and both tails read that set's keys); several instances may name one set.  One launch, as without a map: the map
+ * travels with the descriptors in the same upload.  BCE_ERR_ARG for an id that does not exist, BCE_ERR_NO_KEYS for a named
+ * set without keys.  keyset_of_instance == NULL is bce_eval_gates_strided (the selected set). */
+int bce_eval_gates_keyed(bce_ctx*, uint32_t n_desc, const bce_gate_desc* descs, uint32_t instances, uint32_t slot_stride,
+                         const uint32_t* keyset_of_instance /*[instances]*/);
 int bce_synchronize(bce_ctx*);
 
 /* ---- the hot path, a whole step schedule at once ----------------------------------------------------------
@@ -231,6 +264,12 @@ int bce_synchronize(bce_ctx*);
 typedef struct bce_plan bce_plan;
 int bce_plan_create(bce_ctx*, uint32_t n_steps, const uint32_t* step_sizes, const bce_gate_desc* descs,
                     uint32_t instances, uint32_t slot_stride, uint32_t slot_base, bce_plan** out);
+/* bce_plan_create with a key-set map fixed at creation (copied; resident next to the descriptors): bce_plan_run_step and
+ * bce_plan_run (the hipGraph replay) then run instance k under set keyset_of_instance[k], whatever is selected.  Errors as
+ * bce_eval_gates_keyed; NULL is bce_plan_create.  bce_plan_set_checks on such a plan: BCE_ERR_UNSUPPORTED. */
+int bce_plan_create_keyed(bce_ctx*, uint32_t n_steps, const uint32_t* step_sizes, const bce_gate_desc* descs,
+                          uint32_t instances, uint32_t slot_stride, uint32_t slot_base,
+                          const uint32_t* keyset_of_instance /*[instances]*/, bce_plan** out);
 int bce_plan_run_step(bce_ctx*, bce_plan*, uint32_t step);
 int bce_plan_run(bce_ctx*, bce_plan*);
 void bce_plan_destroy(bce_ctx*, bce_plan*);

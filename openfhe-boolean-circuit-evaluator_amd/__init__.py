@@ -97,6 +97,8 @@ ENGINE_SYMBOLS = [
     "bce_params_derive", "bce_params_derive_set", "bce_dag_launch_choice",
     "bce_plan_create", "bce_plan_run_step", "bce_plan_run", "bce_plan_destroy",
     "bce_check_slots", "bce_plan_set_checks", "bce_plan_set_expected", "bce_check_reset", "bce_check_get",
+    "bce_keyset_add", "bce_keyset_select", "bce_keyset_drop", "bce_keyset_count", "bce_keyset_selected",
+    "bce_eval_gates_keyed", "bce_plan_create_keyed", "bce_decrypt_bits_keyed",
 ]
 
 _lib = None
@@ -162,6 +164,15 @@ def lib():
     L.bce_decrypt_bits.argtypes = [vp, vp, u32, vp]
     L.bce_eval_gates.argtypes = [vp, u32, vp]
     L.bce_eval_gates_strided.argtypes = [vp, u32, vp, u32, u32]
+    L.bce_eval_gates_keyed.argtypes = [vp, u32, vp, u32, u32, vp]
+    L.bce_decrypt_bits_keyed.argtypes = [vp, vp, u32, vp, vp]
+    L.bce_keyset_add.argtypes = [vp, C.POINTER(u32)]
+    L.bce_keyset_select.argtypes = [vp, u32]
+    L.bce_keyset_drop.argtypes = [vp, u32]
+    L.bce_keyset_count.argtypes = [vp]
+    L.bce_keyset_count.restype = u32
+    L.bce_keyset_selected.argtypes = [vp]
+    L.bce_keyset_selected.restype = u32
     L.bce_synchronize.argtypes = [vp]
     L.bce_timing_reset.argtypes = [vp]
     L.bce_timing_get.argtypes = [vp, C.POINTER(Timing)]
@@ -202,6 +213,7 @@ def lib():
     L.bce_dag_set_checks.argtypes = [vp, vp, u32, vp, i32]
     L.bce_dag_set_expected.argtypes = [vp, vp, u32, vp]
     L.bce_plan_create.argtypes = [vp, u32, vp, vp, u32, u32, u32, C.POINTER(vp)]
+    L.bce_plan_create_keyed.argtypes = [vp, u32, vp, vp, u32, u32, u32, vp, C.POINTER(vp)]
     L.bce_plan_run_step.argtypes = [vp, vp, u32]
     L.bce_plan_run.argtypes = [vp, vp]
     L.bce_plan_destroy.argtypes = [vp, vp]
@@ -316,6 +328,25 @@ class BinFHEContext:
 
     BTKeyGen = KeyGen
 
+    # --- key sets: one per client; a call without a key-set map acts on the selected set (include/bce_gpu.h) ---
+    def keyset_add(self):
+        """a new, empty key set; returns its id (the lowest free one, >= 1)"""
+        out = C.c_uint32()
+        self._ck(self._L.bce_keyset_add(self.h, C.byref(out)))
+        return int(out.value)
+
+    def keyset_select(self, keyset):
+        self._ck(self._L.bce_keyset_select(self.h, int(keyset)))
+
+    def keyset_drop(self, keyset):
+        self._ck(self._L.bce_keyset_drop(self.h, int(keyset)))
+
+    def keyset_count(self):
+        return int(self._L.bce_keyset_count(self.h))
+
+    def keyset_selected(self):
+        return int(self._L.bce_keyset_selected(self.h))
+
     def import_keys(self, s, z, bsk, ksk):
         s = np.ascontiguousarray(s, dtype=np.int32)
         z = np.ascontiguousarray(z, dtype=np.int32)
@@ -388,16 +419,29 @@ class BinFHEContext:
         assert bits.size == slots.size
         self._ck(self._L.bce_encrypt_bits(self.h, _p(bits), _p(slots), slots.size, int(enc_index_base), mode))
 
-    def Decrypt(self, slots):
+    def Decrypt(self, slots, keysets=None):
+        """keysets: the key set of every slot (bce_decrypt_bits_keyed), or None: all under the selected set"""
         slots = np.ascontiguousarray(slots, dtype=np.uint32)
         out = np.zeros(slots.size, dtype=np.uint8)
-        self._ck(self._L.bce_decrypt_bits(self.h, _p(slots), slots.size, _p(out)))
+        if keysets is not None:
+            ids = np.ascontiguousarray(keysets, dtype=np.uint32)
+            if ids.size != slots.size:
+                raise ValueError("keysets names %d slots, the call has %d" % (ids.size, slots.size))
+            self._ck(self._L.bce_decrypt_bits_keyed(self.h, _p(slots), slots.size, _p(ids), _p(out)))
+        else:
+            self._ck(self._L.bce_decrypt_bits(self.h, _p(slots), slots.size, _p(out)))
         return out
 
     # --- the hot path: batched EvalBinGate / EvalNOT (src/gate.cpp:112,133,172,198-202) ---
-    def EvalGates(self, descs, instances=1, slot_stride=0):
+    def EvalGates(self, descs, instances=1, slot_stride=0, keysets=None):
+        """keysets: the key set of every instance (bce_eval_gates_keyed), or None: all run under the selected set"""
         arr = descs if isinstance(descs, C.Array) else make_descs(descs)
-        if instances == 1:
+        if keysets is not None:
+            ids = np.ascontiguousarray(keysets, dtype=np.uint32)
+            if ids.size != int(instances):
+                raise ValueError("keysets names %d instances, the call has %d" % (ids.size, int(instances)))
+            self._ck(self._L.bce_eval_gates_keyed(self.h, len(arr), arr, int(instances), int(slot_stride), _p(ids)))
+        elif instances == 1:
             self._ck(self._L.bce_eval_gates(self.h, len(arr), arr))
         else:
             self._ck(self._L.bce_eval_gates_strided(self.h, len(arr), arr, instances, slot_stride))
@@ -469,14 +513,21 @@ class BinFHEContext:
         return d
 
     # --- a whole step schedule resident on the device (bce_plan_*) ---
-    def plan_create(self, steps, instances=1, slot_stride=0, slot_base=0):
-        """steps: list of frontiers, each a list of (op, in0, in1, out[, neg0, neg1]); returns an opaque handle"""
+    def plan_create(self, steps, instances=1, slot_stride=0, slot_base=0, keysets=None):
+        """steps: list of frontiers, each a list of (op, in0, in1, out[, neg0, neg1]); returns an opaque handle.
+        keysets: the key set of every instance, fixed for the plan's life (bce_plan_create_keyed)"""
         flat = [t for st in steps for t in st]
         arr = (GateDesc * max(1, len(flat)))()
         for i, t in enumerate(flat):
             arr[i] = GateDesc(*(tuple(t) + (0, 0))[:6])
         sizes = (C.c_uint32 * max(1, len(steps)))(*[len(st) for st in steps])
         h = C.c_void_p()
+        if keysets is not None:
+            ids = np.ascontiguousarray(keysets, dtype=np.uint32)
+            if ids.size != int(instances):
+                raise ValueError("keysets names %d instances, the plan has %d" % (ids.size, int(instances)))
+            self._ck(self._L.bce_plan_create_keyed(self.h, len(steps), sizes, arr, int(instances), int(slot_stride), int(slot_base), _p(ids), C.byref(h)))
+            return h
         self._ck(self._L.bce_plan_create(self.h, len(steps), sizes, arr, int(instances), int(slot_stride), int(slot_base), C.byref(h)))
         return h
 
@@ -658,7 +709,7 @@ CIRCUIT_SYMBOLS = [
     "bce_circuit_read_bristol", "bce_circuit_get_info", "bce_circuit_reset", "bce_circuit_rearm", "bce_circuit_set_plaintext",
     "bce_circuit_set_encrypted", "bce_circuit_set_verify", "bce_circuit_get_flags", "bce_circuit_set_batched",
     "bce_circuit_set_encrypt_mode", "bce_circuit_get_encrypt_mode", "bce_circuit_plan_hash", "bce_circuit_set_shard_locality", "bce_circuit_set_xor_fast", "bce_circuit_set_xor_shared", "bce_circuit_xor_shared_active", "bce_circuit_set_xor_single", "bce_circuit_get_xor_single", "bce_circuit_set_relevel", "bce_circuit_get_relevel", "bce_circuit_set_dataflow", "bce_circuit_set_dataflow_shared", "bce_circuit_dataflow_active", "bce_circuit_set_graph", "bce_circuit_graph_active", "bce_circuit_set_device_verify", "bce_circuit_device_verify_active", "bce_circuit_get_check_report", "bce_circuit_resolve_mode", "bce_circuit_dataflow_plan", "bce_circuit_set_balance", "bce_circuit_relevel_steps", "bce_circuit_relevel_descs", "bce_circuit_relevel_publications", "bce_circuit_check_relevel", "bce_circuit_set_instances", "bce_circuit_set_input", "bce_circuit_clock",
-    "bce_circuit_get_output", "bce_circuit_get_buses", "bce_circuit_get_counts", "bce_circuit_get_stats", "bce_circuit_dump",
+    "bce_circuit_set_instance_keysets", "bce_circuit_get_output", "bce_circuit_get_buses", "bce_circuit_get_counts", "bce_circuit_get_stats", "bce_circuit_dump",
     "bce_circuit_set_exchange", "bce_circuit_enable_rccl", "bce_circuit_exchange_capacity", "bce_assemble_bristol", "bce_pool_gather",
     "bce_pool_scatter",
 ]
@@ -686,6 +737,7 @@ def _bind_circuit():
         getattr(L, "bce_circuit_" + name).argtypes = [vp, i32]
     L.bce_circuit_get_flags.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.bce_circuit_set_instances.argtypes = [vp, u32]
+    L.bce_circuit_set_instance_keysets.argtypes = [vp, vp, u32]
     L.bce_circuit_set_balance.argtypes = [vp, i32, u32, u32]
     L.bce_circuit_set_dataflow.argtypes = [vp, i32]
     L.bce_circuit_set_dataflow_shared.argtypes = [vp, i32]
@@ -933,6 +985,12 @@ class Circuit:
 
     def setInstances(self, k):
         self._ck(self._L.bce_circuit_set_instances(self.h, int(k)))
+
+    def setInstanceKeys(self, keysets):
+        """instance k is encrypted, evaluated and decrypted under key set keysets[k] of the engine (one id per instance, before
+        SetInput; an empty list returns to the selected set).  Not with setDataflow, setVerify, setDeviceVerify or gate sharding."""
+        ids = np.ascontiguousarray(keysets, dtype=np.uint32)
+        self._ck(self._L.bce_circuit_set_instance_keysets(self.h, _p(ids) if ids.size else None, ids.size))
 
     def setBalance(self, on, lone=0, full=0):
         """bootstrap-depth schedule filled by slack up to the engine's launch staircase (default on); before SetInput"""

@@ -410,13 +410,38 @@ RunMode Circuit::runMode() const {
     return resolve_mode(m);
 }
 
+void Circuit::refuseWithKeys(const char* who) const {
+    if (!instance_keys_.empty()) throw Unsupported(std::string(who) + " together with setInstanceKeys: per-instance key sets run the step schedule only");
+}
+void Circuit::keysCombinationSupported(const char* who) const {
+    if (instance_keys_.empty()) return;
+    const char* with = opt_.dataflow ? "setDataflow" : opt_.verify ? "setVerify" : opt_.device_verify ? "setDeviceVerify" : gateSharded() ? "gate sharding" : nullptr;
+    if (with) throw Unsupported(std::string(who) + ": setInstanceKeys together with " + with + " is not supported");
+}
+
+void Circuit::setInstanceKeys(const std::vector<uint32_t>& ids) {
+    if (inputs_set_) throw std::logic_error("setInstanceKeys: call it before SetInput");
+    if (!ids.empty() && ids.size() != instances_) throw std::invalid_argument("setInstanceKeys: " + std::to_string(ids.size()) + " ids for " + std::to_string(instances_) + " instances");
+    const std::vector<uint32_t> was = std::move(instance_keys_);
+    instance_keys_ = ids;
+    try {
+        keysCombinationSupported("setInstanceKeys");
+    } catch (...) {
+        instance_keys_ = was;
+        throw;
+    }
+    dropPlan();
+}
+
 void Circuit::setVerify(bool b) {
+    if (b) refuseWithKeys("setVerify");
     setModeFlag(opt_.verify, b, "setVerify");   // one of the things xorMode() reads
     if (b) { setPlaintext(true); setEncrypted(true); }
 }
 
 void Circuit::setInstances(unsigned k) {
     if (k == 0) throw std::invalid_argument("setInstances: need at least one instance");
+    if (k != instances_) instance_keys_.clear();   // one id per instance: the list of another K no longer fits
     instances_ = k;
     plain_.assign(instances_, std::vector<uint8_t>(wire_names_.size(), 0));
     circuitOut.assign(instances_, std::vector<uint8_t>(n_output_bits.empty() ? 0 : n_output_bits[0], 0));
@@ -433,6 +458,7 @@ void Circuit::SetInput(const Inputs& input, bool verbose) { SetInput(0, input, v
 
 void Circuit::SetInput(unsigned inst, const Inputs& input, bool verbose) {
     if (inst >= instances_) throw std::out_of_range("SetInput: instance out of range");
+    keysCombinationSupported("SetInput");
     size_t total_bits = 0;
     for (size_t k = 0; k < input.size(); ++k) {
         if (verbose) std::cout << "setting input " << k << " size " << input[k].size() << std::endl;
@@ -463,7 +489,16 @@ void Circuit::SetInput(unsigned inst, const Inputs& input, bool verbose) {
         ck(bce_pool_reserve(cc, instances_ * stride_), "SetInput(pool)");
         // stream index = (evaluation epoch, instance, input position): every rank draws the same ciphertexts
         uint64_t base = ((epoch_ & 0xFFFFFull) << 44) | ((uint64_t)inst << 24);
-        ck(bce_encrypt_bits(cc, bits.data(), slots.data(), (uint32_t)slots.size(), base, encrypt_mode_), "SetInput(Encrypt)");
+        if (instance_keys_.empty()) {
+            ck(bce_encrypt_bits(cc, bits.data(), slots.data(), (uint32_t)slots.size(), base, encrypt_mode_), "SetInput(Encrypt)");
+        } else {   // under the instance's key set; the selection is restored whatever happens
+            const uint32_t was = bce_keyset_selected(cc);
+            ck(bce_keyset_select(cc, instance_keys_[inst]), "SetInput(key set)");
+            const int rc = bce_encrypt_bits(cc, bits.data(), slots.data(), (uint32_t)slots.size(), base, encrypt_mode_);
+            const std::string msg = rc != BCE_OK ? bce_last_error(cc) : "";
+            bce_keyset_select(cc, was);
+            if (rc != BCE_OK) throw std::runtime_error("SetInput(Encrypt): " + msg);
+        }
         if (!constWires_.empty()) {
             // public constants: trivial ciphertexts (a = 0, b = value * q/4), exact and noiseless
             uint64_t p[BCE_P_COUNT];
@@ -511,6 +546,7 @@ void Circuit::setExchange(uint32_t rank, uint32_t world, int shard_mode, bce_all
     if (world > 1 && !fn) throw std::invalid_argument("setExchange: allgather callback missing");
     if (world > 1 && shard_mode == 0 && instances_ % world) throw std::invalid_argument("setExchange: instance sharding needs instances divisible by world");
     if (world > 250) throw std::invalid_argument("setExchange: world too large");
+    if (world > 1 && shard_mode == 1) refuseWithKeys("gate sharding (setExchange)");
     rank_ = rank; world_ = world; shard_mode_ = shard_mode; xfn_ = fn; xuser_ = user;
     if (units_mode_ != xorMode()) buildUnits();   // gate sharding keeps the reference lowering
     host_send_ = host_send; host_recv_ = host_recv; dev_send_ = dev_send; dev_recv_ = dev_recv; xcap_ = capacity;
@@ -703,7 +739,9 @@ void Circuit::ensurePlan(bce_plan*& plan, unsigned lo, uint32_t K) {
         for (const auto& st : steps_.steps)
             if (!st.empty()) { sizes.push_back((uint32_t)st.size()); all.insert(all.end(), st.begin(), st.end()); }
         if (!sizes.empty()) {
-            ck(bce_plan_create(cc, (uint32_t)sizes.size(), sizes.data(), all.data(), K, stride_, lo * stride_, &plan), "Clock(schedule upload)");
+            // with setInstanceKeys: the ids of the instances [lo, lo + K), fixed in the plan
+            const uint32_t* const keys = instance_keys_.empty() ? nullptr : instance_keys_.data() + lo;
+            ck(bce_plan_create_keyed(cc, (uint32_t)sizes.size(), sizes.data(), all.data(), K, stride_, lo * stride_, keys, &plan), "Clock(schedule upload)");
             plan_lo_ = lo; plan_K_ = K; plan_stride_ = stride_;
         }
     }
@@ -802,6 +840,7 @@ void Circuit::compareOutputs(unsigned lo, unsigned hi) {
 // temporaries of its own (SSA: the device runs independent tasks in any order, so no slot may be reused); sched::lower_tasks.
 // Under the shared lowering there is a list only with setDataflowShared: a pair task into the same two temporaries, then the AND.
 void Circuit::setDataflow(bool b) {
+    if (b) refuseWithKeys("setDataflow");
     if (inputs_set_) {
         // the pool layout is fixed.  The schedule can be switched off and on again while that layout has room for its
         // temporaries (it was chosen when the inputs were set; tools/verify_cost.py alternates the schedules on one set of
@@ -882,7 +921,7 @@ std::vector<bce_gate_desc> Circuit::rebased(std::vector<bce_gate_desc> descs, un
 void Circuit::evalStrided(const std::vector<bce_gate_desc>& descs, unsigned lo, uint32_t K, const char* what) {
     if (descs.empty() || !K) return;
     const std::vector<bce_gate_desc> d = rebased(descs, lo);
-    ck(bce_eval_gates_strided(cc, (uint32_t)d.size(), d.data(), K, stride_), what);
+    ck(bce_eval_gates_keyed(cc, (uint32_t)d.size(), d.data(), K, stride_, instance_keys_.empty() ? nullptr : instance_keys_.data() + lo), what);
     ++stats_.sublaunches;
 }
 
@@ -902,7 +941,13 @@ void Circuit::decryptOutputs(unsigned lo, unsigned hi, const std::vector<int>* g
     }
     if (!oslots.empty()) {
         std::vector<uint8_t> res(oslots.size());
-        ck(bce_decrypt_bits(cc, oslots.data(), (uint32_t)oslots.size(), res.data()), "Clock(Decrypt)");
+        if (instance_keys_.empty()) {
+            ck(bce_decrypt_bits(cc, oslots.data(), (uint32_t)oslots.size(), res.data()), "Clock(Decrypt)");
+        } else {   // one gather; every output bit under its instance's key set
+            std::vector<uint32_t> sets(oslots.size());
+            for (size_t k = 0; k < oslots.size(); ++k) sets[k] = instance_keys_[obits[k].first];
+            ck(bce_decrypt_bits_keyed(cc, oslots.data(), (uint32_t)oslots.size(), sets.data(), res.data()), "Clock(Decrypt)");
+        }
         for (size_t k = 0; k < oslots.size(); ++k) circuitOut[obits[k].first][obits[k].second] = res[k];
     }
 }
@@ -1055,6 +1100,9 @@ Outputs Circuit::Clock() {
     size_t done_gates = 0;
     // gate-level rounds (the reference's Clock loop), the bootstrap-depth step schedule or the dataflow kernel: run_mode.hpp
     const RunMode mode = runMode();
+    keysCombinationSupported("Clock");
+    if (!instance_keys_.empty() && mode.path != RunPath::Steps)
+        throw Unsupported("Clock: setInstanceKeys runs the bootstrap-depth step schedule only (encrypted, batched, relevel on, no plaintext pass)");
     const bool releveled = mode.path != RunPath::Rounds;
     if (releveled) {
         auto t0 = Clock_t::now();

@@ -91,6 +91,9 @@ using Inputs = std::vector<std::vector<unsigned int>>;
 using Outputs = std::vector<std::vector<unsigned int>>;
 using NetList = std::map<std::string, NameList>;
 
+// a combination of options the runtime does not implement: BCE_ERR_UNSUPPORTED at the C boundary
+struct Unsupported : std::runtime_error { using std::runtime_error::runtime_error; };
+
 class Circuit {
 public:
     // Circuit(set, method), src/circuit.cpp:45-98: creates the engine on device 0 and generates
@@ -118,6 +121,12 @@ public:
 
     // ---- extensions --------------------------------------------------------------
     void setInstances(unsigned k);            // K lock-step input sets (before SetInput)
+    // Per-instance key sets (bce_gpu.h, "key sets"): instance k is encrypted, evaluated and decrypted under set ids[k] of the
+    // engine.  Before SetInput, one id per instance; an empty list returns to the selected set.  Clock() then runs the
+    // bootstrap-depth step schedule keyed (bce_plan_create_keyed; setGraph on top).  Not together with setDataflow, setVerify,
+    // setDeviceVerify or gate sharding: Unsupported, from this setter, from those setters and at SetInput.
+    void setInstanceKeys(const std::vector<uint32_t>& ids);
+    const std::vector<uint32_t>& getInstanceKeys() const { return instance_keys_; }
     unsigned getInstances() const { return instances_; }
     // ---- what a Clock() runs.  The setters below record choices; which path, XOR lowering, device checks and graph
     // replay result from them is decided in ONE place, resolve_mode() in run_mode.hpp (table: DESIGN.md 5.1), and the
@@ -166,7 +175,7 @@ public:
     bool getDataflowShared() const { return opt_.dataflow_shared; }
     // opt-in: replay the bootstrap-depth schedule's launches as ONE hipGraph per Clock() (bce_plan_run) instead of one
     // host call per step.  Same ciphertexts.
-    void setGraph(bool b) { opt_.graph = b; }
+    void setGraph(bool b) { opt_.graph = b; }   // (with setInstanceKeys: the keyed plan's graph)
     bool getGraph() const { return opt_.graph; }
     bool graphActive() const { return runMode().graph; }
     // opt-in: verify mode (src/gate.cpp:153-160: decrypt every gate output, compare with the plaintext pass, "Bad <OP> fixing",
@@ -174,7 +183,7 @@ public:
     // persistent kernel with setDataflow, instead of the gate-level rounds with one host decryption per level.  Differences
     // to the host path: a repaired register holds the trivial ciphertext of the right bit (bce_gpu.h), and NOT gates have no
     // register on these schedules, so a wrong NOT input is caught at its consumer -- fix counts can differ for that reason.
-    void setDeviceVerify(bool b) { setModeFlag(opt_.device_verify, b, "setDeviceVerify"); }
+    void setDeviceVerify(bool b) { if (b) refuseWithKeys("setDeviceVerify"); setModeFlag(opt_.device_verify, b, "setDeviceVerify"); }
     bool getDeviceVerify() const { return opt_.device_verify; }
     bool deviceVerifyActive() const { return runMode().device_checks; }
     const bce_check_report& checkReport() const { return check_report_; }   // of the last Clock() on the device path
@@ -247,6 +256,9 @@ private:
     unsigned n_buses_ = 0;
 
     unsigned instances_ = 1;
+    std::vector<uint32_t> instance_keys_;           // setInstanceKeys: [instances_] key-set ids, or empty
+    void refuseWithKeys(const char* who) const;     // Unsupported when instance keys are set
+    void keysCombinationSupported(const char* who) const;   // Unsupported when instance keys meet dataflow, verify, device verify or gate sharding
     std::vector<std::vector<uint8_t>> plain_;       // [instance][wire]
     std::vector<std::vector<uint8_t>> circuitOut;   // [instance][bit]
     uint64_t enc_counter_ = 0, epoch_ = 0;

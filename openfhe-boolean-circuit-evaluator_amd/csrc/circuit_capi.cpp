@@ -33,6 +33,9 @@ int guarded(bce_circuit* h, F fn) {
     } catch (const std::logic_error& e) {
         h->err = e.what();
         return BCE_ERR_STATE;
+    } catch (const bce::Unsupported& e) {
+        h->err = e.what();
+        return BCE_ERR_UNSUPPORTED;
     } catch (const std::exception& e) {
         h->err = e.what();
         return BCE_ERR_STATE;
@@ -88,6 +91,12 @@ int bce_circuit_xor_shared_active(const bce_circuit* h) { return h && h->c.xorSh
 int bce_circuit_set_relevel(bce_circuit* h, int on) { return guarded(h, [&] { h->c.setRelevel(on != 0); }); }
 int bce_circuit_get_relevel(bce_circuit* h) { return h && h->c.getRelevel() ? 1 : 0; }
 int bce_circuit_set_instances(bce_circuit* h, uint32_t k) { return guarded(h, [&] { h->c.setInstances(k); }); }
+int bce_circuit_set_instance_keysets(bce_circuit* h, const uint32_t* ids, uint32_t count) {
+    return guarded(h, [&] {
+        if (count && !ids) throw std::invalid_argument("bce_circuit_set_instance_keysets: null id list");
+        h->c.setInstanceKeys(std::vector<uint32_t>(ids, ids + count));
+    });
+}
 int bce_circuit_set_shard_locality(bce_circuit* h, int on) { return guarded(h, [&] { h->c.setShardLocality(on != 0); }); }
 uint64_t bce_circuit_plan_hash(const bce_circuit* h) { return h ? h->c.planHash() : 0; }
 int bce_circuit_get_encrypt_mode(const bce_circuit* h) { return h ? h->c.getEncryptMode() : -1; }

@@ -257,7 +257,7 @@ typedef const __attribute__((address_space(4))) DevParams ConstDevParams;
 typedef const __attribute__((address_space(4))) DagParams ConstDagParams;
 template <typename C, typename S>
 __device__ __forceinline__ C* as_constant(const S* p) {
-    C* c = (C*)(uintptr_t)p;
+    C* c = to_constant<C>(p);   // gate_front.hpp
     asm volatile("" : "+s"(c));
     return c;
 }
@@ -288,7 +288,7 @@ __device__ __forceinline__ void dag_check(const DT& D, const PT& P, u32 t, u32 k
     const u32 slot = u_ld(&D.tasks[t].out) + D.slot_base + k * D.slot_stride;
     const u32 n = P.n, q = P.q;
     u32* const row = P.pool + (size_t)slot * P.pool_stride;
-    const LweRowCheck r = lwe_row_check<true>(row, D.s8, n, q, want, lane);
+    const LweRowCheck r = lwe_row_check<true>(row, key_set(P, k).s8, n, q, want, lane);
     const u32 got = __builtin_amdgcn_readfirstlane(r.got);
     const int err = (int)__builtin_amdgcn_readfirstlane((u32)r.err);
     const bool bad = got != want, fix = bad && D.repair != 0;

@@ -80,6 +80,14 @@ int upload_ctx(bce_ctx* c, const HostTables& T) {
         if (!up(c->d_fwd_mfma, T.fwd.table, "forward matrix table")) return BCE_ERR_HIP;
         P.fwd_mfma_tab = c->d_fwd_mfma.get();
     }
+    // the key-set table: every entry null until a set gets its buffers (alloc_keys)
+    if (c->d_keysets.alloc(BCE_MAX_KEYSETS) != hipSuccess || hipMemset(c->d_keysets.get(), 0, BCE_MAX_KEYSETS * sizeof(KeySetDev)) != hipSuccess) {
+        g_create_error = "hipMalloc(key-set table) failed";
+        return BCE_ERR_HIP;
+    }
+    P.keysets = c->d_keysets.get();
+    P.keyset_sel = 0;
+    P.keyset_map = nullptr;
     c->enc_seed_ok = os_entropy(c->enc_seed);
     return BCE_OK;
 }
@@ -110,6 +118,7 @@ int build_ctx(const Shape& s, int device, bce_ctx** out) {
     c->method = s.method; c->device = device;
     c->is64 = P.is64 != 0;
     c->wbytes = c->is64 ? 8 : 4;
+    c->keysets[0] = std::make_unique<KeySet>();
     if (const int rc = upload_ctx(c.get(), cp.T)) return rc;
     *out = c.release();
     return BCE_OK;
@@ -119,9 +128,9 @@ u64 rgsw_rows_total(const bce_ctx* c);
 // evaluation-form key words -> what the kernels read: rows l >= 1 of every RGSW ciphertext minus B^l times row 0
 // when the lowest gadget digit is folded (P.fold); IEEE doubles for the double-precision 64-bit kernels (exact, Q < 2^39)
 int bsk_words_to_kernel_layout(bce_ctx* c) {
-    if (c->P.fold) HIP_TRY(c, launch_fold_gadget(c->P, c->d_bsk.get(), rgsw_rows_total(c) / (2ull * c->dG), +1, c->stream));
+    if (c->P.fold) HIP_TRY(c, launch_fold_gadget(c->P, c->keys().d_bsk.get(), rgsw_rows_total(c) / (2ull * c->dG), +1, c->stream));
     if (!c->P.fp64) { HIP_TRY(c, hipStreamSynchronize(c->stream)); return BCE_OK; }
-    HIP_TRY(c, launch_words_u64_f64(reinterpret_cast<u64*>(c->d_bsk.get()), (size_t)c->bsk_polys * c->N, 1, c->stream));
+    HIP_TRY(c, launch_words_u64_f64(reinterpret_cast<u64*>(c->keys().d_bsk.get()), (size_t)c->keys().bsk_polys * c->N, 1, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return BCE_OK;
 }
@@ -132,17 +141,20 @@ u64 rgsw_rows_total(const bce_ctx* c) {
 }
 
 int alloc_keys(bce_ctx* c) {
-    if (!c->d_bsk.get()) {
-        c->bsk_polys = rgsw_rows_total(c) * 2;
-        HIP_TRY(c, c->d_bsk.alloc(c->wbytes * c->bsk_polys * c->N));
+    if (c->keys().d_bsk.get() && c->keys().d_ksk.get() && c->keys().d_s8.get()) return BCE_OK;   // (and the table holds their row)
+    if (!c->keys().d_bsk.get()) {
+        c->keys().bsk_polys = rgsw_rows_total(c) * 2;
+        HIP_TRY(c, c->keys().d_bsk.alloc(c->wbytes * c->keys().bsk_polys * c->N));
     }
-    if (!c->d_ksk.get()) {
+    if (!c->keys().d_ksk.get()) {
         size_t rows = (size_t)c->N * c->baseKS * c->dKS;
-        HIP_TRY(c, c->d_ksk.alloc(rows * c->P.ksk_stride * (c->P.ksk_u16 ? 2 : 4)));
+        HIP_TRY(c, c->keys().d_ksk.alloc(rows * c->P.ksk_stride * (c->P.ksk_u16 ? 2 : 4)));
     }
-    c->P.bsk = reinterpret_cast<const u32*>(c->d_bsk.get());
-    c->P.bsk64 = reinterpret_cast<const u64*>(c->d_bsk.get());
-    c->P.ksk = c->d_ksk.get();
+    if (!c->keys().d_s8.get()) HIP_TRY(c, c->keys().d_s8.alloc(((size_t)c->n + 63) / 64 * 64));
+    // the set's row of the device table: written when the set gets its buffers (they never move), after the work in flight
+    const KeySetDev row{c->keys().d_bsk.get(), c->keys().d_ksk.get(), c->keys().d_s8.get()};
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(c->d_keysets.get() + c->selected, &row, sizeof row, hipMemcpyHostToDevice));
     return BCE_OK;
 }
 
@@ -153,40 +165,43 @@ int upload_ksk(bce_ctx* c, const u32* ksk) {
         std::vector<uint16_t> buf(rows * S, 0);
         for (size_t r = 0; r < rows; ++r)
             for (size_t k = 0; k < W; ++k) buf[r * S + k] = (uint16_t)ksk[r * W + k];
-        HIP_TRY(c, hipMemcpy(c->d_ksk.get(), buf.data(), buf.size() * 2, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(c->keys().d_ksk.get(), buf.data(), buf.size() * 2, hipMemcpyHostToDevice));
     } else {
         std::vector<u32> buf(rows * S, 0);
         for (size_t r = 0; r < rows; ++r) std::memcpy(&buf[r * S], &ksk[r * W], W * 4);
-        HIP_TRY(c, hipMemcpy(c->d_ksk.get(), buf.data(), buf.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(c->keys().d_ksk.get(), buf.data(), buf.size() * 4, hipMemcpyHostToDevice));
     }
     return BCE_OK;
 }
 
 // the LWE secret as the device-side check reads it (k_lwe_check): int8[n], padded with zeros to a multiple of 64.  The
-// buffer is allocated once per context, so a captured plan's pointer to it survives a key import.
+// buffer is allocated once per key set (alloc_keys), so the device table's pointer to it survives a key import.
 int upload_secret(bce_ctx* c) {
     const size_t padded = ((size_t)c->n + 63) / 64 * 64;
     std::vector<int8_t> s8(padded, 0);
-    for (u32 k = 0; k < c->n; ++k) s8[k] = (int8_t)c->s[k];
-    if (!c->d_s8.get()) HIP_TRY(c, c->d_s8.alloc(padded));   // once: the pointer must not move (see above)
+    for (u32 k = 0; k < c->n; ++k) s8[k] = (int8_t)c->keys().s[k];
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(c->d_s8.get(), s8.data(), padded, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->keys().d_s8.get(), s8.data(), padded, hipMemcpyHostToDevice));
     return BCE_OK;
 }
 
 // Stage a descriptor list into the next ring slot (1,024 descriptors at least).  The caller launches the kernel that reads
-// descs_of(slot) and then marks the slot: its event must follow that kernel, not just the copy.
-int stage_descs(bce_ctx* c, const bce_gate_desc* d, size_t n, StagedUpload** slot) {
+// descs_of(slot) and then marks the slot: its event must follow that kernel, not just the copy.  map (may be null): the
+// key-set map of a keyed launch, n_map words behind the descriptors in the same copy (map_of).
+int stage_descs(bce_ctx* c, const bce_gate_desc* d, size_t n, StagedUpload** slot, const u32* map = nullptr, size_t n_map = 0) {
     StagedUpload& r = c->ring[c->ring_pos];
     c->ring_pos = (c->ring_pos + 1) % bce_ctx::kRing;
-    const size_t bytes = n * sizeof(bce_gate_desc);
-    HIP_TRY(c, r.reserve(bytes, std::max(n, (size_t)1024) * sizeof(bce_gate_desc), nullptr));
-    std::memcpy(r.host(), d, bytes);
+    const size_t dbytes = n * sizeof(bce_gate_desc), bytes = dbytes + (map ? n_map * sizeof(u32) : 0);
+    HIP_TRY(c, r.reserve(bytes, std::max(bytes, (size_t)1024 * sizeof(bce_gate_desc)), nullptr));
+    std::memcpy(r.host(), d, dbytes);
+    if (map) std::memcpy(static_cast<char*>(r.host()) + dbytes, map, n_map * sizeof(u32));
     HIP_TRY(c, r.copy(bytes, c->stream));
     *slot = &r;
     return BCE_OK;
 }
 const bce_gate_desc* descs_of(const StagedUpload* slot) { return static_cast<const bce_gate_desc*>(slot->device()); }
+const u32* map_of(const StagedUpload* slot, size_t n) { return reinterpret_cast<const u32*>(descs_of(slot) + n); }
+static_assert(sizeof(bce_gate_desc) % sizeof(u32) == 0, "a key-set map behind a descriptor list is aligned");
 
 void drain_timing(bce_ctx* c) {
     for (auto& p : c->pending) {
@@ -240,11 +255,11 @@ struct KeygenDev {
 };
 
 int keygen_params(bce_ctx* c, const GaussSampler& gauss, KeygenDev& D, KeygenParams& kp) {
-    HIP_TRY(c, upload_vector(D.s, c->s));
-    HIP_TRY(c, upload_vector(D.z, c->z));
+    HIP_TRY(c, upload_vector(D.s, c->keys().s));
+    HIP_TRY(c, upload_vector(D.z, c->keys().z));
     HIP_TRY(c, D.cdf.alloc(81));
     HIP_TRY(c, hipMemcpy(D.cdf.get(), gauss.table(), 81 * sizeof(u64), hipMemcpyHostToDevice));
-    std::memcpy(kp.seed, c->seed, 32);
+    std::memcpy(kp.seed, c->keys().seed, 32);
     kp.n = c->n; kp.N = c->N; kp.Q = c->Q; kp.q = c->q; kp.qKS = c->qKS;
     kp.qbits = bit_length(c->Q - 1); kp.ksbits = bit_length(c->qKS - 1);
     kp.R = 2 * c->dG; kp.ap = c->method == BCE_AP ? 1 : 0; kp.baseR = c->baseR; kp.dR = c->dR;
@@ -270,12 +285,12 @@ int keygen_bsk(bce_ctx* c, const KeygenParams& kp, KeygenDev& D) {
     HIP_TRY(c, D.zq.alloc(N * wb));
     {
         std::vector<u64> zq(N);
-        for (u32 k = 0; k < N; ++k) zq[k] = lift_signed(c->z[k], Q);
+        for (u32 k = 0; k < N; ++k) zq[k] = lift_signed(c->keys().z[k], Q);
         if (const int rc = words_to_device(c, D.zq.get(), zq.data(), N, c->is64)) return rc;
     }
     int rc = dev_ntt(c, D.zq.get(), 1, 0);
     if (rc) return rc;
-    char* dev = c->d_bsk.get();
+    char* dev = c->keys().d_bsk.get();
     for (u64 r0 = 0; r0 < rows; r0 += chunk) {
         const u64 cnt = std::min(chunk, rows - r0);
         char* dst = dev + r0 * 2 * N * wb;
@@ -304,11 +319,12 @@ int check_dag_runs(bce_ctx* c) {
     return rc;
 }
 
+// map (may be null): the key set of every instance (bce_eval_gates_keyed); null: every instance runs under the selected set
 int eval_impl(bce_ctx* c, u32 n_desc, const bce_gate_desc* descs, u32 instances, u32 slot_stride, u64* dbg_acc,
-              u64* dbg_lweN, u64* dbg_ks) {
+              u64* dbg_lweN, u64* dbg_ks, const u32* map = nullptr) {
     if (n_desc == 0 || instances == 0) return BCE_OK;
     if (!descs) return c->fail(BCE_ERR_ARG, "null descriptor list");
-    if (const int rc = need_keys(c)) return rc;
+    if (const int rc = map ? need_keys_of_map(c, "bce_eval_gates_keyed", map, instances) : need_keys(c)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     std::vector<bce_gate_desc> boot, unary;
     boot.reserve(n_desc);
@@ -328,14 +344,15 @@ int eval_impl(bce_ctx* c, u32 n_desc, const bce_gate_desc* descs, u32 instances,
         int rc = ensure_acc(c, nb);
         if (rc) return rc;
         StagedUpload* slot = nullptr;
-        rc = stage_descs(c, boot.data(), boot.size(), &slot);
+        rc = stage_descs(c, boot.data(), boot.size(), &slot, map, instances);
         if (rc) return rc;
         DevBuf<u32> d_lweN, d_ks;
         // staged outputs of a launch with pairs: the kernels write the second outputs to a second block of nb rows
         const size_t dbg_rows = n_pairs ? 2 * nb : nb;
         if (dbg_lweN) HIP_TRY(c, d_lweN.alloc(dbg_rows * (c->N + 1)));
         if (dbg_ks) HIP_TRY(c, d_ks.alloc(dbg_rows * (c->n + 1)));
-        rc = launch_bootstraps(c, descs_of(slot), (u32)boot.size(), instances, slot_stride, c->d_acc.get(), d_lweN.get(), d_ks.get(), true, nullptr, n_pairs != 0);
+        rc = launch_bootstraps(c, descs_of(slot), (u32)boot.size(), instances, slot_stride, c->d_acc.get(), d_lweN.get(), d_ks.get(), true, nullptr, n_pairs != 0, nullptr,
+                               map ? map_of(slot, boot.size()) : nullptr);
         if (rc) return rc;
         slot->mark(c->stream);
         if (dbg_acc || dbg_lweN || dbg_ks) {
@@ -430,8 +447,10 @@ int expected_are_messages(bce_ctx* c, const char* who, const uint8_t* expect, si
 // bce_timing; untimed (stream capture of bce_plan_run): launches only, *fused_out says whether the tail was fused.
 // pairs: at least one descriptor is a pair (its second tail pass runs in the fused epilogue or as a second tail launch).
 int launch_bootstraps(bce_ctx* c, const bce_gate_desc* dd, u32 n, u32 instances, u32 slot_stride, void* d_acc,
-                      u32* d_lweN, u32* d_ks, bool timed, bool* fused_out, bool pairs, u64* d_partial) {
+                      u32* d_lweN, u32* d_ks, bool timed, bool* fused_out, bool pairs, u64* d_partial, const u32* d_map) {
     const size_t nb = (size_t)n * instances;
+    DevParams P = c->P;      // the launch's copy: a keyed launch (d_map: [instances] key-set ids on the device) names its map in it
+    P.keyset_map = d_map;
     int kid = 0;
     bool tail_fused = false;
     const bool events = timed && c->events_on;
@@ -440,7 +459,7 @@ int launch_bootstraps(bce_ctx* c, const bce_gate_desc* dd, u32 n, u32 instances,
     LaunchEvents le0{};
     if (events) { e0 = get_events(c, 0); le0 = LaunchEvents{e0.a, e0.b}; }
     {   // a launch that fails hands its event pair back (it would otherwise be neither pending nor free)
-        const hipError_t e = launch_blind_rotate(c->P, dd, n, instances, slot_stride, d_acc, c->stream, &kid, d_lweN, d_ks, &tail_fused, le0);
+        const hipError_t e = launch_blind_rotate(P, dd, n, instances, slot_stride, d_acc, c->stream, &kid, d_lweN, d_ks, &tail_fused, le0);
         if (e != hipSuccess) {
             if (events) c->free_events.push_back(e0);
             HIP_TRY(c, e);
@@ -462,10 +481,10 @@ int launch_bootstraps(bce_ctx* c, const bce_gate_desc* dd, u32 n, u32 instances,
             le1 = LaunchEvents{e1.a, e1.b};
         }
         if (!d_partial) {
-            const size_t need = tail_partial_words(c->P, (u32)nb);   // grows like the accumulators (ensure_acc)
+            const size_t need = tail_partial_words(P, (u32)nb);   // grows like the accumulators (ensure_acc)
             HIP_TRY(c, c->d_tail_partial.grow(need, std::max(need, 2 * c->d_tail_partial.capacity()), c->stream));
         }
-        const hipError_t e = launch_tail(c->P, dd, n, instances, slot_stride, d_acc, d_partial ? d_partial : c->d_tail_partial.get(), d_lweN, d_ks, c->stream, le1, pairs);
+        const hipError_t e = launch_tail(P, dd, n, instances, slot_stride, d_acc, d_partial ? d_partial : c->d_tail_partial.get(), d_lweN, d_ks, c->stream, le1, pairs);
         if (e != hipSuccess) {
             if (events) c->free_events.push_back(e1);
             HIP_TRY(c, e);
@@ -553,13 +572,13 @@ int bce_keygen(bce_ctx* c, const uint8_t seed_in[32]) {
     HIP_TRY(c, hipSetDevice(c->device));
     int rc = alloc_keys(c);
     if (rc) return rc;
-    std::memcpy(c->seed, seed, 32);
+    std::memcpy(c->keys().seed, seed, 32);
     const u32 n = c->n, N = c->N;
     const GaussSampler gauss(3.19);
-    c->s.resize(n);
-    c->z.resize(N);
-    { ChaChaStream st(seed, kDomSK, 0); for (u32 i = 0; i < n; ++i) c->s[i] = draw_ternary(st); }
-    { ChaChaStream st(seed, kDomZ, 0); for (u32 i = 0; i < N; ++i) c->z[i] = draw_ternary(st); }
+    c->keys().s.resize(n);
+    c->keys().z.resize(N);
+    { ChaChaStream st(seed, kDomSK, 0); for (u32 i = 0; i < n; ++i) c->keys().s[i] = draw_ternary(st); }
+    { ChaChaStream st(seed, kDomZ, 0); for (u32 i = 0; i < N; ++i) c->keys().z[i] = draw_ternary(st); }
     if ((rc = upload_secret(c))) return rc;
 
     KeygenDev D;
@@ -569,13 +588,13 @@ int bce_keygen(bce_ctx* c, const uint8_t seed_in[32]) {
     // the padded row layout the tail kernel gathers from
     {
         const u64 rows = (u64)N * c->baseKS * c->dKS;
-        HIP_TRY(c, hipMemsetAsync(c->d_ksk.get(), 0, rows * c->P.ksk_stride * (c->P.ksk_u16 ? 2 : 4), c->stream));
-        HIP_TRY(c, launch_gen_ksk_rows(kp, rows, c->d_ksk.get(), c->P.ksk_u16 ? 1 : 0, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->keys().d_ksk.get(), 0, rows * c->P.ksk_stride * (c->P.ksk_u16 ? 2 : 4), c->stream));
+        HIP_TRY(c, launch_gen_ksk_rows(kp, rows, c->keys().d_ksk.get(), c->P.ksk_u16 ? 1 : 0, c->stream));
     }
     rc = keygen_bsk(c, kp, D);
     if (!rc) rc = bsk_words_to_kernel_layout(c);
     if (rc) return rc;
-    c->have_keys = true;
+    c->keys().have_keys = true;
     return BCE_OK;
 }
 
@@ -599,9 +618,9 @@ static int import_keys_impl(bce_ctx* c, const int32_t* s, const int32_t* z, cons
     HIP_TRY(c, hipSetDevice(c->device));
     int rc = alloc_keys(c);
     if (rc) return rc;
-    c->s.assign(s, s + c->n);
-    if (z) c->z.assign(z, z + c->N); else c->z.clear();
-    std::memset(c->seed, 0, sizeof c->seed);   // imported keys have no generation seed
+    c->keys().s.assign(s, s + c->n);
+    if (z) c->keys().z.assign(z, z + c->N); else c->keys().z.clear();
+    std::memset(c->keys().seed, 0, sizeof c->keys().seed);   // imported keys have no generation seed
     if ((rc = upload_secret(c))) return rc;
     {   // words -> device words, chunked; coefficient-domain words are then transformed in place on the device
         // (evaluation-form words arrive in the engine's own order: OpenFHE's bit-reversed CT order for the minimal
@@ -611,22 +630,22 @@ static int import_keys_impl(bce_ctx* c, const int32_t* s, const int32_t* z, cons
             const u64 cnt = std::min(chunk, bsk_words - o);
             for (u64 i = 0; i < cnt; ++i)
                 if (bsk[o + i] >= c->Q) return c->fail(BCE_ERR_ARG, "bsk word %llu not reduced mod Q", (unsigned long long)(o + i));
-            if ((rc = words_to_device(c, c->d_bsk.get() + o * c->wbytes, bsk + o, cnt, c->is64))) return rc;
+            if ((rc = words_to_device(c, c->keys().d_bsk.get() + o * c->wbytes, bsk + o, cnt, c->is64))) return rc;
         }
-        if (!evaluation_form && (rc = dev_ntt(c, c->d_bsk.get(), bsk_words / c->N, 0))) return rc;
+        if (!evaluation_form && (rc = dev_ntt(c, c->keys().d_bsk.get(), bsk_words / c->N, 0))) return rc;
         if ((rc = bsk_words_to_kernel_layout(c))) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     rc = upload_ksk(c, ksk);
     if (rc) return rc;
-    c->have_keys = true;
+    c->keys().have_keys = true;
     return BCE_OK;
 }
 
 int bce_export_sk(const bce_ctx* c, int32_t* s, int32_t* z) {
-    if (!c || !c->have_keys) return BCE_ERR_NO_KEYS;
-    if (s) std::memcpy(s, c->s.data(), c->n * sizeof(int32_t));
-    if (z && !c->z.empty()) std::memcpy(z, c->z.data(), c->N * sizeof(int32_t));
+    if (!c || !c->keys().have_keys) return BCE_ERR_NO_KEYS;   // (c->keys(): the selected set, like every call without a map)
+    if (s) std::memcpy(s, c->keys().s.data(), c->n * sizeof(int32_t));
+    if (z && !c->keys().z.empty()) std::memcpy(z, c->keys().z.data(), c->N * sizeof(int32_t));
     return BCE_OK;
 }
 
@@ -635,7 +654,7 @@ int bce_export_bsk(bce_ctx* c, uint64_t* bsk) { return export_bsk_impl(c, bsk, f
 
 static int export_bsk_impl(bce_ctx* c, uint64_t* bsk, bool evaluation_form) {
     if (!c || !bsk) return BCE_ERR_ARG;
-    if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "no keys");
+    if (!c->keys().have_keys) return c->fail(BCE_ERR_NO_KEYS, "no keys");
     HIP_TRY(c, hipSetDevice(c->device));
     const u64 words = bce_bsk_words(c);
     const u64 per_rgsw = 4ull * c->dG;  // polynomials of one RGSW ciphertext: chunks hold whole ciphertexts (un-folding works per ciphertext)
@@ -645,7 +664,7 @@ static int export_bsk_impl(bce_ctx* c, uint64_t* bsk, bool evaluation_form) {
     void* const d_tmp = tmp.get();
     for (u64 p0 = 0; p0 < words / c->N; p0 += chunk_polys) {
         const u64 cnt = std::min(chunk_polys, words / c->N - p0), w = cnt * c->N;
-        const char* src = c->d_bsk.get() + p0 * c->N * c->wbytes;
+        const char* src = c->keys().d_bsk.get() + p0 * c->N * c->wbytes;
         HIP_TRY(c, hipMemcpyAsync(d_tmp, src, w * c->wbytes, hipMemcpyDeviceToDevice, c->stream));
         if (c->P.fp64) HIP_TRY(c, launch_words_u64_f64(static_cast<u64*>(d_tmp), w, 0, c->stream));  // doubles -> u64 words
         if (c->P.fold) HIP_TRY(c, launch_fold_gadget(c->P, d_tmp, cnt / (4ull * c->dG), -1, c->stream));   // rows l >= 1 += B^l row 0
@@ -660,17 +679,17 @@ int bce_export_bsk_eval(bce_ctx* c, uint64_t* bsk) { return export_bsk_impl(c, b
 
 int bce_export_ksk(bce_ctx* c, uint32_t* ksk) {
     if (!c || !ksk) return BCE_ERR_ARG;
-    if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "no keys");
+    if (!c->keys().have_keys) return c->fail(BCE_ERR_NO_KEYS, "no keys");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t rows = (size_t)c->N * c->baseKS * c->dKS, W = c->n + 1, S = c->P.ksk_stride;
     if (c->P.ksk_u16) {
         std::vector<uint16_t> buf(rows * S);
-        HIP_TRY(c, hipMemcpy(buf.data(), c->d_ksk.get(), buf.size() * 2, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(buf.data(), c->keys().d_ksk.get(), buf.size() * 2, hipMemcpyDeviceToHost));
         for (size_t r = 0; r < rows; ++r)
             for (size_t k = 0; k < W; ++k) ksk[r * W + k] = buf[r * S + k];
     } else {
         std::vector<u32> buf(rows * S);
-        HIP_TRY(c, hipMemcpy(buf.data(), c->d_ksk.get(), buf.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(buf.data(), c->keys().d_ksk.get(), buf.size() * 4, hipMemcpyDeviceToHost));
         for (size_t r = 0; r < rows; ++r) std::memcpy(&ksk[r * W], &buf[r * S], W * 4);
     }
     return BCE_OK;
@@ -754,7 +773,7 @@ int bce_lwe_read(bce_ctx* c, const uint32_t* slots, uint32_t count, uint64_t* ct
 int bce_encrypt_bits(bce_ctx* c, const uint8_t* bits, const uint32_t* slots, uint32_t count, uint64_t enc_index_base,
                      int mode) {
     if (!c || !bits || !slots) return BCE_ERR_ARG;
-    if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "no keys");
+    if (!c->keys().have_keys) return c->fail(BCE_ERR_NO_KEYS, "no keys");
     const u32 n = c->n;
     const u64 q = c->q;
     const size_t W = n + 1;
@@ -772,7 +791,7 @@ int bce_encrypt_bits(bce_ctx* c, const uint8_t* bits, const uint32_t* slots, uin
         u128 acc = 0;
         for (u32 k = 0; k < n; ++k) {
             ct[k] = draw_uniform(st, q);
-            acc += (u128)ct[k] * lift_signed(c->s[k], q);
+            acc += (u128)ct[k] * lift_signed(c->keys().s[k], q);
         }
         u64 e = lift_signed(gauss.draw(st), q);
         ct[n] = (u64)((acc + e + (u64)(bits[i] % 4) * (q / 4)) % q);
@@ -803,8 +822,12 @@ int bce_set_encrypt_seed(bce_ctx* c, const uint8_t seed[32]) {
 }
 
 int bce_decrypt_bits(bce_ctx* c, const uint32_t* slots, uint32_t count, uint8_t* bits) {
+    return bce_decrypt_bits_keyed(c, slots, count, nullptr, bits);
+}
+
+int bce_decrypt_bits_keyed(bce_ctx* c, const uint32_t* slots, uint32_t count, const uint32_t* keyset_of_slot, uint8_t* bits) {
     if (!c || !slots || !bits) return BCE_ERR_ARG;
-    if (!c->have_keys) return c->fail(BCE_ERR_NO_KEYS, "no keys");
+    if (const int rc = keyset_of_slot ? need_keys_of_map(c, "bce_decrypt_bits_keyed", keyset_of_slot, count) : need_keys(c)) return rc;
     const u32 n = c->n;
     const u64 q = c->q;
     const size_t W = n + 1;
@@ -813,16 +836,17 @@ int bce_decrypt_bits(bce_ctx* c, const uint32_t* slots, uint32_t count, uint8_t*
     if (rc) return rc;
     for (u32 i = 0; i < count; ++i) {
         const u64* ct = &cts[(size_t)i * W];
+        const std::vector<int32_t>& s = keyset_of_slot ? c->keysets[keyset_of_slot[i]]->s : c->keys().s;
         // <a, s> over the integers with s in {-1, 0, 1}: |sum| < n q, reduced once (same residue as the reference's
         // mod-q accumulation, lwe-pke.cpp Decrypt)
         u64 inner_q;
         if (q <= (1ull << 24)) {
             int64_t inner = 0;
-            for (u32 k = 0; k < n; ++k) inner += (int64_t)ct[k] * c->s[k];
+            for (u32 k = 0; k < n; ++k) inner += (int64_t)ct[k] * s[k];
             inner_q = (u64)(((inner % (int64_t)q) + (int64_t)q) % (int64_t)q);
         } else {
             u128 inner = 0;
-            for (u32 k = 0; k < n; ++k) inner += (u128)ct[k] * lift_signed(c->s[k], q);
+            for (u32 k = 0; k < n; ++k) inner += (u128)ct[k] * lift_signed(s[k], q);
             inner_q = (u64)(inner % q);
         }
         u64 r = (ct[n] + q - inner_q) % q;
@@ -842,6 +866,52 @@ int bce_eval_gates_strided(bce_ctx* c, uint32_t n_desc, const bce_gate_desc* des
     if (!c) return BCE_ERR_ARG;
     return eval_impl(c, n_desc, descs, instances, slot_stride, nullptr, nullptr, nullptr);
 }
+
+int bce_eval_gates_keyed(bce_ctx* c, uint32_t n_desc, const bce_gate_desc* descs, uint32_t instances, uint32_t slot_stride,
+                         const uint32_t* keyset_of_instance) {
+    if (!c) return BCE_ERR_ARG;
+    return eval_impl(c, n_desc, descs, instances, slot_stride, nullptr, nullptr, nullptr, keyset_of_instance);
+}
+
+// ---- key sets (include/bce_gpu.h, "key sets") --------------------------------------------------------------------------
+int bce_keyset_add(bce_ctx* c, uint32_t* id) {
+    if (!c || !id) return BCE_ERR_ARG;
+    for (u32 i = 1; i < BCE_MAX_KEYSETS; ++i)
+        if (!c->keysets[i]) {
+            c->keysets[i] = std::make_unique<KeySet>();
+            *id = i;
+            return BCE_OK;
+        }
+    return c->fail(BCE_ERR_ARG, "bce_keyset_add: the context holds %d key sets already", BCE_MAX_KEYSETS);
+}
+
+int bce_keyset_select(bce_ctx* c, uint32_t id) {
+    if (!c) return BCE_ERR_ARG;
+    if (id >= BCE_MAX_KEYSETS || !c->keysets[id]) return c->fail(BCE_ERR_ARG, "bce_keyset_select: key set %u does not exist", id);
+    c->selected = c->P.keyset_sel = id;
+    return BCE_OK;
+}
+
+int bce_keyset_drop(bce_ctx* c, uint32_t id) {
+    if (!c) return BCE_ERR_ARG;
+    if (id >= BCE_MAX_KEYSETS || !c->keysets[id]) return c->fail(BCE_ERR_ARG, "bce_keyset_drop: key set %u does not exist", id);
+    if (id == 0) return c->fail(BCE_ERR_ARG, "bce_keyset_drop: key set 0 lives as long as the context");
+    if (id == c->selected) return c->fail(BCE_ERR_ARG, "bce_keyset_drop: key set %u is the selected one", id);
+    if (plan_names_keyset(c, id)) return c->fail(BCE_ERR_STATE, "bce_keyset_drop: a live plan was created with a map that names key set %u", id);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = sync_stream(c)) return rc;
+    const KeySetDev none{};
+    HIP_TRY(c, hipMemcpy(c->d_keysets.get() + id, &none, sizeof none, hipMemcpyHostToDevice));
+    c->keysets[id].reset();
+    return BCE_OK;
+}
+
+uint32_t bce_keyset_count(const bce_ctx* c) {
+    u32 count = 0;
+    for (u32 i = 0; c && i < BCE_MAX_KEYSETS; ++i) count += c->keysets[i] ? 1 : 0;
+    return count;
+}
+uint32_t bce_keyset_selected(const bce_ctx* c) { return c ? c->selected : 0; }
 
 int bce_synchronize(bce_ctx* c) {
     if (!c) return BCE_ERR_ARG;

@@ -177,7 +177,7 @@ int bce_dag_run(bce_ctx* c, bce_dag* g, uint32_t instances, uint32_t slot_stride
     if (g->n_checks) {   // verify mode: the worker checks (and repairs) before it releases a task's consumers
         if (const int rc = ensure_check(c)) return rc;
         D.chk_of_task = g->d_chk_of_task.get(); D.expect = static_cast<const uint8_t*>(g->expect.device()); D.n_checks = g->n_checks; D.repair = (u32)g->chk_repair;
-        D.s8 = c->d_s8.get(); D.report = c->d_check(); D.log = c->d_check_log();
+        D.report = c->d_check(); D.log = c->d_check_log();
     }
     // one or two workgroups per CU, the grid, the policy bits and the gate constants (ctx_params.cpp)
     const DagLaunchChoice L = dag_launch_choice(c->P, kernel_class(c->P).wg_per_cu_full, c->P.is64 ? 0 : bootstrap_dag_lds_bytes(c->P, 4),

@@ -6,6 +6,7 @@
 #include <array>
 #include <cstdarg>
 #include <cstdio>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <unordered_set>
@@ -31,9 +32,22 @@ extern std::unordered_set<const bce_ctx*> g_live;
 
 // What the kernels of a captured plan hold by value (bce_plan_run): the context's device pointers and kernel choices
 struct CaptureSnapshot {
-    std::array<const void*, 6> ptrs{};
-    std::array<u32, 3> flags{};
+    std::array<const void*, 4> ptrs{};
+    std::array<u32, 4> flags{};   // the last one: the selected key set (0 for a plan with a key-set map: it does not follow the selection)
     bool operator==(const CaptureSnapshot& o) const { return ptrs == o.ptrs && flags == o.flags; }
+};
+
+// The key material of one client (include/bce_gpu.h, "key sets").  A context holds up to BCE_MAX_KEYSETS of them; everything
+// derived from the parameters alone (tables, fold decision, lazy bounds, pool) stays per context.  The three device buffers
+// are allocated once per set and never reallocated: the context's device table (bce_ctx::d_keysets) holds their addresses.
+struct KeySet {
+    DevBuf<char> d_bsk;          // u32 words (Q < 2^28), u64 words (is64) or doubles (fp64), in the kernels' layout
+    DevBuf<char> d_ksk;
+    DevBuf<int8_t> d_s8;         // the LWE secret as the device-side checks read it: int8[n padded to 64]
+    u64 bsk_polys = 0;
+    bool have_keys = false;
+    std::vector<int32_t> s, z;   // host secrets
+    uint8_t seed[32] = {0};      // key-generation seed (bce_keygen); zero after bce_import_keys
 };
 
 }  // namespace bce
@@ -59,17 +73,16 @@ struct bce_ctx {
     // device tables / keys
     DevBuf<uint2> d_twf;
     DevBuf<u32> d_fwd_mfma, d_psi, d_psi_r2, d_xcd_gate;
-    DevBuf<char> d_bsk;          // u32 words (Q < 2^28) or u64 words (is64)
     DevBuf<ulonglong2> d_tw64;
     DevBuf<double2> d_tw64d;      // (w, w / Q) for the double-precision formulation
     bool is64 = false;
     size_t wbytes = 4;
-    DevBuf<char> d_ksk;
-    u64 bsk_polys = 0;
-    bool have_keys = false;
-    // host secrets
-    std::vector<int32_t> s, z;
-    uint8_t seed[32] = {0};       // key-generation seed (bce_keygen); zero after bce_import_keys
+    // key sets: set 0 exists from creation; a call that takes no key-set map acts on the selected one
+    std::array<std::unique_ptr<bce::KeySet>, BCE_MAX_KEYSETS> keysets;
+    u32 selected = 0;             // mirrored in P.keyset_sel
+    DevBuf<bce::KeySetDev> d_keysets;   // [BCE_MAX_KEYSETS] what the kernels read (P.keysets); one allocation per context
+    bce::KeySet& keys() { return *keysets[selected]; }
+    const bce::KeySet& keys() const { return *keysets[selected]; }
     // Encryption randomness is independent of the key seed: drawn from OS entropy when the context is created,
     // consumed through a per-context counter that only moves forward, so no (a, e) pair is ever reused.
     // bce_set_encrypt_seed() switches to the deterministic, caller-indexed streams of the parity tests.
@@ -89,9 +102,8 @@ struct bce_ctx {
     static constexpr int kRing = 4;
     StagedUpload ring[kRing];       // descriptor lists of the launches in flight (stage_descs)
     int ring_pos = 0;
-    // verify mode on the device (bce_check_*): the LWE secret as int8[n padded to 64] (uploaded wherever `s` is set), the
-    // report block followed by the mismatch log, and the staging pair of bce_check_slots (slot list + expected bits)
-    DevBuf<int8_t> d_s8;            // allocated once per context, never reallocated: captured plans point to it
+    // verify mode on the device (bce_check_*): the report block followed by the mismatch log, and the staging pair of
+    // bce_check_slots (slot list + expected bits); the LWE secret it decrypts with belongs to the key set (KeySet::d_s8)
     DevBuf<char> d_check_mem;
     bce_check_report* d_check() const { return reinterpret_cast<bce_check_report*>(d_check_mem.get()); }
     bce_check_entry* d_check_log() const { return reinterpret_cast<bce_check_entry*>(d_check_mem.get() + sizeof(bce_check_report)); }
@@ -113,8 +125,9 @@ struct bce_ctx {
     int dag_pending = 0;
     uint64_t dag_last[7] = {0, 0, 0, 0, 0, 0, 0};
 
-    bce::CaptureSnapshot capture_snapshot() const {
-        return {{P.pool, P.bsk, P.bsk64, P.ksk, P.tw_f, P.psi_tab}, {P.variant, P.fuse_tail, P.fold}};
+    // keyed: for a plan created with a key-set map.  The keys themselves are found through P.keysets at replay.
+    bce::CaptureSnapshot capture_snapshot(bool keyed) const {
+        return {{P.pool, P.keysets, P.tw_f, P.psi_tab}, {P.variant, P.fuse_tail, P.fold, keyed ? 0u : selected}};
     }
 
     int fail(int code, const char* fmt, ...) {
@@ -137,7 +150,17 @@ struct bce_ctx {
 namespace bce {
 
 inline int need_keys(bce_ctx* c) {
-    return c->have_keys ? BCE_OK : c->fail(BCE_ERR_NO_KEYS, "bce_keygen / bce_import_keys has not been called");
+    if (c->keys().have_keys) return BCE_OK;
+    return c->selected ? c->fail(BCE_ERR_NO_KEYS, "key set %u has no keys: bce_keygen / bce_import_keys has not been called under its selection", c->selected)
+                       : c->fail(BCE_ERR_NO_KEYS, "bce_keygen / bce_import_keys has not been called");
+}
+// a key-set map: every id names an existing set with keys (`who` names the call in the message)
+inline int need_keys_of_map(bce_ctx* c, const char* who, const u32* map, u32 instances) {
+    for (u32 k = 0; k < instances; ++k) {
+        if (map[k] >= BCE_MAX_KEYSETS || !c->keysets[map[k]]) return c->fail(BCE_ERR_ARG, "%s: instance %u names key set %u, which does not exist", who, k, map[k]);
+        if (!c->keysets[map[k]]->have_keys) return c->fail(BCE_ERR_NO_KEYS, "%s: key set %u (instance %u) has no keys", who, map[k], k);
+    }
+    return BCE_OK;
 }
 
 // device copy of a host vector in a buffer that is still empty (one element at least)
@@ -155,7 +178,7 @@ int drain_if_long(bce_ctx* c);
 int sync_stream(bce_ctx* c);
 int expected_are_messages(bce_ctx* c, const char* who, const uint8_t* expect, size_t count);
 int launch_bootstraps(bce_ctx* c, const bce_gate_desc* dd, u32 n, u32 instances, u32 slot_stride, void* d_acc, u32* d_lweN, u32* d_ks,
-                      bool timed, bool* fused_out, bool pairs, u64* d_partial = nullptr);
+                      bool timed, bool* fused_out, bool pairs, u64* d_partial = nullptr, const u32* d_map = nullptr);
 
 // Schedules.  bce_plan_destroy / bce_dag_destroy, and the deleter of a schedule under construction: nothing to free and
 // nothing to touch when the context no longer exists (it took its schedules along) or does not own `s`
@@ -178,6 +201,7 @@ struct ScheduleDeleter {
 };
 // for bce_ctx_destroy, which has synchronised and emptied the context's sets (engine_plan.cpp, engine_dag.cpp)
 void delete_leftover(bce_plan* p);
+bool plan_names_keyset(bce_ctx* c, u32 id);   // engine_plan.cpp: a live plan of c was created with a map that names set id
 void delete_leftover(bce_dag* g);
 
 }  // namespace bce

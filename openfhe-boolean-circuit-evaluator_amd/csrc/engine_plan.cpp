@@ -15,7 +15,9 @@ struct bce_plan {
     u32 instances = 0, slot_stride = 0, slot_base = 0;
     u32 max_step = 0;                          // descriptors of the largest step
     u64 boots_per_run = 0;
-    DevBuf<bce_gate_desc> d_descs;             // all steps, resident
+    DevBuf<bce_gate_desc> d_descs;             // all steps, resident; a keyed plan's map sits behind them in the same block
+    std::vector<u32> keymap;                   // bce_plan_create_keyed: the key set of every instance (empty: the plan follows the selection)
+    const u32* d_map = nullptr;                // its device copy inside d_descs, or null
     // captured form (bce_plan_run): its own accumulator / partial-sum scratch, so that nothing the graph points to is ever
     // re-allocated by other calls on the context.  d_descs, d_acc, d_partial, d_chk_slots and `expect` never move while
     // `exec` exists: each is allocated once, the check lists only after bce_plan_set_checks dropped the capture.
@@ -45,6 +47,12 @@ struct bce_plan {
 };
 
 void bce::delete_leftover(bce_plan* p) { delete p; }
+bool bce::plan_names_keyset(bce_ctx* c, u32 id) {
+    std::lock_guard<std::mutex> lk(g_live_mu);
+    for (const bce_plan* p : c->plans)
+        if (std::find(p->keymap.begin(), p->keymap.end(), id) != p->keymap.end()) return true;
+    return false;
+}
 
 namespace {
 void plan_free_checks(bce_plan* p) {
@@ -56,7 +64,7 @@ void plan_free_checks(bce_plan* p) {
 // the checks of plan step s, after its kernels (no allocation, no synchronisation: also runs under stream capture)
 int plan_check_step(bce_ctx* c, const bce_plan* p, size_t s) {
     if (!p->chk_total || !p->chk_cnt[s]) return BCE_OK;
-    HIP_TRY(c, launch_lwe_check(c->P, c->d_s8.get(), p->d_chk_slots.get() + p->chk_off[s], p->d_expect() + p->chk_off[s], p->chk_cnt[s], p->chk_total,
+    HIP_TRY(c, launch_lwe_check(c->P, p->d_chk_slots.get() + p->chk_off[s], p->d_expect() + p->chk_off[s], p->chk_cnt[s], p->chk_total,
                                 p->instances, p->slot_stride, p->chk_repair, (u32)s, c->d_check(), c->d_check_log(), c->stream));
     return BCE_OK;
 }
@@ -65,6 +73,10 @@ int checked_slots_in_pool(bce_ctx* c, const char* who, const uint32_t* slots, u6
     for (u64 i = 0; i < count; ++i)
         if (slots[i] + span >= c->pool_slots) return c->fail(BCE_ERR_POOL, "%s: check %llu: slot %llu outside the pool (%u slots)", who, (unsigned long long)i, (unsigned long long)(slots[i] + span), c->pool_slots);
     return BCE_OK;
+}
+// a plan with a map needs the keys of the sets it names (they exist: bce_keyset_drop refuses them), any other the selected set's
+int plan_need_keys(bce_ctx* c, const bce_plan* p, const char* who) {
+    return p->keymap.empty() ? need_keys(c) : need_keys_of_map(c, who, p->keymap.data(), p->instances);
 }
 int plan_checks_ready(bce_ctx* c, const bce_plan* p, const char* who) {
     if (p->chk_total && !p->expected_set) return c->fail(BCE_ERR_STATE, "%s: the plan has checks but bce_plan_set_expected has not been called", who);
@@ -78,21 +90,28 @@ void bce_plan_destroy(bce_ctx* c, bce_plan* p) { destroy_schedule(c, p); }
 
 int bce_plan_create(bce_ctx* c, uint32_t n_steps, const uint32_t* step_sizes, const bce_gate_desc* descs, uint32_t instances,
                     uint32_t slot_stride, uint32_t slot_base, bce_plan** out) {
+    return bce_plan_create_keyed(c, n_steps, step_sizes, descs, instances, slot_stride, slot_base, nullptr, out);
+}
+
+int bce_plan_create_keyed(bce_ctx* c, uint32_t n_steps, const uint32_t* step_sizes, const bce_gate_desc* descs, uint32_t instances,
+                          uint32_t slot_stride, uint32_t slot_base, const uint32_t* keyset_of_instance, bce_plan** out) {
     if (!c || !out) return BCE_ERR_ARG;
     *out = nullptr;
-    if (!step_sizes || !descs || n_steps == 0 || instances == 0) return c->fail(BCE_ERR_ARG, "bce_plan_create: empty schedule");
-    if (const int rc = need_keys(c)) return rc;
+    const u32* const map = keyset_of_instance;
+    const char* const who = map ? "bce_plan_create_keyed" : "bce_plan_create";   // the entry point that was called, for the messages
+    if (!step_sizes || !descs || n_steps == 0 || instances == 0) return c->fail(BCE_ERR_ARG, "%s: empty schedule", who);
+    if (const int rc = map ? need_keys_of_map(c, who, map, instances) : need_keys(c)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     std::unique_ptr<bce_plan, ScheduleDeleter> p(new bce_plan, ScheduleDeleter{c});
     { std::lock_guard<std::mutex> lk(g_live_mu); c->plans.insert(p.get()); }
     p->instances = instances; p->slot_stride = slot_stride; p->slot_base = slot_base;
     u64 total = 0;
     for (u32 s = 0; s < n_steps; ++s) {
-        if (step_sizes[s] == 0) return c->fail(BCE_ERR_ARG, "bce_plan_create: step %u is empty", s);
+        if (step_sizes[s] == 0) return c->fail(BCE_ERR_ARG, "%s: step %u is empty", who, s);
         p->off.push_back((u32)total); p->cnt.push_back(step_sizes[s]);
         p->max_step = std::max(p->max_step, step_sizes[s]);
         total += step_sizes[s];
-        if (total >= (1ull << 31)) return c->fail(BCE_ERR_ARG, "bce_plan_create: too many descriptors");
+        if (total >= (1ull << 31)) return c->fail(BCE_ERR_ARG, "%s: too many descriptors", who);
     }
     std::vector<bce_gate_desc> d(descs, descs + total);
     const u64 span = (u64)slot_base + (u64)(instances - 1) * slot_stride;
@@ -101,17 +120,26 @@ int bce_plan_create(bce_ctx* c, uint32_t n_steps, const uint32_t* step_sizes, co
     for (u64 i = 0; i < total; ++i) {
         bce_gate_desc& g = d[i];
         const DescKind k = desc_kind(g.op);
-        if (!k.boot()) return c->fail(BCE_ERR_ARG, "bce_plan_create: descriptor %llu is not a bootstrapped gate (op %u)", (unsigned long long)i, g.op);
+        if (!k.boot()) return c->fail(BCE_ERR_ARG, "%s: descriptor %llu is not a bootstrapped gate (op %u)", who, (unsigned long long)i, g.op);
         if (k.pair()) {
             while (step + 1 < n_steps && i >= (u64)p->off[step + 1]) ++step;
             p->pairs[step] = 1;
         }
         const u64 hi = top_slot(g, k);
-        if (hi + span >= c->pool_slots) return c->fail(BCE_ERR_POOL, "bce_plan_create: descriptor %llu: slot %llu outside the pool (%u slots)", (unsigned long long)i, (unsigned long long)(hi + span), c->pool_slots);
+        if (hi + span >= c->pool_slots) return c->fail(BCE_ERR_POOL, "%s: descriptor %llu: slot %llu outside the pool (%u slots)", who, (unsigned long long)i, (unsigned long long)(hi + span), c->pool_slots);
         g.in0 += slot_base; g.in1 += slot_base; g.out += slot_base;
     }
     p->boots_per_run = total * instances;
+    if (map) {   // the map rides behind the descriptors, in whole descriptor-sized words of the same resident block
+        d.resize(total + ((size_t)instances * sizeof(u32) + sizeof(bce_gate_desc) - 1) / sizeof(bce_gate_desc), bce_gate_desc{});
+        std::memcpy(static_cast<void*>(d.data() + total), map, (size_t)instances * sizeof(u32));
+    }
     HIP_TRY(c, upload_vector(p->d_descs, d));
+    if (map) {   // named only now: bce_keyset_drop looks at the plans that exist
+        p->d_map = reinterpret_cast<const u32*>(p->d_descs.get() + total);
+        std::lock_guard<std::mutex> lk(g_live_mu);
+        p->keymap.assign(map, map + instances);
+    }
     *out = p.release();
     return BCE_OK;
 }
@@ -119,12 +147,12 @@ int bce_plan_create(bce_ctx* c, uint32_t n_steps, const uint32_t* step_sizes, co
 int bce_plan_run_step(bce_ctx* c, bce_plan* p, uint32_t step) {
     if (!c || !p) return BCE_ERR_ARG;
     if (step >= p->cnt.size()) return c->fail(BCE_ERR_ARG, "bce_plan_run_step: step %u of %zu", step, p->cnt.size());
-    if (const int rc = need_keys(c)) return rc;
+    if (const int rc = plan_need_keys(c, p, "bce_plan_run_step")) return rc;
     if (const int rc = plan_checks_ready(c, p, "bce_plan_run_step")) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const int rc = ensure_acc(c, (size_t)p->cnt[step] * p->instances);
     if (rc) return rc;
-    const int rc2 = launch_bootstraps(c, p->d_descs.get() + p->off[step], p->cnt[step], p->instances, p->slot_stride, c->d_acc.get(), nullptr, nullptr, true, nullptr, p->pairs[step] != 0);
+    const int rc2 = launch_bootstraps(c, p->d_descs.get() + p->off[step], p->cnt[step], p->instances, p->slot_stride, c->d_acc.get(), nullptr, nullptr, true, nullptr, p->pairs[step] != 0, nullptr, p->d_map);
     if (rc2) return rc2;
     if (const int rc3 = plan_check_step(c, p, step)) return rc3;
     return drain_if_long(c);
@@ -132,11 +160,12 @@ int bce_plan_run_step(bce_ctx* c, bce_plan* p, uint32_t step) {
 
 int bce_plan_run(bce_ctx* c, bce_plan* p) {
     if (!c || !p) return BCE_ERR_ARG;
-    if (const int rc = need_keys(c)) return rc;
+    if (const int rc = plan_need_keys(c, p, "bce_plan_run")) return rc;
     if (const int rc = plan_checks_ready(c, p, "bce_plan_run")) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (p->exec && !(c->capture_snapshot() == p->captured)) {
-        // the pool grew (bce_pool_reserve) or keys were re-imported since the capture: the graph's kernel arguments are stale
+    if (p->exec && !(c->capture_snapshot(p->d_map != nullptr) == p->captured)) {
+        // the pool grew (bce_pool_reserve) or, for a plan without a map, another key set was selected since the capture: the
+        // graph's kernel arguments are stale.  (The keys themselves are read through the context's table at every replay.)
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         p->drop_capture();
     }
@@ -152,7 +181,7 @@ int bce_plan_run(bce_ctx* c, bce_plan* p) {
         u64 fused = 0;
         for (size_t s = 0; s < p->cnt.size() && rc == BCE_OK; ++s) {
             bool f = false;
-            rc = launch_bootstraps(c, p->d_descs.get() + p->off[s], p->cnt[s], p->instances, p->slot_stride, p->d_acc.get(), nullptr, nullptr, false, &f, p->pairs[s] != 0, p->d_partial.get());
+            rc = launch_bootstraps(c, p->d_descs.get() + p->off[s], p->cnt[s], p->instances, p->slot_stride, p->d_acc.get(), nullptr, nullptr, false, &f, p->pairs[s] != 0, p->d_partial.get(), p->d_map);
             fused += f ? 1 : 0;
             if (rc == BCE_OK) rc = plan_check_step(c, p, s);
         }
@@ -162,7 +191,7 @@ int bce_plan_run(bce_ctx* c, bce_plan* p) {
         if (e != hipSuccess || !g) return c->fail(BCE_ERR_HIP, "bce_plan_run: stream capture failed: %s", hipGetErrorString(e));
         p->graph = g;
         p->fused_launches = fused;
-        p->captured = c->capture_snapshot();
+        p->captured = c->capture_snapshot(p->d_map != nullptr);
         const hipError_t e2 = hipGraphInstantiate(&p->exec, p->graph, nullptr, nullptr, 0);
         if (e2 != hipSuccess) { p->exec = nullptr; return c->fail(BCE_ERR_HIP, "bce_plan_run: hipGraphInstantiate: %s", hipGetErrorString(e2)); }
     }
@@ -199,13 +228,14 @@ int bce_check_slots(bce_ctx* c, uint32_t count, const uint32_t* slots, const uin
     std::memcpy(static_cast<char*>(st.host()) + slot_bytes, expect, items);
     HIP_TRY(c, st.send(bytes, c->stream));
     const char* dev = static_cast<const char*>(st.device());
-    HIP_TRY(c, launch_lwe_check(c->P, c->d_s8.get(), reinterpret_cast<const u32*>(dev), reinterpret_cast<const uint8_t*>(dev + slot_bytes),
+    HIP_TRY(c, launch_lwe_check(c->P, reinterpret_cast<const u32*>(dev), reinterpret_cast<const uint8_t*>(dev + slot_bytes),
                                 count, count, instances, slot_stride, repair, tag, c->d_check(), c->d_check_log(), c->stream));
     return BCE_OK;
 }
 
 int bce_plan_set_checks(bce_ctx* c, bce_plan* p, const uint32_t* check_sizes, const uint32_t* slots, int repair) {
     if (!c || !p) return BCE_ERR_ARG;
+    if (!p->keymap.empty()) return c->fail(BCE_ERR_UNSUPPORTED, "bce_plan_set_checks on a plan created with a key-set map (bce_plan_create_keyed): device-side checks run under one key set");
     if (const int rc = need_keys(c)) return rc;
     const size_t n_steps = p->cnt.size();
     u64 total = 0;

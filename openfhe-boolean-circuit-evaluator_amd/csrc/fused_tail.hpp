@@ -99,13 +99,13 @@ __device__ __forceinline__ void tail_row_numbers(const PT& P, const CW* coef, u3
 
 // Stage 2: red[slice][group * VW + e] = sum over the slice's rows of the LR in rowidx of K[row][group * VW + e].  U rows in
 // flight per lane; u32 running sums are folded into the u64 totals every ks_chunk rows (ks_chunk * qKS <= 2^32: no wrap).
+// ksk: the key-switching key of the bootstrap's key set (key_set, gate_front.hpp).
 template <typename KT, u32 U, typename PT>
-__device__ __forceinline__ void tail_gather_rows(const PT& P, const TailGeom& tg, u32 wave, u32 lane, const u32* rowidx, u32 LR,
-                                                 u64* red) {
+__device__ __forceinline__ void tail_gather_rows(const PT& P, const KT* __restrict__ ksk, const TailGeom& tg, u32 wave, u32 lane,
+                                                 const u32* rowidx, u32 LR, u64* red) {
     constexpr u32 VW = 16 / sizeof(KT);
     const u32 Gv = tg.Gv, SL = tg.SL, slice = wave / tg.RW, group = (wave - slice * tg.RW) * 64 + lane;
     if (slice >= SL || group >= Gv) return;
-    const KT* __restrict__ ksk = reinterpret_cast<const KT*>(P.ksk);
     auto load_row = [&](u32 r) {
         const u32 row = __builtin_amdgcn_readfirstlane(rowidx[r]);
         return reinterpret_cast<const uint4*>(ksk + (size_t)row * P.ksk_stride)[group];
@@ -180,14 +180,14 @@ __device__ __forceinline__ u32 tail_finish_word(const PT& P, u64 sum, u32 k, con
 #define BCE_FUSED_U 8   // rows in flight per lane (tools/fused_u_sweep.sh)
 #endif
 template <typename KT, u32 T, typename CW, typename PT>
-__device__ __forceinline__ void fused_tail(const PT& P, const CW* coef, u32* rowidx, u64* red, u32* out, u32 boot,
+__device__ __forceinline__ void fused_tail(const PT& P, const KT* __restrict__ ksk, const CW* coef, u32* rowidx, u64* red, u32* out, u32 boot,
                                            u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks, u64 off, u32 rot = 0) {
     const u32 N = P.N, n = P.n, tid = threadIdx.x, lane = tid & 63;
     const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     tail_row_numbers(P, coef, rot, 0u, N, tid, T, rowidx, dbg_lweN, boot);
     __syncthreads();
     const TailGeom tg(n, sizeof(KT) == 2, T);
-    tail_gather_rows<KT, BCE_FUSED_U>(P, tg, wave, lane, rowidx, N * P.dKS, red);
+    tail_gather_rows<KT, BCE_FUSED_U>(P, ksk, tg, wave, lane, rowidx, N * P.dKS, red);
     __syncthreads();
     for (u32 k = tid; k <= n; k += T)
         out[k] = tail_finish_word(P, tail_slice_sum(tg, red, k), k, coef, rot, off, dbg_lweN, dbg_ks, boot);
@@ -199,16 +199,19 @@ __device__ __forceinline__ void fused_tail(const PT& P, const CW* coef, u32* row
 // are stored before the worker's drain / barrier / release (dag_worker); its debug pointers are null and the row index
 // stays `boot`.
 template <u32 T, bool PERSIST, typename CW, typename PT>
-__device__ __forceinline__ void fused_tail_outputs(const PT& P, const bce_gate_desc& g, u32 soff, const CW* coef, u32* rowidx,
+__device__ __forceinline__ void fused_tail_outputs(const PT& P, const bce_gate_desc& g, u32 inst, u32 soff, const CW* coef, u32* rowidx,
                                                    u64* red, u32 boot, u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks) {
     u32* outp = P.pool + (size_t)(g.out + soff) * P.pool_stride;
     const u64 off = tail_offset<CW>(P, g.op);
-    if (P.ksk_u16) fused_tail<uint16_t, T>(P, coef, rowidx, red, outp, boot, dbg_lweN, dbg_ks, off);
-    else fused_tail<u32, T>(P, coef, rowidx, red, outp, boot, dbg_lweN, dbg_ks, off);
+    const void* const ksk = key_set(P, inst).ksk;   // the instance's key set
+    const uint16_t* const k16 = static_cast<const uint16_t*>(ksk);
+    const u32* const k32 = static_cast<const u32*>(ksk);
+    if (P.ksk_u16) fused_tail<uint16_t, T>(P, k16, coef, rowidx, red, outp, boot, dbg_lweN, dbg_ks, off);
+    else fused_tail<u32, T>(P, k32, coef, rowidx, red, outp, boot, dbg_lweN, dbg_ks, off);
     if (pair_second(g.op)) {
         __syncthreads();
         const u32 e = pair_rotation(P, g.op), row = PERSIST ? boot : boot + gridDim.x;
-        if (P.ksk_u16) fused_tail<uint16_t, T>(P, coef, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, off, e);
-        else fused_tail<u32, T>(P, coef, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, off, e);
+        if (P.ksk_u16) fused_tail<uint16_t, T>(P, k16, coef, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, off, e);
+        else fused_tail<u32, T>(P, k32, coef, rowidx, red, outp + P.pool_stride, row, dbg_lweN, dbg_ks, off, e);
     }
 }

@@ -7,6 +7,24 @@
 // word j of a polynomial in LDS: four words of padding after every 64 (bank-conflict-free strided access)
 __device__ __forceinline__ u32 phys(u32 j) { return j + ((j >> 6) << 2); }
 
+// ---- key sets (include/bce_gpu.h, "key sets") ---------------------------------------------------------------------------
+// The one way a body finds its keys: instance `inst` of a launch runs under set map[inst] when the launch carries a map, else
+// under the selected set.  inst is uniform per workgroup; the map and the context's table are read through the constant
+// address space (nothing writes them while a kernel runs), so the id and the three bases are scalar loads into SGPRs.
+// a pointer into device memory that no kernel writes while this one runs, as a constant-address-space pointer (uniform
+// loads through it are scalar).  The one cast; as_constant (dag_sched.hpp) adds what the persistent loop needs on top of it.
+template <typename C, typename S>
+__device__ __forceinline__ C* to_constant(const S* p) { return (C*)(uintptr_t)p; }
+typedef const __attribute__((address_space(4))) KeySetDev ConstKeySetDev;
+typedef const __attribute__((address_space(4))) u32 ConstMapWord;
+template <typename PT>
+__device__ __forceinline__ ConstKeySetDev& key_set(const PT& P, u32 inst) {
+    const u32 k = __builtin_amdgcn_readfirstlane(inst);
+    ConstMapWord* const map = to_constant<ConstMapWord>(P.keyset_map);
+    const u32 id = map ? map[k] : P.keyset_sel;
+    return to_constant<ConstKeySetDev>(P.keysets)[id];
+}
+
 // gate constant q1 of BootstrapGateCore (OR 5q/8, AND 7q/8, NOR q/8, NAND 3q/8)
 __device__ __forceinline__ u32 gate_const(u32 op, u32 q) {
     const u32 e = q >> 3;

@@ -853,7 +853,8 @@ __global__ __launch_bounds__(128 * DG, (OCC * 2 * DG + 3) / 4) void k_blind_rota
     const u32 Q = P.Q, q = P.q, n = P.n;
 
     const bce_gate_desc g = descs[blockIdx.x % n_desc];
-    const u32 soff = (blockIdx.x / n_desc) * slot_stride;
+    const u32 inst = blockIdx.x / n_desc, soff = inst * slot_stride;
+    const u32* const bsk = static_cast<const u32*>(key_set(P, inst).bsk);   // this instance's key set
 
     bootstrap_prologue<LOGN, LAZY, T>(P, g, soff, twf, acc, av, tid, lane, wave);
 
@@ -861,7 +862,7 @@ __global__ __launch_bounds__(128 * DG, (OCC * 2 * DG + 3) / 4) void k_blind_rota
     constexpr u32 rgsw = R * 2 * N;  // words per RGSW ciphertext
     // GINX key = n * 2 * rgsw words < 4 GiB: one buffer resource covers it (raw, no stride, bounds-checked)
     const __amdgpu_buffer_rsrc_t rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<u32*>(P.bsk), 0, AP ? 0x7FFFFFFF : (int)(n * 2 * rgsw * 4), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<u32*>(bsk), 0, AP ? 0x7FFFFFFF : (int)(n * 2 * rgsw * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t psi_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32*>(P.psi_tab), 0, N * 4, 0x00020000);
     // GINX: one step per LWE coefficient; AP: one step per (coefficient, base-baseR digit)
     const u32 nsteps = AP ? n * P.dR : n;
@@ -872,13 +873,13 @@ __global__ __launch_bounds__(128 * DG, (OCC * 2 * DG + 3) / 4) void k_blind_rota
         if constexpr (!AP) {
             ap = ginx_exponent(P, q, av[step]);
             if (ap == 0) continue;
-            bk = P.bsk + (size_t)step * 2 * rgsw;
+            bk = bsk + (size_t)step * 2 * rgsw;
             rowb = step * (2 * rgsw * 4);
         } else {
             const u32 i = step / P.dR, k = step - i * P.dR;
             const u32 a0 = ap_digit(P, q, av[i], k);
             if (a0 == 0) continue;
-            bk = P.bsk + (((size_t)i * P.baseR + a0) * P.dR + k) * rgsw;
+            bk = bsk + (((size_t)i * P.baseR + a0) * P.dR + k) * rgsw;
         }
         // (1) two waves: INTT of acc[c], SignedDigitDecompose -> dct[2l + c] (coefficient form)
         if (wave < 2) {
@@ -1231,11 +1232,11 @@ struct LatLds {
     static constexpr size_t tail_bytes = (xbm - dct) * sizeof(u32);   // digit rows + exchange buffers: dead when the fused tail runs
 };
 // lat_bootstrap: ONE gate bootstrap by the calling workgroup (all 512 threads), the body shared by the per-frontier
-// kernel k_blind_rotate_lat and the dependency-driven persistent kernel k_bootstrap_dag.  g: the gate, soff: slot offset
-// of the instance, boot: index of this bootstrap in acc_out / the debug buffers (acc_out may be null).
+// kernel k_blind_rotate_lat and the dependency-driven persistent kernel k_bootstrap_dag.  g: the gate, inst: the instance
+// (its key set: key_set, gate_front.hpp), soff: slot offset of the instance, boot: index of this bootstrap in acc_out / the debug buffers (acc_out may be null).
 // V: a LatVariant; PERSIST: the caller is the persistent kernel's loop.
 template <class V, bool PERSIST, typename PT>
-__device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g, const u32 soff, const u32 boot, u32* smem,
+__device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g, const u32 inst, const u32 soff, const u32 boot, u32* smem,
                                               u32* __restrict__ acc_out, u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks) {
     constexpr int LOGN = V::LOGN, DG = V::DG, WPS = V::WPS;
     constexpr bool AP = V::AP, FUSE = V::FUSE, FOLD = V::FOLD, QUNITS = V::QUNITS, MFMA = V::MFMA;
@@ -1285,8 +1286,8 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
     constexpr u32 rgsw = R * 2 * N;
     // GINX key: n * 2 RGSW ciphertexts; AP key: n * baseR * dR of them, below 2^31 bytes: kernel_class grants this family to
     // an AP context on that condition (kSplitApKeyBytes), since rowb below is 32 bits wide and is range-checked with the rest
-    const __amdgpu_buffer_rsrc_t rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<u32*>(P.bsk), 0, AP ? 0x7FFFFFFF : (int)(n * 2 * rgsw * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<void*>(key_set(P, inst).bsk), 0, AP ? 0x7FFFFFFF : (int)(n * 2 * rgsw * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t psi_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32*>(P.psi_tab_r2), 0, N * 4, 0x00020000);
     // digit extraction constants (see the throughput kernel)
     const u32 gb = P.gBits, Qh = Q >> 1;
@@ -1480,7 +1481,7 @@ __device__ __forceinline__ void lat_bootstrap(const PT& P, const bce_gate_desc g
         if constexpr (WPS >= 4) __builtin_amdgcn_s_setprio(0);
         __syncthreads();
         // rowidx and the partial sums live in the digit rows + exchange buffers (LatLds::tail_bytes = 54 KiB, all dead now)
-        fused_tail_outputs<T, PERSIST>(P, g, soff, acc, dct, reinterpret_cast<u64*>(dct + ((N * P.dKS + 3) & ~3u)), boot, dbg_lweN, dbg_ks);
+        fused_tail_outputs<T, PERSIST>(P, g, inst, soff, acc, dct, reinterpret_cast<u64*>(dct + ((N * P.dKS + 3) & ~3u)), boot, dbg_lweN, dbg_ks);
     }
 }
 
@@ -1489,7 +1490,8 @@ __global__ __launch_bounds__(V::T, V::WPS) void k_blind_rotate_lat(DevParams P, 
                                                                    u32 slot_stride, u32* __restrict__ acc_out,
                                                                    u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks) {
     extern __shared__ __align__(16) u32 smem[];
-    lat_bootstrap<V, false>(P, descs[blockIdx.x % n_desc], (blockIdx.x / n_desc) * slot_stride, blockIdx.x, smem, acc_out, dbg_lweN, dbg_ks);
+    const u32 inst = blockIdx.x / n_desc;
+    lat_bootstrap<V, false>(P, descs[blockIdx.x % n_desc], inst, inst * slot_stride, blockIdx.x, smem, acc_out, dbg_lweN, dbg_ks);
 }
 
 // the fused tail's scratch inside the digit rows + exchange buffers of lat_bootstrap (512 threads)
@@ -1649,7 +1651,7 @@ __global__ __launch_bounds__(V::T, V::WPS) void k_bootstrap_dag(const DevParams*
     extern __shared__ __align__(16) u32 smem[];
     // the worker's mailbox sits in front of the LDS layout of lat_bootstrap
     dag_worker(Pp, Dp, smem, [&](ConstDagParams& D, u32 t, u32 k) {
-        lat_bootstrap<V, true>(*as_constant<ConstDevParams>(Pp), D.tasks[t], D.slot_base + k * D.slot_stride, 0, smem + kDagMailboxWords,
+        lat_bootstrap<V, true>(*as_constant<ConstDevParams>(Pp), D.tasks[t], k, D.slot_base + k * D.slot_stride, 0, smem + kDagMailboxWords,
                                nullptr, nullptr, nullptr);
     });
 }
@@ -1764,9 +1766,9 @@ __global__ __launch_bounds__(256) void k_tail_gather(DevParams P, u32 S, const A
     tail_row_numbers(P, acc_in + (size_t)boot * 2 * N, rot, s * ni, ni, tid, 256u, rowidx, dbg_lweN, dbg_row);
     __syncthreads();
     const TailGeom tg(n, VW == 8, 256);                   // one group per lane of up to 4 waves
-    tail_gather_rows<KT, 8>(P, tg, wave, lane, rowidx, LR, red);
+    const KT* __restrict__ ksk = static_cast<const KT*>(key_set(P, boot / n_desc).ksk);   // this instance's key set
+    tail_gather_rows<KT, 8>(P, ksk, tg, wave, lane, rowidx, LR, red);
     __syncthreads();
-    const KT* __restrict__ ksk = reinterpret_cast<const KT*>(P.ksk);
     const u32 Gv = tg.Gv;
     u64* out = partial + ((size_t)boot * S + s) * (n + 1);
     for (u32 k = tid; k < Gv * VW && k <= n; k += 256) out[k] = tail_slice_sum(tg, red, k);
@@ -1890,7 +1892,7 @@ hipError_t launch_pool_pack(const DevParams& P, const bce_gate_desc* d, u32 coun
 // wave; the report is read by the host after the stream has drained, nothing in this launch reads it.
 // No LDS, no barrier.  Repair writes the TRIVIAL ciphertext (0, ..., 0, expect q/4) with vector stores.
 __global__ __launch_bounds__(64 * kCheckWaves) void k_lwe_check(u32* __restrict__ pool, u32 pool_stride, u32 n, u32 q,
-                                                               const int8_t* __restrict__ s, const u32* __restrict__ slots,
+                                                               KeySetRef K, const u32* __restrict__ slots,
                                                                const uint8_t* __restrict__ expect, u32 count, u32 expect_stride,
                                                                u32 items, u32 slot_stride, int repair, u32 tag,
                                                                bce_check_report* __restrict__ rep, bce_check_entry* __restrict__ log) {
@@ -1903,6 +1905,7 @@ __global__ __launch_bounds__(64 * kCheckWaves) void k_lwe_check(u32* __restrict_
         const u32 slot = slots[index] + inst * slot_stride;
         const u32 want = expect[(size_t)inst * expect_stride + index];
         u32* row = pool + (size_t)slot * pool_stride;
+        const int8_t* const s = key_set(K, inst).s8;   // the instance's key set (gate_front.hpp)
         const LweRowCheck r = lwe_row_check<false>(row, s, n, q, want, lane);   // dag_sched.hpp: shared with the dataflow kernel
         const u32 got = r.got;
         const int err = r.err;
@@ -1939,14 +1942,15 @@ __global__ __launch_bounds__(64 * kCheckWaves) void k_lwe_check(u32* __restrict_
     }
 }
 
-hipError_t launch_lwe_check(const DevParams& P, const int8_t* s, const u32* d_slots, const uint8_t* d_expect, u32 count,
+hipError_t launch_lwe_check(const DevParams& P, const u32* d_slots, const uint8_t* d_expect, u32 count,
                             u32 expect_stride, u32 instances, u32 slot_stride, int repair, u32 tag, bce_check_report* d_report,
                             bce_check_entry* d_log, hipStream_t stream) {
     const u64 items = (u64)count * instances;
     if (items == 0) return hipSuccess;
     if (items > (1ull << 31)) return hipErrorInvalidValue;   // the item counter of a wave is 32 bits wide and steps past `items`
     const u32 blocks = (u32)std::min<u64>((items + kCheckWaves - 1) / kCheckWaves, 4096);
-    hipLaunchKernelGGL(k_lwe_check, dim3(blocks), dim3(64 * kCheckWaves), 0, stream, P.pool, P.pool_stride, P.n, P.q, s, d_slots,
+    hipLaunchKernelGGL(k_lwe_check, dim3(blocks), dim3(64 * kCheckWaves), 0, stream, P.pool, P.pool_stride, P.n, P.q,
+                       KeySetRef{P.keysets, P.keyset_sel}, d_slots,
                        d_expect, count, expect_stride, (u32)items, slot_stride, repair, tag, d_report, d_log);
     return hipGetLastError();
 }

@@ -14,6 +14,21 @@ namespace bce {
 using u32 = uint32_t;
 using u64 = uint64_t;
 
+// The keys of one key set as the kernels read them: one entry of the context's device table (all null for a free id).
+struct KeySetDev {
+    const void* bsk;    // EVALUATION domain, GINX [n][2][R][2][N]; AP [n][baseR][dR][R][2][N]; u32 words, u64 words (is64) or doubles (fp64)
+    const void* ksk;    // [N][baseKS][dKS][ksk_stride]
+    const int8_t* s8;   // the LWE secret as the device-side checks read it: int8[n], zero-padded to a multiple of 64
+};
+
+// What key_set() reads, for kernels that take no DevParams (k_lwe_check): the table and the selected set.  Checks never
+// run with a key-set map (bce_plan_set_checks refuses a keyed plan), so the map is null by type.
+struct KeySetRef {
+    const KeySetDev* keysets;
+    u32 keyset_sel;
+    static constexpr const u32* keyset_map = nullptr;
+};
+
 // Everything a kernel needs, passed by value (lives in SGPRs / kernarg).
 struct DevParams {
     u32 n, N, logN;
@@ -62,7 +77,6 @@ struct DevParams {
     const u32* psi_tab_r2;  // [N] psi^e * R^2 mod Q
     u32 qinv_neg;           // -Q^-1 mod 2^32
     u32 r2_off;             // Q - (R^2 mod Q): psi^e R^2 + r2_off = (psi^e - 1) R^2 mod Q, lazily in [0, 2Q)
-    const u32* bsk;     // EVALUATION domain, GINX [n][2][R][2][N]; AP [n][baseR][dR][R][2][N]
     // ---- 64-bit ring modulus path (kernels64.hip), used when is64 != 0 (Q >= 2^28) ----
     u32 is64;
     u64 Q64, Q8p1_64;
@@ -70,14 +84,12 @@ struct DevParams {
     u64 c64;            // 2^64 mod Q
     u64 Ninv64, Ninv64_s;
     const ulonglong2* tw64;  // [N] (psi^brv(i), floor(. * 2^64 / Q))
-    const u64* bsk64;
     // double-precision formulation of the 64-bit path (kernels64.hip, namespace wd), used when fp64 != 0 (Q < 2^39):
-    // the key words at bsk64 are then IEEE doubles
+    // the bootstrapping-key words of a key set are then IEEE doubles
     u32 fp64;
     double Qd, invQd;          // Q, 1/Q
     double Ninvd, Ninvd_q;     // N^-1 mod Q and N^-1 / Q
     const double2* tw64d;      // [N] (psi^brv(i), psi^brv(i) / Q)
-    const void* ksk;    // [N][baseKS][dKS][ksk_stride]
     u32* pool;          // [slots][pool_stride]
     u32 pool_stride;
     // ---- matrix-pipe forward stages of the quarter units (at the end: the other kernels' argument layout is unchanged) ----
@@ -86,6 +98,10 @@ struct DevParams {
                            // ntt_forward_quarter3<true>; tables and conditions: fwd_mfma.hpp; BCE_FWD_MFMA=0 keeps the quarter-unit body)
     u32 w14, w14s;         // 2^14 mod Q and its Shoup companion (recombination of the limb products)
     const u32* fwd_mfma_tab;   // [4 quarters][4 tiles][64 lanes][4 words]: A operands, or null
+    // ---- key sets: where a workgroup finds its keys (gate_front.hpp, key_set) ----
+    const KeySetDev* keysets;  // [BCE_MAX_KEYSETS], one fixed table per context (captured graphs point at it)
+    u32 keyset_sel;            // the selected set: what a launch without a map runs under
+    const u32* keyset_map;     // [instances] set of every instance, or null; set per launch in the launch's copy of this block
 };
 
 // ---- the kernel-class rule: which blind-rotation family a context runs, and everything that follows from it -----------
@@ -168,7 +184,6 @@ struct DagParams : DagRearm {
     const uint8_t* expect;        // [instances][n_checks] expected messages (0..3)
     u32 n_checks;
     u32 repair;                   // != 0: a mismatching row is overwritten with the trivial ciphertext of the expected message
-    const int8_t* s8;             // the LWE secret as k_lwe_check reads it
     bce_check_report* report;     // the context's report block and mismatch log (bce_check_reset / bce_check_get)
     bce_check_entry* log;
 };
@@ -248,7 +263,7 @@ hipError_t launch_pool_pack(const DevParams& P, const bce_gate_desc* d_descs, u3
 
 // Verify mode on the device (k_lwe_check; reference: the decrypt-compare-repair of every gate output, src/gate.cpp:153-160).
 // Item i = (check i % count, instance i / count) reads pool row d_slots[i % count] + (i / count) * slot_stride and the
-// expected bit d_expect[(i / count) * expect_stride + i % count]; phase = b - <a, s> mod q with s = int8[n] in {-1, 0, 1},
+// expected bit d_expect[(i / count) * expect_stride + i % count]; phase = b - <a, s> mod q with s = int8[n] in {-1, 0, 1} of the instance's key set,
 // got = Round(4 phase / q), err = centred(phase - expect q/4).  Counters go to *d_report with agent-scope atomics, every
 // mismatch (got != expect) to d_log[kCheckLogCap] while it has room.  repair != 0: a mismatching row is overwritten with the
 // TRIVIAL ciphertext (0, ..., 0, expect q/4) -- not the reference's Encrypt(sk, bit): no device PRNG, no host round trip,
@@ -256,7 +271,7 @@ hipError_t launch_pool_pack(const DevParams& P, const bce_gate_desc* d_descs, u3
 // No allocation, no synchronisation, counters are never reset here: the launch can be captured into a hipGraph.
 constexpr u32 kCheckLogCap = 4096;
 constexpr u32 kCheckWaves = 4;       // items a workgroup works on at a time (one wave each)
-hipError_t launch_lwe_check(const DevParams& P, const int8_t* d_s, const u32* d_slots, const uint8_t* d_expect, u32 count,
+hipError_t launch_lwe_check(const DevParams& P, const u32* d_slots, const uint8_t* d_expect, u32 count,
                             u32 expect_stride, u32 instances, u32 slot_stride, int repair, u32 tag, bce_check_report* d_report,
                             bce_check_entry* d_log, hipStream_t s);
 

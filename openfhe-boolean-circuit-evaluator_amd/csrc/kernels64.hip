@@ -273,7 +273,7 @@ __global__ __launch_bounds__(128 * DG) void k_blind_rotate64(DevParams P, const 
 
     const ulonglong2 ninv = make_ulonglong2(P.Ninv64, P.Ninv64_s);
     constexpr size_t rgsw = (size_t)R * 2 * N;
-    const u64* __restrict__ bsk = P.bsk64;
+    const u64* __restrict__ bsk = static_cast<const u64*>(key_set(P, blockIdx.x / n_desc).bsk);   // this instance's key set
     const u32 nsteps = AP ? n * P.dR : n;
     BCE_PROF_INIT();
     for (u32 step = 0; step < nsteps; ++step) {
@@ -1056,9 +1056,10 @@ struct WdLds {
 // V: a WdVariant; PERSIST (dataflow kernel, k_bootstrap_dag64): called from a loop -- the thread index is opaque per call so
 // that the compiler cannot split the caller's loop on it, and nothing leaves through acc_out
 template <class V, bool PERSIST = false, typename PT = DevParams>
-__device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g, const u32 soff, const u32 boot, double* smemd,
+__device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g, const u32 inst, const u32 soff, const u32 boot, double* smemd,
                                              u64* __restrict__ acc_out, u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks) {
-    // one gate bootstrap by one workgroup; `boot` = index of the bootstrap in the launch (acc_out / dbg rows).
+    // one gate bootstrap by one workgroup; `inst` = its instance (key set: key_set, gate_front.hpp), `boot` = index of the
+    // bootstrap in the launch (acc_out / dbg rows).
     constexpr int LOGN = V::LOGN, DG = V::DG;
     constexpr bool AP = V::AP, SPLIT = V::SPLIT, W16 = V::W16, FOLD = V::FOLD, FUSE = V::FUSE, W1 = V::W1, KN = V::KN;
     static_assert(!PERSIST || FUSE, "persistent callers rely on the fused tail");
@@ -1097,7 +1098,7 @@ __device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g,
     __syncthreads();
 
     constexpr size_t rgsw = (size_t)R * 2 * N;
-    const double* __restrict__ bsk = reinterpret_cast<const double*>(P.bsk64);
+    const double* __restrict__ bsk = static_cast<const double*>(key_set(P, inst).bsk);   // the instance's key set
     // SignedDigitDecompose: representative of the reference (canonical x, `x < Q/2 ? x : x - Q`), closed-form digits
     const double dlo = -(double)((P.Q64 + 1) / 2), dhi = (double)((P.Q64 - 3) / 2);
     const double Bd = (double)(1u << P.gBits), invB = 1.0 / Bd, halfB = 0.5 * Bd;
@@ -1351,7 +1352,7 @@ __device__ __forceinline__ void bootstrap64d(const PT& P, const bce_gate_desc g,
         __syncthreads();
         u32* rowidx = reinterpret_cast<u32*>(dct);                                      // digit rows + exchange buffers: all dead
         u64* red = reinterpret_cast<u64*>(rowidx + ((N * P.dKS + 3) & ~3u));
-        fused_tail_outputs<T, PERSIST>(P, g, soff, reinterpret_cast<const u64*>(acc), rowidx, red, boot, dbg_lweN, dbg_ks);
+        fused_tail_outputs<T, PERSIST>(P, g, inst, soff, reinterpret_cast<const u64*>(acc), rowidx, red, boot, dbg_lweN, dbg_ks);
     }
 }
 
@@ -1360,7 +1361,8 @@ __global__ __launch_bounds__(V::T) void k_blind_rotate64d(DevParams P, const bce
                                                           u32 slot_stride, u64* __restrict__ acc_out,
                                                           u32* __restrict__ dbg_lweN, u32* __restrict__ dbg_ks) {
     extern __shared__ __align__(16) double smemd[];
-    bootstrap64d<V>(P, descs[blockIdx.x % n_desc], (blockIdx.x / n_desc) * slot_stride, blockIdx.x, smemd, acc_out, dbg_lweN, dbg_ks);
+    const u32 inst = blockIdx.x / n_desc;
+    bootstrap64d<V>(P, descs[blockIdx.x % n_desc], inst, inst * slot_stride, blockIdx.x, smemd, acc_out, dbg_lweN, dbg_ks);
 }
 
 // Dataflow evaluation on the config-5 kernel (dag_sched.hpp): one persistent 1,024-thread workgroup per CU (the LDS holds
@@ -1371,7 +1373,7 @@ __global__ __launch_bounds__(V::T) void k_bootstrap_dag64(const DevParams* Pp, c
     extern __shared__ __align__(16) double smemd[];
     u32* mbox = reinterpret_cast<u32*>(smemd);
     dag_worker(Pp, Dp, mbox, [&](ConstDagParams& D, u32 t, u32 k) {
-        bootstrap64d<V, true>(*as_constant<ConstDevParams>(Pp), D.tasks[t], D.slot_base + k * D.slot_stride, 0, smemd + WdLds::mbox,
+        bootstrap64d<V, true>(*as_constant<ConstDevParams>(Pp), D.tasks[t], k, D.slot_base + k * D.slot_stride, 0, smemd + WdLds::mbox,
                               nullptr, nullptr, nullptr);
     });
 }
